@@ -18,8 +18,18 @@ index built once per node (rank 0, shared through /dev/shm) and uploaded by ever
 no data-path collective -- gloo carries only the barriers and the max-over-ranks time.
 
 Prints ONE JSON line on rank 0 (contract in the task statement), including `roofline`
-(algorithmic bytes of the alignment kernel per launch / its HIP-event time per launch)
-and `cpu_baseline` (the oracle/ C restatement on the host cores, same reads).
+(algorithmic bytes of the alignment kernel per launch / its HIP-event time per launch,
+both taken from the timed steps themselves).
+
+A plain run does only what the headline needs: set-up, warm-up, the timed steps, the
+`--dump-outputs` files and the line.  `--full` adds every leg that takes runs of its own:
+`cpu_baseline` and `parity` (the oracle/ C restatement on the host cores, same reads), the
+device-resident rate, the lookup / copy / gather ceilings, SAM records, and the paired,
+`snap-rna single` and RNA paired legs (`--no-extras`, `--no-cpu-baseline`, `--paired-pairs 0`,
+... trim a full run).
+
+`--dump-outputs DIR` writes the records of the last timed step (rank 0's shard), one
+`DIR/<field>.npy` per record field: see dump_outputs().
 """
 import argparse
 import hashlib
@@ -554,6 +564,34 @@ def rna_leg(args, idx, local, build_threads):
         shutil.rmtree(work, ignore_errors=True)
 
 
+DUMP_FIELDS = (("location", np.float64), ("score", np.float32), ("mapq", np.float32), ("result", np.float32),
+               ("direction", np.float32), ("flags", np.float32), ("nLookups", np.float32),
+               ("nLocationsScored", np.float32), ("popularSeedsSkipped", np.float32), ("nHitsIgnored", np.float32),
+               ("probabilityOfAllCandidates", np.float64), ("probabilityOfBestCandidate", np.float64))
+DUMP_MAX_BYTES = 64_000_000
+
+
+def dump_outputs(path, res):
+    """--dump-outputs: the records a caller of the timed path received in the last timed step, one
+    `<field>.npy` per field of snapgpu_result_t that describes the alignment (every value is exact in
+    the float type chosen: locations are below 2^32, the counters far below 2^24).  The four
+    instrumentation counters (nProbes, nHitWords, nOverflowLists, nElements) count accesses of the
+    device's own table layout and are left out.  At most DUMP_MAX_BYTES in all: a larger batch is
+    cut to a fixed, seeded sample of its records, whose indices go to `sample_index.npy`."""
+    os.makedirs(path, exist_ok=True)
+    n = len(res)
+    per_record = sum(np.dtype(t).itemsize for _, t in DUMP_FIELDS)
+    budget = DUMP_MAX_BYTES - 256 * (len(DUMP_FIELDS) + 1)   # the .npy headers
+    if n * per_record > budget:
+        keep = budget // (per_record + 8)
+        sel = np.sort(np.random.default_rng(20).choice(n, size=keep, replace=False))
+        np.save(os.path.join(path, "sample_index.npy"), sel.astype(np.float64))
+        res = res[sel]
+    for name, t in DUMP_FIELDS:
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(res[name]).astype(t))
+    return len(res)
+
+
 def timed_steps(step, steps, dist, sync, own=None):
     """Barrier + sync on both sides of exactly `steps` steps; returns the max over ranks (this
     rank's own time is appended to `own` when given)."""
@@ -656,12 +694,21 @@ def main():
     ap.add_argument("--mode", choices=("stream", "sync"), default="stream",
                     help="stream: submit every step, wait once (a streaming caller); sync: one blocking call per step")
     ap.add_argument("--cpu-sample", type=int, default=1_000_000, help="reads timed on the CPU baseline")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip ceilings, CIGAR/SAM and parity legs")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg that takes runs of its own: the CPU baseline and parity, the "
+                         "device-resident rate, the ceilings, SAM records, the paired / single / RNA legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's records (rank 0's shard) as DIR/<field>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and parity")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip ceilings, CIGAR/SAM and parity legs")
     ap.add_argument("--oracle-standin", action="store_true",
                     help="CPU test of the N-rank launch path only: each rank runs the oracle/ restatement on its "
                          "shard instead of the GPU aligner; the line is marked `standin` and is not a measurement")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full:   # a plain run: the timed steps and the line only
+        args.no_extras = args.no_cpu_baseline = True
     self_launch(args, sys.argv[1:])
     _stdout_to_stderr()
     wl = dict(WORKLOADS[args.workload])
@@ -742,10 +789,14 @@ def main():
 
     own = []
     elapsed = timed_steps(step, args.steps, dist, sync, own)
-    if args.mode == "stream":
+    if args.mode == "stream" and args.steps > 1:
         assert np.array_equal(outs[0].view(np.uint8), outs[1].view(np.uint8))
     log(rank, f"timed {args.steps} steps: {elapsed:.3f}s")
-    res = out
+    # the records of the last timed step (stream mode alternates between the two arrays)
+    res = outs[(args.steps - 1) & 1] if args.mode == "stream" else out
+    if args.dump_outputs and rank == 0:
+        n_dumped = dump_outputs(args.dump_outputs, res)
+        log(rank, f"{n_dumped} of {len(res)} records written to {args.dump_outputs}")
     total_reads = wl["reads"] * world * args.steps
     value = total_reads / elapsed
     ms_per_step = elapsed * 1000.0 / args.steps

@@ -11,7 +11,7 @@ L=$PWD/snap-rnaseq_amd/snapgpu
 cp $L/libsnapgpu.so $L/libsnapgpu_cur.so
 for i in $(seq 1 $R); do
   for v in cur "$@"; do
-    SNAPGPU_LIB=$L/libsnapgpu_$v.so timeout -k 10 300 python bench.py --steps 10 --warmup 2 --no-extras --cpu-sample 200000 $EXTRA \
+    SNAPGPU_LIB=$L/libsnapgpu_$v.so timeout -k 10 300 python bench.py --full --steps 10 --warmup 2 --no-extras --cpu-sample 200000 $EXTRA \
       > $O/ab_${v}_$i.json 2> $O/ab_${v}_$i.err || { tail -5 $O/ab_${v}_$i.err; exit 1; }
   done
 done

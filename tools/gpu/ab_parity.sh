@@ -10,7 +10,7 @@ L=snap-rnaseq_amd/snapgpu
 for i in 1 2; do
   for v in cur "$@"; do
     if [ "$v" = cur ]; then lib=$PWD/$L/libsnapgpu.so; else lib=$PWD/$L/libsnapgpu_$v.so; fi
-    SNAPGPU_LIB=$lib timeout -k 10 300 python bench.py --steps 10 --warmup 2 --no-extras --cpu-sample 300000 \
+    SNAPGPU_LIB=$lib timeout -k 10 300 python bench.py --full --steps 10 --warmup 2 --no-extras --cpu-sample 300000 \
       > $O/ab_${v}_$i.json 2> $O/ab_${v}_$i.err || { tail -5 $O/ab_${v}_$i.err; exit 1; }
   done
 done

@@ -12,7 +12,7 @@ L=$PWD/snap-rnaseq_amd/snapgpu
 cp $L/libsnapgpu.so $L/libsnapgpu_cur.so
 for i in 1 2; do
   for v in cur "$@"; do
-    SNAPGPU_LIB=$L/libsnapgpu_$v.so timeout -k 10 300 python bench.py --steps 10 --warmup 2 --no-extras --cpu-sample 300000 \
+    SNAPGPU_LIB=$L/libsnapgpu_$v.so timeout -k 10 300 python bench.py --full --steps 10 --warmup 2 --no-extras --cpu-sample 300000 \
       > $O/ab_${v}_$i.json 2> $O/ab_${v}_$i.err || { tail -5 $O/ab_${v}_$i.err; exit 1; }
   done
 done

@@ -11,7 +11,7 @@ timeout -k 10 600 python -u -m pytest tests/test_order_long.py tests/test_long_r
 tail -1 $O/order_tests.log
 cp $L/libsnapgpu.so $L/libsnapgpu_cur.so
 for v in cur "$@" cur; do
-  SNAPGPU_LIB=$L/libsnapgpu_$v.so timeout -k 10 400 python bench.py --workload c3 --steps 5 --warmup 1 --no-extras \
+  SNAPGPU_LIB=$L/libsnapgpu_$v.so timeout -k 10 400 python bench.py --full --workload c3 --steps 5 --warmup 1 --no-extras \
     --cpu-sample 300000 > $O/c3_$v.json 2> $O/c3_$v.err || { tail -5 $O/c3_$v.err; exit 1; }
   python3 -c "import json; d=json.loads(open('$O/c3_$v.json').readline()); print('$v', round(d['value']/1e6,3), 'M reads/s', round(d['roofline']['kernel_ms_per_launch'],3), 'ms/launch', 'mismatches', d['parity']['mismatches'])"
 done

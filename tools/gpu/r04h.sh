@@ -18,7 +18,7 @@ for v in ('cur', 'r03'):
         r = d['roofline']
         print(v, i, round(d['value'] / 1e6, 3), 'ms/step', round(d['ms_per_step'], 2), 'kernel', round(r['kernel_ms_per_launch'], 2), 'launch', round(r['launch_duration_ms'], 2))
 PY
-timeout -k 10 600 python bench.py --steps 10 --warmup 2 --no-cpu-baseline > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
+timeout -k 10 600 python bench.py --full --steps 10 --warmup 2 --no-cpu-baseline > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
 python3 - <<'PY'
 import json; d=json.loads(open('gpurun_out/r04h/bench.json').readline())
 print('value', round(d['value']/1e6,3), 'kernel_ms', round(d['roofline']['kernel_ms_per_launch'],2))

@@ -10,7 +10,7 @@ SNAPGPU_LIB=$L/libsnapgpu_rna.so timeout -k 10 600 python -u -m pytest tests/tes
   tests/test_paired.py tests/test_rna_paired.py tests/test_multihit.py -x -v -m gpu --timeout 200 --timeout-method thread > $O/rna_tests.log 2>&1 || { tail -30 $O/rna_tests.log; exit 1; }
 tail -1 $O/rna_tests.log
 run() {   # name lib env-prefix round
-  SNAPGPU_LIB=$L/libsnapgpu_$2.so $3 timeout -k 10 300 python bench.py --steps 10 --warmup 2 --no-extras --cpu-sample 300000 \
+  SNAPGPU_LIB=$L/libsnapgpu_$2.so $3 timeout -k 10 300 python bench.py --full --steps 10 --warmup 2 --no-extras --cpu-sample 300000 \
     > $O/ab_$1_$4.json 2> $O/ab_$1_$4.err || { tail -5 $O/ab_$1_$4.err; exit 1; }
 }
 cp $L/libsnapgpu.so $L/libsnapgpu_cur.so

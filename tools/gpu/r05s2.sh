@@ -11,7 +11,7 @@ tail -1 $O/tests.log
 for i in 1 2; do
   for v in cur prev; do
     if [ $v = cur ]; then lib=$L/libsnapgpu.so; else lib=$L/libsnapgpu_prev.so; fi
-    SNAPGPU_LIB=$lib timeout -k 10 400 python bench.py --no-cpu-baseline --paired-pairs 0 > $O/b_${v}_$i.json 2> $O/b_${v}_$i.err || { tail $O/b_${v}_$i.err; exit 1; }
+    SNAPGPU_LIB=$lib timeout -k 10 400 python bench.py --full --no-cpu-baseline --paired-pairs 0 > $O/b_${v}_$i.json 2> $O/b_${v}_$i.err || { tail $O/b_${v}_$i.err; exit 1; }
     python3 -c "import json; d=json.loads(open('$O/b_${v}_$i.json').readline()); s=d['sam_records']; r=d['rna_paired']; print('$v', 'sam_format', round(s['sam_format_reads_per_s']/1e6,2), 'M lines/s; rna', round(r['value']/1e6,3), 'M reads/s', r['stage_ms'])"
   done
 done

@@ -6,13 +6,13 @@ export TMPDIR=/tmp SNAPGPU_TIMEOUT_S=120
 O=gpurun_out/r06e; mkdir -p $O
 timeout -k 10 600 python -u -m pytest tests/test_single.py tests/test_sorted.py tests/test_contamination.py tests/test_cigar.py tests/test_capi.py -x -v -m gpu --timeout 300 --timeout-method thread > $O/tests.log 2>&1 || { tail -30 $O/tests.log; exit 1; }
 tail -1 $O/tests.log
-timeout -k 10 600 python bench.py --steps 3 --warmup 1 --no-cpu-baseline --paired-pairs 0 --rna-pairs 0 > $O/bench.json 2> $O/bench.err || { tail $O/bench.err; exit 1; }
+timeout -k 10 600 python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --paired-pairs 0 --rna-pairs 0 > $O/bench.json 2> $O/bench.err || { tail $O/bench.err; exit 1; }
 python3 -c "import json; d=json.loads(open('$O/bench.json').readline()); s=d['single_e2e']; print('single', round(s['value']/1e6,3), s['stage_ms'], s['parity'].get('sha256_match'))"
 L=$PWD/snap-rnaseq_amd/snapgpu
 cp $L/libsnapgpu.so $L/libsnapgpu_cur.so
 for i in 1 2 3 4; do
   for v in cur pgrp; do
-    SNAPGPU_LIB=$L/libsnapgpu_$v.so timeout -k 10 300 python bench.py --steps 10 --warmup 2 --no-extras --cpu-sample 200000 \
+    SNAPGPU_LIB=$L/libsnapgpu_$v.so timeout -k 10 300 python bench.py --full --steps 10 --warmup 2 --no-extras --cpu-sample 200000 \
       > $O/ab_${v}_$i.json 2> $O/ab_${v}_$i.err || { tail -5 $O/ab_${v}_$i.err; exit 1; }
   done
 done

@@ -7,7 +7,7 @@ timeout -k 10 300 python -u -m pytest tests/test_single.py tests/test_sorted.py 
 tail -1 $O/tests.log
 for i in 1 2; do
   for w in mmap fwrite; do
-    SNAPGPU_SAM_WRITE=$w timeout -k 10 600 python bench.py --steps 2 --warmup 1 --no-cpu-baseline --paired-pairs 0 --rna-pairs 0 \
+    SNAPGPU_SAM_WRITE=$w timeout -k 10 600 python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --paired-pairs 0 --rna-pairs 0 \
       > $O/bench_${w}_$i.json 2> $O/bench_${w}_$i.err || { tail $O/bench_${w}_$i.err; exit 1; }
     python3 -c "import json; d=json.loads(open('$O/bench_${w}_$i.json').readline()); s=d['single_e2e']; print('$w', round(s['value']/1e6,3), s['stage_ms'], s['parity'].get('sha256_match'))"
   done
