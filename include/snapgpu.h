@@ -154,6 +154,22 @@ snapgpu_index_t *snapgpu_index_build(snapgpu_genome_t *genome, int seedLen, int 
  * exact bias of ComputeBiasTable (GenomeIndex.cpp:1109-1243, 294-346), at least 100 -- the
  * reference's load factor and probe chains. */
 snapgpu_index_t *snapgpu_index_build_ex(snapgpu_genome_t *genome, int seedLen, int nThreads, double slack);
+/* snapgpu_index_build_ex on HIP device `device`: seed scan, sort, run and overflow layout, hash
+ * placement and the table image are computed in HBM and copied into a host index.  Identity
+ * guarantee: slots, overflow, tableBase, tableSize, tableUsed, hasIupac and every
+ * snapgpu_index_info_t field are byte-identical to what snapgpu_index_build_ex(genome, seedLen,
+ * any nThreads, slack) returns, so the result serves save, share, lookup, get_view, every aligner
+ * and the oracle alike.  Same contract: takes ownership of `genome`, seedLen 16..31, slack <= 0
+ * => 0.3.  NULL (genome freed, snapgpu_last_error set) on a bad device or seedLen, on too little
+ * free device memory (asked of hipMemGetInfo before allocating; the message names SNAPGPU_ENOMEM,
+ * the bytes needed and the bytes free) and on any HIP error.  There is no fallback to the CPU
+ * builder. */
+snapgpu_index_t *snapgpu_index_build_gpu(snapgpu_genome_t *genome, int seedLen, double slack, int device);
+/* Diagnostic: wall seconds of the last successful snapgpu_index_build_gpu of this process by
+ * phase -- upload, scan, sort, runs, sizing, placement, write, download (8 doubles) -- and the
+ * most device memory it held at once.  SNAPGPU_EINVAL when there was none. */
+#define SNAPGPU_INDEX_BUILD_PHASES 8
+int snapgpu_index_build_gpu_stats(double phaseSeconds[SNAPGPU_INDEX_BUILD_PHASES], uint64_t *peakDeviceBytes);
 /* GenomeIndex::loadFromDirectory (GenomeIndex.cpp:844-963), reference on-disk format. */
 snapgpu_index_t *snapgpu_index_load(const char *directory);
 /* Write the reference on-disk format (GenomeIndex.cpp:646-710, Genome.cpp:125-158,

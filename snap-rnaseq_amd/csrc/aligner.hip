@@ -18,8 +18,10 @@
 #include "seed_lookup.h"
 #include "cigar.h"
 #include "internal.h"
+#include "large_copy.h"
 
 using namespace sgk;
+using snapgpu::uploadLarge;
 
 int snapgpu_internal_index_args(const snapgpu_aligner_t *a, sgk::KArgs *A, int *device);   // below
 
@@ -1493,52 +1495,6 @@ int waitLane(snapgpu_aligner_t *a, ExecLane &L) {
     if (a->failed) return waitEvent(a, nullptr);
     HIPCHK(hipEventRecord(L.done, L.stream));
     return waitEvent(a, L.done);
-}
-
-// Host -> device copy of a large pageable buffer through two pinned staging buffers: host
-// threads fill one while the DMA engine drains the other (the index tables, up to tens of
-// GB for a human-sized genome; a plain pageable hipMemcpy runs far below PCIe speed).
-int uploadLarge(hipStream_t s, void *dst, const void *src, uint64_t bytes) {
-    if (bytes == 0) return SNAPGPU_OK;
-    if (bytes < (64ull << 20)) {
-        HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s));
-        HIPCHK(hipStreamSynchronize(s));
-        return SNAPGPU_OK;
-    }
-    const uint64_t CH = 256ull << 20;
-    void *stg[2] = {nullptr, nullptr};
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    int rc = SNAPGPU_OK;
-    auto fail = [&](hipError_t e) {
-        snapgpu::setError(std::string("uploadLarge: ") + hipGetErrorString(e));
-        rc = SNAPGPU_EDEVICE;
-    };
-    hipError_t e;
-    for (int i = 0; i < 2 && rc == SNAPGPU_OK; i++) {
-        if ((e = hipHostMalloc(&stg[i], CH, hipHostMallocDefault)) != hipSuccess) fail(e);
-        else if ((e = hipEventCreateWithFlags(&ev[i], hipEventDisableTiming)) != hipSuccess) fail(e);
-    }
-    const unsigned nt = snapgpu::hostThreads(8);
-    for (uint64_t off = 0, k = 0; off < bytes && rc == SNAPGPU_OK; off += CH, k++) {
-        const int b = (int)(k & 1);
-        const uint64_t len = std::min(CH, bytes - off);
-        if (k >= 2 && (e = hipEventSynchronize(ev[b])) != hipSuccess) { fail(e); break; }
-        std::vector<std::thread> th;
-        for (unsigned t = 0; t < nt; t++)
-            th.emplace_back([&, t] {
-                const uint64_t a0 = len * t / nt, a1 = len * (t + 1) / nt;
-                memcpy((char *)stg[b] + a0, (const char *)src + off + a0, a1 - a0);
-            });
-        for (auto &x : th) x.join();
-        if ((e = hipMemcpyAsync((char *)dst + off, stg[b], len, hipMemcpyHostToDevice, s)) != hipSuccess) { fail(e); break; }
-        if ((e = hipEventRecord(ev[b], s)) != hipSuccess) { fail(e); break; }
-    }
-    if ((e = hipStreamSynchronize(s)) != hipSuccess && rc == SNAPGPU_OK) fail(e);
-    for (int i = 0; i < 2; i++) {
-        if (stg[i]) hipHostFree(stg[i]);
-        if (ev[i]) hipEventDestroy(ev[i]);
-    }
-    return rc;
 }
 
 }  // namespace

@@ -60,6 +60,34 @@ static inline bool encodeSeed(const char *b, uint32_t L, int64_t *bases, int64_t
     return true;
 }
 
+// allocateHashTables sizing (GenomeIndex.cpp:294-346) under the exact bias table: see
+// snapgpu_index_build_ex.  One text for the CPU and the GPU builder, so both round alike.
+uint64_t sizeTables(Index &idx, double slack, uint64_t validSeeds, const uint64_t *distinct, const uint64_t *ovfWords,
+                    std::vector<uint64_t> &ovfBase) {
+    const uint32_t nT = idx.nTables, nBases = idx.genome->nBases;
+    uint64_t distinctTotal = 0;
+    for (uint32_t tb = 0; tb < nT; tb++) distinctTotal += distinct[tb];
+    idx.tableSize.assign(nT, 0);
+    idx.tableUsed.assign(nT, 0);
+    idx.tableBase.assign(nT, 0);
+    ovfBase.assign((size_t)nT + 1, 0);
+    const uint64_t avgSize = (uint64_t)((double)nBases * (slack + 1.0) / nT);
+    uint64_t totalSlots = 0;
+    for (uint32_t tb = 0; tb < nT; tb++) {
+        const double bias = distinctTotal ? ((double)distinct[tb] / (double)distinctTotal) *
+                                                ((double)validSeeds / (double)nBases) * nT : 0.0;
+        uint64_t size = (uint64_t)(unsigned)((double)avgSize * bias);
+        if (size < 100) size = 100;
+        if (size < distinct[tb] + 1) size = distinct[tb] + 1;   // Lookup needs an empty slot to stop
+        idx.tableSize[tb] = size;
+        idx.tableUsed[tb] = distinct[tb];
+        idx.tableBase[tb] = totalSlots;
+        totalSlots += size;
+        ovfBase[tb + 1] = ovfBase[tb] + ovfWords[tb];
+    }
+    return totalSlots;
+}
+
 }  // namespace snapgpu
 
 using namespace snapgpu;
@@ -212,27 +240,8 @@ snapgpu_index_t *snapgpu_index_build_ex(snapgpu_genome_t *genome, int seedLen, i
         distinct[tb] = d;
         ovfWords[tb] = ow;
     });
-    uint64_t distinctTotal = 0;
-    for (uint32_t tb = 0; tb < nT; tb++) distinctTotal += distinct[tb];
-    // allocateHashTables sizing (see above)
-    idx->tableSize.assign(nT, 0);
-    idx->tableUsed.assign(nT, 0);
-    idx->tableBase.assign(nT, 0);
-    std::vector<uint64_t> ovfBase(nT + 1, 0);
-    const uint64_t avgSize = (uint64_t)((double)nBases * (slack + 1.0) / nT);
-    uint64_t totalSlots = 0;
-    for (uint32_t tb = 0; tb < nT; tb++) {
-        const double bias = distinctTotal ? ((double)distinct[tb] / (double)distinctTotal) *
-                                                ((double)validSeeds / (double)nBases) * nT : 0.0;
-        uint64_t size = (uint64_t)(unsigned)((double)avgSize * bias);
-        if (size < 100) size = 100;
-        if (size < distinct[tb] + 1) size = distinct[tb] + 1;   // Lookup needs an empty slot to stop
-        idx->tableSize[tb] = size;
-        idx->tableUsed[tb] = distinct[tb];
-        idx->tableBase[tb] = totalSlots;
-        totalSlots += size;
-        ovfBase[tb + 1] = ovfBase[tb] + ovfWords[tb];
-    }
+    std::vector<uint64_t> ovfBase;
+    const uint64_t totalSlots = sizeTables(*idx, slack, validSeeds, distinct.data(), ovfWords.data(), ovfBase);
     const uint64_t totalOverflow = ovfBase[nT];
     if ((uint64_t)nBases + totalOverflow > 0xfffffff0ull) { setError("overflow table namespace exhausted"); delete idx; return nullptr; }
     idx->slots.allocate(3 * totalSlots);

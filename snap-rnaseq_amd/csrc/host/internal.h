@@ -85,6 +85,12 @@ struct Index {
     ~Index();
 };
 
+// index.cpp: the table sizing both index builders share (host double arithmetic, never restated on
+// the device).  From per-table distinct keys and overflow words: idx.tableSize / tableUsed /
+// tableBase and ovfBase[0 .. nTables] (each table's first overflow word); returns the slot total.
+uint64_t sizeTables(Index &idx, double slack, uint64_t validSeeds, const uint64_t *distinct, const uint64_t *ovfWords,
+                    std::vector<uint64_t> &ovfBase);
+
 // SNAPHashTable::hash (HashTable.h:60-72): MurmurHash3 fmix32.
 inline uint32_t hashKey(uint32_t key) {
     key ^= key >> 16;

@@ -153,12 +153,25 @@ class GenomeIndex:
         self._h = handle
 
     @classmethod
-    def build(cls, genome, seed_len=20, n_threads=0, slack=0.3):
+    def build(cls, genome, seed_len=20, n_threads=0, slack=0.3, device=None):
         """GenomeIndex::BuildIndexToDirectory semantics with the reference's table sizing
-        (slack as `snap-rna index -h`); takes ownership of the genome."""
+        (slack as `snap-rna index -h`); takes ownership of the genome.  device=None: the CPU
+        builder on n_threads host threads.  device=<int>: the same index, byte for byte, built on
+        that HIP device (snapgpu_index_build_gpu; n_threads unused); a failure raises, there is no
+        fallback to the CPU."""
         h = genome._h
         genome._h = None          # ownership moves to the index
+        if device is not None:
+            return cls(_check(lib().snapgpu_index_build_gpu(h, seed_len, float(slack), int(device)), "index_build"))
         return cls(_check(lib().snapgpu_index_build_ex(h, seed_len, n_threads, float(slack)), "index_build"))
+
+    @staticmethod
+    def gpu_build_stats():
+        """Wall seconds by phase and peak device bytes of this process's last build(device=<int>)."""
+        t = (C.c_double * len(_ffi.INDEX_BUILD_PHASES))()
+        peak = C.c_uint64()
+        _check(lib().snapgpu_index_build_gpu_stats(t, C.byref(peak)), "index_build_gpu_stats")
+        return {"phase_s": dict(zip(_ffi.INDEX_BUILD_PHASES, list(t))), "peak_device_bytes": peak.value}
 
     @classmethod
     def load(cls, directory):

@@ -235,6 +235,9 @@ class BucketInfo(C.Structure):   # snapgpu_bucket_info_t
                 ("buildMs", C.c_double)]
 
 
+# snapgpu_index_build_gpu_stats: the SNAPGPU_INDEX_BUILD_PHASES phases, in order
+INDEX_BUILD_PHASES = ("upload", "scan", "sort", "runs", "sizing", "placement", "write", "download")
+
 # (name, restype, argtypes)
 _PROTOS = [
     ("snapgpu_abi_version", C.c_int, []),
@@ -252,6 +255,8 @@ _PROTOS = [
     ("snapgpu_genome_piece_name", C.c_char_p, [C.c_void_p, C.c_int]),
     ("snapgpu_index_build", C.c_void_p, [C.c_void_p, C.c_int, C.c_int]),
     ("snapgpu_index_build_ex", C.c_void_p, [C.c_void_p, C.c_int, C.c_int, C.c_double]),
+    ("snapgpu_index_build_gpu", C.c_void_p, [C.c_void_p, C.c_int, C.c_double, C.c_int]),
+    ("snapgpu_index_build_gpu_stats", C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
     ("snapgpu_index_load", C.c_void_p, [C.c_char_p]),
     ("snapgpu_index_share", C.c_int, [C.c_void_p, C.c_char_p]),
     ("snapgpu_index_attach", C.c_void_p, [C.c_char_p]),

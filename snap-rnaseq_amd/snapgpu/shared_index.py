@@ -23,9 +23,11 @@ def _node_local():
     return int(os.environ.get("LOCAL_RANK", "0")), int(os.environ.get("LOCAL_WORLD_SIZE", "0"))
 
 
-def build_once(snapgpu, genome_bases, gen, seed_len, n_threads, rank, world, dist):
+def build_once(snapgpu, genome_bases, gen, seed_len, n_threads, rank, world, dist, device=None):
     """-> (GenomeIndex, info dict).  gen: Genome.synthetic keyword arguments.  One build per
-    node: the builder is LOCAL_RANK 0 (global rank 0 when the launcher sets no LOCAL_RANK)."""
+    node: the builder is LOCAL_RANK 0 (global rank 0 when the launcher sets no LOCAL_RANK).
+    device: None builds on the host threads; an integer builds the same index on that HIP device
+    of the builder rank (GenomeIndex.build(device=...))."""
     tag = f"{genome_bases}_{gen.get('seed', 0)}_{gen.get('n_contigs', 1)}_{gen.get('n_repeat_families', 0)}_{seed_len}"
     local, local_world = _node_local()
     builder = (local == 0) if "LOCAL_RANK" in os.environ else (rank == 0)
@@ -36,7 +38,7 @@ def build_once(snapgpu, genome_bases, gen, seed_len, n_threads, rank, world, dis
         g = snapgpu.Genome.synthetic(genome_bases, **gen)
         info["genome_s"] = round(time.time() - t0, 2)
         t1 = time.time()
-        idx = snapgpu.GenomeIndex.build(g, seed_len, n_threads)
+        idx = snapgpu.GenomeIndex.build(g, seed_len, n_threads, device=device)
         info["build_s"] = round(time.time() - t1, 2)
         info["built_by_this_rank"] = True
         ii = idx.info()
