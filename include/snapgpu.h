@@ -472,6 +472,45 @@ int snapgpu_sam_format_clipped(const snapgpu_index_t *idx, const snapgpu_reads_t
                                const char *readGroup, const uint32_t *frontClipped, const uint32_t *unclippedLength,
                                char *out, uint64_t cap, uint64_t *used);
 
+/* The same lines written on the GPU (sam_format.hip: a length pass, an exclusive scan into 64-bit
+ * line starts and a write pass that stages each workgroup's byte range in LDS), so that only the
+ * text crosses PCIe.  Byte-identical to snapgpu_sam_format / snapgpu_sam_format_clipped; the host
+ * formatter stays the default of the product paths.  There is no fallback to it: a failure is an
+ * error.  After the write pass a device check counts the lines whose last byte is not '\n' where
+ * the scan placed it: always 0, else the download fails with SNAPGPU_EDEVICE. */
+/* Resident: SAM lines of the records and CIGARs that snapgpu_align_resident + snapgpu_cigar_resident
+ * left in HBM for d.  reads is the batch d was uploaded from (n and lengths are checked); its clip
+ * state is used.  ids/idOffsets/idLengths NULL => reads->ids...; asynchronous on the side stream
+ * (the next snapgpu_align_resident waits for it before it rewrites the records).  SNAPGPU_EINVAL:
+ * no snapgpu_cigar_resident before, a reads batch that does not match d, an unclipped read longer
+ * than 1024 bases, no ids at all. */
+int snapgpu_sam_resident(snapgpu_aligner_t *a, snapgpu_device_reads_t *d, const snapgpu_reads_t *reads,
+                         const char *ids, const uint64_t *idOffsets, const uint32_t *idLengths,
+                         const char *readGroup);
+/* Waits; same size contract as snapgpu_sam_format: *used = bytes needed, SNAPGPU_EINVAL if cap is
+ * too small (nothing usable written). */
+int snapgpu_sam_download(snapgpu_aligner_t *a, snapgpu_device_reads_t *d, char *out, uint64_t cap, uint64_t *used);
+/* Batch form, for callers and tests that hold records and CIGARs on the host: the arguments of
+ * snapgpu_sam_format_clipped with the aligner in place of the index; uploads, runs the same
+ * kernels, downloads. */
+int snapgpu_sam_format_gpu(snapgpu_aligner_t *a, const snapgpu_reads_t *reads, const char *ids,
+                           const uint64_t *idOffsets, const uint32_t *idLengths, const snapgpu_result_t *results,
+                           const int32_t *editDistance, const uint32_t *nOps, const uint32_t *ops,
+                           const char *readGroup, const uint32_t *frontClipped, const uint32_t *unclippedLength,
+                           char *out, uint64_t cap, uint64_t *used);
+/* kernel time (length + scan + write, HIP events) and download time of the last call */
+int snapgpu_sam_last_ms(snapgpu_aligner_t *a, double *kernelMs, double *downloadMs);
+/* Diagnostic: the kernel time of the last call by pass -- length, scan, write (with the check). */
+int snapgpu_sam_pass_ms(snapgpu_aligner_t *a, double *lengthMs, double *scanMs, double *writeMs);
+/* The exact byte length of every line snapgpu_sam_format_clipped prints (same arguments, same
+ * validation; NULL clip arrays mean the batch's own clip state, or unclipped), computed on the host
+ * by the code the device length pass runs.  Needs no GPU. */
+int snapgpu_sam_line_lengths(const snapgpu_index_t *idx, const snapgpu_reads_t *reads, const char *ids,
+                             const uint64_t *idOffsets, const uint32_t *idLengths, const snapgpu_result_t *results,
+                             const int32_t *editDistance, const uint32_t *nOps, const uint32_t *ops,
+                             const char *readGroup, const uint32_t *frontClipped, const uint32_t *unclippedLength,
+                             uint32_t *lineLengths);
+
 /* The SAM header as SAMFormat::writeHeader (SAM.cpp:700-800) writes it for a FASTQ input:
  * @HD (SO:coordinate if sorted), rgLine or "@RG\tID:FASTQ\tSM:sample", @PG with CL:commandLine
  * and VN:version, one @SQ per genome piece.  Same size / error contract as snapgpu_sam_format. */

@@ -19,6 +19,7 @@
 #include "cigar.h"
 #include "internal.h"
 #include "large_copy.h"
+#include "sam_format.h"
 
 using namespace sgk;
 using snapgpu::uploadLarge;
@@ -1055,6 +1056,25 @@ struct EvSet {
     uint32_t *hCounter = nullptr;
 };
 
+// Device SAM formatter (sam_format.hip) state of one resident batch, or of the aligner's batch-form
+// calls: grow-only device buffers, as the CIGAR buffers are.
+struct SamState {
+    struct Buf { void *p = nullptr; uint64_t cap = 0; };
+    Buf aux;            // ids, id offsets / lengths, clip arrays, piece names, read group (one packed upload)
+    Buf len, scans, start, sums, text, bad;
+    Buf bases, quals;   // the reads where the unclipped extents pass the resident upload (or the batch form's reads)
+    Buf res, ed, nOps, ops;   // batch form: records and CIGARs from the host
+    std::vector<char> hAux;   // host copy of aux (alive while its upload may be in flight)
+    uint64_t fullBytes = 0;   // bytes of bases / quals valid in `bases` / `quals` (resident: 0 = the batch's own)
+    bool idsCached = false;   // aux holds the batch's own ids (reads->ids), with this read group:
+    std::string cachedRg;
+    bool cachedHasRg = false;
+    uint64_t n = 0, textBound = 0;
+    bool ran = false;
+    hipEvent_t ev[4] = {};    // before the length pass, after the check; after the length pass, after the scan
+    double downloadMs = 0;
+};
+
 struct snapgpu_device_reads {
     snapgpu_aligner_t *owner = nullptr;
     char *dBases = nullptr, *dQuals = nullptr;
@@ -1068,6 +1088,9 @@ struct snapgpu_device_reads {
     uint64_t n = 0;
     uint32_t maxLen = 0;
     int device = 0;
+    uint64_t bytes = 0;       // bases / quals bytes uploaded: the largest clipped end
+    uint64_t extentHash = 0;  // of the offsets and lengths uploaded (snapgpu_sam_resident checks its batch)
+    SamState sam;
 };
 
 struct snapgpu_aligner {
@@ -1150,6 +1173,12 @@ struct snapgpu_aligner {
     uint64_t exReadsCapN = 0, exReadsCapBytes = 0;
     void *cgPin = nullptr, *cgPinOut = nullptr;
     uint64_t cgPinCap = 0, cgPinOutCap = 0;
+    // device SAM formatter: the batch form's state, the state the last call used (snapgpu_sam_last_ms)
+    // and the pinned staging of the text download (two chunks in flight)
+    SamState samBatch;
+    SamState *samLast = nullptr;
+    void *samPin[2] = {};
+    hipEvent_t samPinDone[2] = {};
     hipStream_t stream() const { return lane[0].stream; }
 };
 
@@ -1468,6 +1497,17 @@ void devFree(const snapgpu_aligner_t *a, void *p) {
 
 void hostPinnedFree(void *p) { if (p) hipHostFree(p); }
 
+void samStateFree(const snapgpu_aligner_t *a, SamState &S) {
+    for (auto *b : {&S.aux, &S.len, &S.scans, &S.start, &S.sums, &S.text, &S.bad, &S.bases, &S.quals, &S.res, &S.ed, &S.nOps, &S.ops}) {
+        devFree(a, b->p);
+        b->p = nullptr;
+        b->cap = 0;
+    }
+    if (!(a && a->failed))
+        for (auto &e : S.ev)
+            if (e) { hipEventDestroy(e); e = nullptr; }
+}
+
 // Wait for an event, honouring SNAPGPU_TIMEOUT_S: on expiry the aligner is marked failed.
 int waitEvent(snapgpu_aligner_t *a, hipEvent_t ev) {
     if (a->failed) { snapgpu::setError("aligner failed earlier (device timeout): no further work accepted"); return SNAPGPU_EDEVICE; }
@@ -1709,6 +1749,11 @@ void snapgpu_aligner_free(snapgpu_aligner_t *a) {
     for (auto &b : a->aux) devFree(a, b.p);
     hostPinnedFree(a->cgPin);
     hostPinnedFree(a->cgPinOut);
+    samStateFree(a, a->samBatch);
+    for (int k = 0; k < 2; k++) {
+        if (!a->failed) hostPinnedFree(a->samPin[k]);
+        if (a->samPinDone[k]) hipEventDestroy(a->samPinDone[k]);
+    }
     snapgpu_device_reads_free(a->exReads);
     for (auto *b : {&a->exSearch, &a->exScratch, &a->exFound, &a->exHits, &a->exOff, &a->exDense}) devFree(a, b->p);
     delete a;
@@ -1862,6 +1907,13 @@ snapgpu_aligner_t *snapgpu_aligner_create(int device, const snapgpu_index_t *idx
     return a;
 }
 
+// running hash of a batch's (offset, length) pairs
+static inline uint64_t extentMix(uint64_t h, uint64_t off, uint32_t len) {
+    h = (h ^ off) * 0x9e3779b97f4a7c15ull;
+    h = (h ^ len) * 0xc2b2ae3d27d4eb4full;
+    return h ^ (h >> 29);
+}
+
 snapgpu_device_reads_t *snapgpu_reads_upload(snapgpu_aligner_t *a, const snapgpu_reads_t *r) {
     if (!a || !r) { snapgpu::setError("reads_upload: null"); return nullptr; }
     if (a->failed) { snapgpu::setError("aligner failed earlier (device timeout)"); return nullptr; }
@@ -1876,7 +1928,9 @@ snapgpu_device_reads_t *snapgpu_reads_upload(snapgpu_aligner_t *a, const snapgpu
         uint64_t endb = r->offsets[i] + r->lengths[i];
         if (endb > bytes) bytes = endb;
         if (r->lengths[i] > d->maxLen) d->maxLen = r->lengths[i];
+        d->extentHash = extentMix(d->extentHash, r->offsets[i], r->lengths[i]);
     }
+    d->bytes = bytes;
     bytes += 64;
     hipStream_t s = a->stream();
     HIPCHKN(hipMalloc(&d->dBases, bytes));
@@ -1903,6 +1957,8 @@ void snapgpu_device_reads_free(snapgpu_device_reads_t *d) {
     devFree(a, d->dBases); devFree(a, d->dQuals); devFree(a, d->dOffsets); devFree(a, d->dLengths);
     devFree(a, d->dOut); devFree(a, d->dDefer); devFree(a, d->dSeeds);
     devFree(a, d->dCigEd); devFree(a, d->dCigN); devFree(a, d->dCigOps);
+    if (a && a->samLast == &d->sam) const_cast<snapgpu_aligner_t *>(a)->samLast = nullptr;
+    samStateFree(a, d->sam);
     delete d;
 }
 
@@ -2979,6 +3035,343 @@ int snapgpu_cigar_last_ms(snapgpu_aligner_t *a, double *ms) {
     float f = 0;
     HIPCHK(hipEventElapsedTime(&f, a->cev[0], a->cev[1]));
     *ms = f;
+    return SNAPGPU_OK;
+}
+
+// ------------------------------------------------- SAM text on the device (sam_format.hip)
+static const uint64_t kSamChunk = 16ull << 20;   // bytes per pinned staging chunk of the text download
+
+static hipError_t samGrow(snapgpu_aligner_t *a, SamState::Buf &b, uint64_t bytes) {
+    if (bytes <= b.cap) return hipSuccess;
+    devFree(a, b.p);
+    b.p = nullptr;
+    b.cap = 0;
+    const uint64_t want = bytes + bytes / 4 + 256;
+    const hipError_t e = hipMalloc(&b.p, want);
+    if (e == hipSuccess) b.cap = want;
+    return e;
+}
+
+// The small host-side inputs of the formatter, packed for one upload.
+struct SamHostIn {
+    uint64_t n = 0;
+    const uint64_t *offsets = nullptr;   // null: already on the device (resident batch)
+    const uint32_t *lengths = nullptr;
+    const char *ids = nullptr;
+    const uint64_t *idOffsets = nullptr;
+    const uint32_t *idLengths = nullptr;
+    const uint32_t *front = nullptr, *unclipped = nullptr;
+    const char *rg = nullptr;
+};
+
+// Upload H's arrays, the piece names and the read group into S.aux (unless S still holds them:
+// skip) and point A at them; textBound = a bound on the bytes of text from the host's side.
+static int samPrepare(snapgpu_aligner_t *a, SamState &S, const SamHostIn &H, bool skip, samline::Args &A) {
+    const uint64_t n = H.n;
+    const snapgpu::Genome &g = *a->idx->genome;
+    std::vector<uint32_t> nameOff;
+    std::string names;
+    snapgpu::samPieceNames(g, nameOff, names);
+    const uint32_t rgLen = H.rg ? (uint32_t)strlen(H.rg) : 0u;
+    uint64_t idBytes = 0, bound = 0;
+    uint32_t maxName = 1;
+    for (size_t p = 0; p + 1 < nameOff.size(); p++) maxName = std::max(maxName, nameOff[p + 1] - nameOff[p]);
+    // per line: flags, POS, MAPQ, tabs, mate fields, tags and NM (< 64), RNAME, two soft clips and
+    // SNAPGPU_CIGAR_MAX_OPS ops of at most 11 bytes each
+    const uint64_t perLine = 64 + maxName + (H.rg ? 6 + rgLen : 0) + 22 + 11ull * SNAPGPU_CIGAR_MAX_OPS;
+    for (uint64_t i = 0; i < n; i++) {
+        idBytes = std::max<uint64_t>(idBytes, H.idOffsets[i] + H.idLengths[i]);
+        const uint32_t len = H.unclipped ? H.unclipped[i] : H.lengths[i];
+        bound += H.idLengths[i] + 2ull * std::min(len, samline::kMaxSeq) + perLine;
+    }
+    S.textBound = bound;
+    auto al16 = [](uint64_t x) { return (x + 15) & ~15ull; };
+    const uint64_t oIdOff = 0, oIdLen = al16(oIdOff + n * 8), oFront = al16(oIdLen + n * 4),
+                   oFull = al16(oFront + (H.unclipped ? n * 4 : 0)), oOff = al16(oFull + (H.unclipped ? n * 4 : 0)),
+                   oLen = al16(oOff + (H.offsets ? n * 8 : 0)), oNameOff = al16(oLen + (H.offsets ? n * 4 : 0)),
+                   oNames = al16(oNameOff + nameOff.size() * 4), oRg = al16(oNames + names.size()),
+                   oIds = al16(oRg + rgLen), bytes = al16(oIds + idBytes) + 16;
+    if (!skip) {
+        if (S.ran && S.ev[1]) HIPCHK(hipEventSynchronize(S.ev[1]));   // an earlier call's kernels may still read aux
+        HIPCHK(samGrow(a, S.aux, bytes));
+        S.hAux.assign(bytes, 0);
+        char *h = S.hAux.data();
+        if (n) {
+            memcpy(h + oIdOff, H.idOffsets, n * 8);
+            memcpy(h + oIdLen, H.idLengths, n * 4);
+            if (H.unclipped) { memcpy(h + oFront, H.front, n * 4); memcpy(h + oFull, H.unclipped, n * 4); }
+            if (H.offsets) { memcpy(h + oOff, H.offsets, n * 8); memcpy(h + oLen, H.lengths, n * 4); }
+        }
+        memcpy(h + oNameOff, nameOff.data(), nameOff.size() * 4);
+        memcpy(h + oNames, names.data(), names.size());
+        if (rgLen) memcpy(h + oRg, H.rg, rgLen);
+        if (idBytes) memcpy(h + oIds, H.ids, idBytes);
+        // on the otherwise idle copy stream, and waited for: the host copy may go, and the side
+        // stream (which may still be in the CIGAR kernel) is not waited for
+        HIPCHK(hipMemcpyAsync(S.aux.p, h, bytes, hipMemcpyHostToDevice, a->copyStream));
+        HIPCHK(hipStreamSynchronize(a->copyStream));
+    }
+    const char *d = (const char *)S.aux.p;
+    A.idOffsets = (const uint64_t *)(d + oIdOff);
+    A.idLengths = (const uint32_t *)(d + oIdLen);
+    A.front = H.unclipped ? (const uint32_t *)(d + oFront) : nullptr;
+    A.unclipped = H.unclipped ? (const uint32_t *)(d + oFull) : nullptr;
+    if (H.offsets) { A.offsets = (const uint64_t *)(d + oOff); A.lengths = (const uint32_t *)(d + oLen); }
+    A.pieceOffsets = a->dPieces;
+    A.pieceNameOff = (const uint32_t *)(d + oNameOff);
+    A.pieceNames = d + oNames;
+    A.nPieces = (int32_t)g.pieceOffsets.size();
+    A.rg = H.rg ? d + oRg : nullptr;
+    A.rgLen = rgLen;
+    A.ids = d + oIds;
+    return SNAPGPU_OK;
+}
+
+// Length pass, scan, write pass and check of n records on the side stream, into S's buffers.
+static int samLaunch(snapgpu_aligner_t *a, SamState &S, const samline::Args &A, uint64_t n) {
+    for (auto &e : S.ev)
+        if (!e) HIPCHK(hipEventCreate(&e));
+    S.n = n;
+    S.ran = true;
+    a->samLast = &S;
+    if (n == 0) return SNAPGPU_OK;
+    if (n > 0xffffffffull) { snapgpu::setError("batch too large"); return SNAPGPU_EINVAL; }
+    HIPCHK(samGrow(a, S.len, n * 4));
+    HIPCHK(samGrow(a, S.scans, n * sizeof(samline::Scans)));
+    HIPCHK(samGrow(a, S.start, (n + 1) * 8));
+    HIPCHK(samGrow(a, S.sums, samgpu::scanTiles(n) * 8));
+    HIPCHK(samGrow(a, S.bad, 16));
+    HIPCHK(samGrow(a, S.text, S.textBound + 16));
+    const samgpu::Buffers B{(uint32_t *)S.len.p, (samline::Scans *)S.scans.p, (uint64_t *)S.start.p, (uint64_t *)S.sums.p, (char *)S.text.p,
+                            S.textBound, (uint32_t *)S.bad.p, {S.ev[2], S.ev[3]}};
+    HIPCHK(hipEventRecord(S.ev[0], a->sideStream));
+    HIPCHK(samgpu::launch(A, n, B, a->sideStream));
+    HIPCHK(hipEventRecord(S.ev[1], a->sideStream));
+    return SNAPGPU_OK;
+}
+
+// Wait for S's kernels, check them, and copy the text to the caller's (pageable) buffer in chunks
+// through two pinned staging buffers: chunk k + 1 crosses PCIe while host threads copy chunk k out.
+static int samDownload(snapgpu_aligner_t *a, SamState &S, char *out, uint64_t cap, uint64_t *used) {
+    *used = 0;
+    S.downloadMs = 0;
+    if (S.n == 0) return SNAPGPU_OK;
+    if (int rc = waitEvent(a, S.ev[1])) return rc;
+    const auto t0 = std::chrono::steady_clock::now();
+    uint64_t total = 0;
+    uint32_t bad = 0;
+    HIPCHK(hipMemcpy(&total, (const uint64_t *)S.start.p + S.n, 8, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&bad, S.bad.p, 4, hipMemcpyDeviceToHost));
+    if (bad || total > S.textBound) {
+        char msg[160];
+        snprintf(msg, sizeof msg, "sam: %u of %llu lines do not end where the scan placed them (text %llu bytes, bound %llu)",
+                 bad, (unsigned long long)S.n, (unsigned long long)total, (unsigned long long)S.textBound);
+        snapgpu::setError(msg);
+        return SNAPGPU_EDEVICE;
+    }
+    *used = total;
+    if (total > cap || !out) { snapgpu::setError("sam_download: output buffer too small"); return SNAPGPU_EINVAL; }
+    for (int k = 0; k < 2; k++) {
+        if (!a->samPin[k]) HIPCHK(hipHostMalloc(&a->samPin[k], kSamChunk, hipHostMallocDefault));
+        if (!a->samPinDone[k]) HIPCHK(hipEventCreateWithFlags(&a->samPinDone[k], hipEventDisableTiming));
+    }
+    const uint64_t nChunks = (total + kSamChunk - 1) / kSamChunk;
+    auto issue = [&](uint64_t k) -> hipError_t {
+        const uint64_t b = k * kSamChunk, m = std::min(kSamChunk, total - b);
+        hipError_t e = hipMemcpyAsync(a->samPin[k & 1], (const char *)S.text.p + b, m, hipMemcpyDeviceToHost, a->sideStream);
+        return e != hipSuccess ? e : hipEventRecord(a->samPinDone[k & 1], a->sideStream);
+    };
+    const unsigned nt = snapgpu::hostThreads(16);
+    HIPCHK(issue(0));
+    for (uint64_t k = 0; k < nChunks; k++) {
+        if (k + 1 < nChunks) HIPCHK(issue(k + 1));
+        if (int rc = waitEvent(a, a->samPinDone[k & 1])) return rc;
+        const uint64_t b = k * kSamChunk, m = std::min(kSamChunk, total - b);
+        const char *src = (const char *)a->samPin[k & 1];
+        const unsigned t = m < (1u << 20) ? 1u : nt;
+        std::vector<std::thread> th;
+        for (unsigned j = 1; j < t; j++)
+            th.emplace_back([=] { memcpy(out + b + m * j / t, src + m * j / t, m * (j + 1) / t - m * j / t); });
+        memcpy(out + b, src, m / t);
+        for (auto &x : th) x.join();
+    }
+    S.downloadMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return SNAPGPU_OK;
+}
+
+int snapgpu_sam_resident(snapgpu_aligner_t *a, snapgpu_device_reads_t *d, const snapgpu_reads_t *reads,
+                         const char *ids, const uint64_t *idOffsets, const uint32_t *idLengths,
+                         const char *readGroup) {
+    if (!a || !d || !reads) { snapgpu::setError("sam_resident: null argument"); return SNAPGPU_EINVAL; }
+    if (a->failed) { snapgpu::setError("aligner failed earlier (device timeout)"); return SNAPGPU_EDEVICE; }
+    if (d->owner != a) { snapgpu::setError("sam_resident: the resident batch belongs to another aligner"); return SNAPGPU_EINVAL; }
+    uint64_t bytes = 0, hash = 0;
+    if (reads->n == d->n)
+        for (uint64_t i = 0; i < reads->n; i++) {
+            bytes = std::max<uint64_t>(bytes, reads->offsets[i] + reads->lengths[i]);
+            hash = extentMix(hash, reads->offsets[i], reads->lengths[i]);
+        }
+    if (reads->n != d->n || bytes != d->bytes || hash != d->extentHash) {
+        snapgpu::setError("sam_resident: the reads batch does not match the resident batch (n, offsets or lengths differ)");
+        return SNAPGPU_EINVAL;
+    }
+    const bool ownIds = !ids;
+    if (ownIds) { ids = reads->ids; idOffsets = reads->idOffsets; idLengths = reads->idLengths; }
+    if (!ids || !idOffsets || !idLengths) {
+        snapgpu::setError("sam_resident: no read ids (pass ids, or use a batch that carries them)");
+        return SNAPGPU_EINVAL;
+    }
+    const uint32_t *front = nullptr, *unclipped = nullptr;
+    if (int rc = snapgpu::samCheckClips(reads, nullptr, &front, &unclipped)) return rc;
+    if (!d->dCigEd) {
+        snapgpu::setError("sam_resident: no snapgpu_cigar_resident before snapgpu_sam_resident");
+        return SNAPGPU_EINVAL;
+    }
+    HIPCHK(hipSetDevice(a->device));
+    SamState &S = d->sam;
+    hipStream_t st = a->sideStream;
+    // snapgpu_reads_upload copied bases and qualities up to the largest clipped end: where the
+    // unclipped extents (SEQ / QUAL) pass it, the formatter reads a copy that holds them all
+    uint64_t need = d->bytes;
+    if (unclipped)
+        for (uint64_t i = 0; i < reads->n; i++)
+            need = std::max<uint64_t>(need, reads->offsets[i] - front[i] + unclipped[i]);
+    if (need > d->bytes && S.fullBytes != need) {
+        if (S.ran && S.ev[1]) HIPCHK(hipEventSynchronize(S.ev[1]));
+        const uint64_t tail = need - d->bytes;
+        S.hAux.assign(2 * tail, 0);
+        memcpy(S.hAux.data(), reads->bases + d->bytes, tail);
+        memcpy(S.hAux.data() + tail, reads->quals + d->bytes, tail);
+        for (int q = 0; q < 2; q++) {
+            SamState::Buf &b = q ? S.quals : S.bases;
+            HIPCHK(samGrow(a, b, need + 64));
+            HIPCHK(hipMemsetAsync((char *)b.p + need, 0, 64, a->copyStream));
+            HIPCHK(hipMemcpyAsync(b.p, q ? d->dQuals : d->dBases, d->bytes, hipMemcpyDeviceToDevice, a->copyStream));
+            HIPCHK(hipMemcpyAsync((char *)b.p + d->bytes, S.hAux.data() + q * tail, tail, hipMemcpyHostToDevice, a->copyStream));
+        }
+        HIPCHK(hipStreamSynchronize(a->copyStream));
+        S.fullBytes = need;
+    }
+    samline::Args A;
+    memset(&A, 0, sizeof(A));
+    const bool full = need > d->bytes;
+    A.bases = full ? (const char *)S.bases.p : d->dBases;
+    A.quals = full ? (const char *)S.quals.p : d->dQuals;
+    A.offsets = d->dOffsets;
+    A.lengths = d->dLengths;
+    A.res = d->dOut;
+    A.ed = d->dCigEd;
+    A.nOps = d->dCigN;
+    A.ops = d->dCigOps;
+    SamHostIn H;
+    H.n = reads->n; H.lengths = reads->lengths;   // offsets and lengths are resident: the lengths only bound the text
+    H.ids = ids; H.idOffsets = idOffsets; H.idLengths = idLengths;
+    H.front = front; H.unclipped = unclipped; H.rg = readGroup;
+    // the batch's own ids do not change: their upload is kept for the next call with the same read group
+    const bool skip = ownIds && S.idsCached && S.cachedHasRg == (readGroup != nullptr) &&
+                      (!readGroup || S.cachedRg == readGroup);
+    if (int rc = samPrepare(a, S, H, skip, A)) return rc;
+    S.idsCached = ownIds;
+    S.cachedHasRg = readGroup != nullptr;
+    S.cachedRg = readGroup ? readGroup : "";
+    // the records may come from pass sets on both lanes; the CIGAR kernel is ahead on this stream
+    for (auto &L : a->lane) {
+        HIPCHK(hipEventRecord(L.done, L.stream));
+        HIPCHK(hipStreamWaitEvent(st, L.done, 0));
+    }
+    if (int rc = samLaunch(a, S, A, reads->n)) return rc;
+    // the next pass set over these reads rewrites the records: it waits for the SAM kernels
+    HIPCHK(hipEventRecord(a->residentSideDone, st));
+    a->residentSidePending = true;
+    return SNAPGPU_OK;
+}
+
+int snapgpu_sam_download(snapgpu_aligner_t *a, snapgpu_device_reads_t *d, char *out, uint64_t cap, uint64_t *used) {
+    if (!a || !d || !used) { snapgpu::setError("sam_download: null argument"); return SNAPGPU_EINVAL; }
+    if (a->failed) { snapgpu::setError("aligner failed earlier (device timeout)"); return SNAPGPU_EDEVICE; }
+    if (!d->sam.ran) { snapgpu::setError("sam_download: no snapgpu_sam_resident before snapgpu_sam_download"); return SNAPGPU_EINVAL; }
+    HIPCHK(hipSetDevice(a->device));
+    return samDownload(a, d->sam, out, cap, used);
+}
+
+int snapgpu_sam_format_gpu(snapgpu_aligner_t *a, const snapgpu_reads_t *reads, const char *ids,
+                           const uint64_t *idOffsets, const uint32_t *idLengths, const snapgpu_result_t *results,
+                           const int32_t *editDistance, const uint32_t *nOps, const uint32_t *ops,
+                           const char *readGroup, const uint32_t *frontClipped, const uint32_t *unclippedLength,
+                           char *out, uint64_t cap, uint64_t *used) {
+    if (!a || !reads || !ids || !idOffsets || !idLengths || !results || !editDistance || !nOps || !ops || !used) {
+        snapgpu::setError("sam_format: null argument");
+        return SNAPGPU_EINVAL;
+    }
+    if (a->failed) { snapgpu::setError("aligner failed earlier (device timeout)"); return SNAPGPU_EDEVICE; }
+    if (int rc = snapgpu::samCheckClips(reads, nOps, &frontClipped, &unclippedLength)) return rc;
+    HIPCHK(hipSetDevice(a->device));
+    SamState &S = a->samBatch;
+    hipStream_t st = a->sideStream;
+    const uint64_t n = reads->n;
+    if (S.ran && S.ev[1]) HIPCHK(hipEventSynchronize(S.ev[1]));
+    uint64_t need = 0;
+    for (uint64_t i = 0; i < n; i++)
+        need = std::max<uint64_t>(need, unclippedLength ? reads->offsets[i] - frontClipped[i] + unclippedLength[i]
+                                                        : reads->offsets[i] + reads->lengths[i]);
+    samline::Args A;
+    memset(&A, 0, sizeof(A));
+    struct Up { SamState::Buf *b; const void *src; uint64_t bytes; };
+    const Up ups[] = {{&S.bases, reads->bases, need}, {&S.quals, reads->quals, need},
+                      {&S.res, results, n * sizeof(snapgpu_result_t)}, {&S.ed, editDistance, n * 4},
+                      {&S.nOps, nOps, n * 4}, {&S.ops, ops, n * SNAPGPU_CIGAR_MAX_OPS * 4}};
+    for (const Up &u : ups) {
+        HIPCHK(samGrow(a, *u.b, u.bytes + 64));
+        HIPCHK(hipMemsetAsync((char *)u.b->p + u.bytes, 0, 64, st));
+        if (u.bytes) HIPCHK(hipMemcpyAsync(u.b->p, u.src, u.bytes, hipMemcpyHostToDevice, st));
+    }
+    A.bases = (const char *)S.bases.p;
+    A.quals = (const char *)S.quals.p;
+    A.res = (const snapgpu_result_t *)S.res.p;
+    A.ed = (const int32_t *)S.ed.p;
+    A.nOps = (const uint32_t *)S.nOps.p;
+    A.ops = (const uint32_t *)S.ops.p;
+    SamHostIn H;
+    H.n = n; H.offsets = reads->offsets; H.lengths = reads->lengths;
+    H.ids = ids; H.idOffsets = idOffsets; H.idLengths = idLengths;
+    H.front = frontClipped; H.unclipped = unclippedLength; H.rg = readGroup;
+    if (int rc = samPrepare(a, S, H, false, A)) return rc;
+    if (int rc = samLaunch(a, S, A, n)) return rc;
+    return samDownload(a, S, out, cap, used);
+}
+
+int snapgpu_sam_last_ms(snapgpu_aligner_t *a, double *kernelMs, double *downloadMs) {
+    if (!a || !kernelMs || !downloadMs) return SNAPGPU_EINVAL;
+    if (!a->samLast) { snapgpu::setError("sam_last_ms: no device SAM call on this aligner"); return SNAPGPU_EINVAL; }
+    if (a->failed) { snapgpu::setError("aligner failed earlier (device timeout)"); return SNAPGPU_EDEVICE; }
+    HIPCHK(hipSetDevice(a->device));
+    SamState &S = *a->samLast;
+    float f = 0;
+    if (S.n) {
+        HIPCHK(hipEventSynchronize(S.ev[1]));
+        HIPCHK(hipEventElapsedTime(&f, S.ev[0], S.ev[1]));
+    }
+    *kernelMs = f;
+    *downloadMs = S.downloadMs;
+    return SNAPGPU_OK;
+}
+
+int snapgpu_sam_pass_ms(snapgpu_aligner_t *a, double *lengthMs, double *scanMs, double *writeMs) {
+    if (!a || !lengthMs || !scanMs || !writeMs) return SNAPGPU_EINVAL;
+    if (!a->samLast) { snapgpu::setError("sam_pass_ms: no device SAM call on this aligner"); return SNAPGPU_EINVAL; }
+    if (a->failed) { snapgpu::setError("aligner failed earlier (device timeout)"); return SNAPGPU_EDEVICE; }
+    HIPCHK(hipSetDevice(a->device));
+    SamState &S = *a->samLast;
+    float f[3] = {0, 0, 0};
+    if (S.n) {
+        HIPCHK(hipEventSynchronize(S.ev[1]));
+        HIPCHK(hipEventElapsedTime(&f[0], S.ev[0], S.ev[2]));
+        HIPCHK(hipEventElapsedTime(&f[1], S.ev[2], S.ev[3]));
+        HIPCHK(hipEventElapsedTime(&f[2], S.ev[3], S.ev[1]));
+    }
+    *lengthMs = f[0];
+    *scanMs = f[1];
+    *writeMs = f[2];
     return SNAPGPU_OK;
 }
 

@@ -140,6 +140,11 @@ struct SamLine {
     uint32_t mateFront = 0, mateClippedLen = 0, mateFullLen = 0;
 };
 void samAppendLine(std::string &o, const Genome &g, const SamLine &L);
+// sam.cpp: the input check the host and device formatters share (limits, clip arrays; NULL clip
+// arrays resolve to the batch's own clip state), and the genome's piece names as one blob
+int samCheckClips(const snapgpu_reads_t *reads, const uint32_t *nOps, const uint32_t **front,
+                  const uint32_t **unclipped);
+void samPieceNames(const Genome &g, std::vector<uint32_t> &nameOff, std::string &names);
 // `-so` for SAM output (SortedDataFilter::onNextBatch, SortedDataWriter.cpp:186-240, with
 // SAMFormat::getSortInfo, SAM.cpp:639-685): the records of `parts` (whole lines, in write order)
 // stable-sorted by their location key, concatenated

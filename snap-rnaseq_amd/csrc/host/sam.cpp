@@ -6,6 +6,7 @@
 // (snapgpu_cigar_resident / snapgpu_cigar_batch); this file only prints.  Lines
 // are formatted in parallel chunks and concatenated in read order.
 #include "internal.h"
+#include "sam_line.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -276,21 +277,16 @@ void samAppendLine(std::string &o, const Genome &g, const SamLine &L) {
 
 }  // namespace snapgpu
 
-namespace {
-}  // namespace
+namespace snapgpu {
 
-extern "C" int snapgpu_sam_format_clipped(const snapgpu_index_t *idx, const snapgpu_reads_t *reads, const char *ids,
-                                          const uint64_t *idOffsets, const uint32_t *idLengths,
-                                          const snapgpu_result_t *results, const int32_t *editDistance,
-                                          const uint32_t *nOps, const uint32_t *ops, const char *readGroup,
-                                          const uint32_t *frontClipped, const uint32_t *unclippedLength, char *out,
-                                          uint64_t cap, uint64_t *used) {
-    if (!idx || !reads || !ids || !idOffsets || !idLengths || !results || !editDistance || !nOps || !ops || !used) {
-        setError("sam_format: null argument");
-        return SNAPGPU_EINVAL;
-    }
+// The formatters' shared input check: the host formatter's limits (nOps, 1024 bases) and the clip
+// arrays, which must describe the batch's own clip state; NULL clip arrays resolve to that state
+// (or stay NULL: unclipped).  nOps NULL: the counts are cigar_kernel's own, still on the device.
+int samCheckClips(const snapgpu_reads_t *reads, const uint32_t *nOps, const uint32_t **front,
+                  const uint32_t **unclipped) {
+    const uint32_t *frontClipped = *front, *unclippedLength = *unclipped;
     for (uint64_t i = 0; i < reads->n; i++)
-        if (nOps[i] > SNAPGPU_CIGAR_MAX_OPS || (unclippedLength ? unclippedLength[i] : reads->lengths[i]) > 1024 ||
+        if ((nOps && nOps[i] > SNAPGPU_CIGAR_MAX_OPS) || (unclippedLength ? unclippedLength[i] : reads->lengths[i]) > 1024 ||
             (unclippedLength && (!frontClipped || unclippedLength[i] < reads->lengths[i] + frontClipped[i] ||
                                  reads->offsets[i] < frontClipped[i]))) {   // the reference writer: <= 500
             setError("sam_format: nOps > SNAPGPU_CIGAR_MAX_OPS, read longer than 1024 bases or bad clip arrays");
@@ -306,6 +302,104 @@ extern "C" int snapgpu_sam_format_clipped(const snapgpu_index_t *idx, const snap
         frontClipped = reads->frontClipped;
         unclippedLength = reads->unclippedLength;
     }
+    *front = unclippedLength ? frontClipped : nullptr;
+    *unclipped = unclippedLength;
+    return SNAPGPU_OK;
+}
+
+// The genome's pieces as sam_line.h takes them: name p = names[nameOff[p] .. nameOff[p + 1])
+void samPieceNames(const Genome &g, std::vector<uint32_t> &nameOff, std::string &names) {
+    nameOff.assign(1, 0u);
+    names.clear();
+    for (const auto &s : g.pieceNames) {
+        names += s;
+        nameOff.push_back((uint32_t)names.size());
+    }
+}
+
+}  // namespace snapgpu
+
+namespace {
+
+struct HostLines {
+    samline::Args A;
+    std::vector<uint32_t> nameOff;
+    std::string names;
+};
+
+int hostLineArgs(HostLines &H, const snapgpu_index_t *idx, const snapgpu_reads_t *reads, const char *ids,
+                 const uint64_t *idOffsets, const uint32_t *idLengths, const snapgpu_result_t *results,
+                 const int32_t *editDistance, const uint32_t *nOps, const uint32_t *ops, const char *readGroup,
+                 const uint32_t *frontClipped, const uint32_t *unclippedLength) {
+    if (!idx || !reads || !ids || !idOffsets || !idLengths || !results || !editDistance || !nOps || !ops) {
+        setError("sam_format: null argument");
+        return SNAPGPU_EINVAL;
+    }
+    if (int rc = samCheckClips(reads, nOps, &frontClipped, &unclippedLength)) return rc;
+    const Genome &g = *idx->genome;
+    samPieceNames(g, H.nameOff, H.names);
+    H.A = samline::Args{reads->bases, reads->quals, reads->offsets, reads->lengths, frontClipped, unclippedLength,
+                        ids, idOffsets, idLengths, results, editDistance, nOps, ops, g.pieceOffsets.data(),
+                        H.nameOff.data(), H.names.data(), (int32_t)g.pieceOffsets.size(),
+                        readGroup ? (uint32_t)strlen(readGroup) : 0u, readGroup};
+    return SNAPGPU_OK;
+}
+
+}  // namespace
+
+// sam_line.h's length of every line, on the host (what the device length pass computes)
+extern "C" int snapgpu_sam_line_lengths(const snapgpu_index_t *idx, const snapgpu_reads_t *reads, const char *ids,
+                                        const uint64_t *idOffsets, const uint32_t *idLengths,
+                                        const snapgpu_result_t *results, const int32_t *editDistance,
+                                        const uint32_t *nOps, const uint32_t *ops, const char *readGroup,
+                                        const uint32_t *frontClipped, const uint32_t *unclippedLength,
+                                        uint32_t *lineLengths) {
+    HostLines H;
+    if (int rc = hostLineArgs(H, idx, reads, ids, idOffsets, idLengths, results, editDistance, nOps, ops, readGroup,
+                              frontClipped, unclippedLength))
+        return rc;
+    if (!lineLengths && reads->n) {
+        setError("sam_line_lengths: null argument");
+        return SNAPGPU_EINVAL;
+    }
+    const samline::Serial g{nullptr};
+    for (uint64_t i = 0; i < reads->n; i++) lineLengths[i] = samline::lineLength(H.A, samline::fields(H.A, i, g));
+    return SNAPGPU_OK;
+}
+
+// sam_line.h's writer on one host thread (the code the device write pass runs per wave), for tests
+// that need no GPU: out must hold the sum of snapgpu_sam_line_lengths.
+extern "C" int snapgpu_internal_sam_line_write(const snapgpu_index_t *idx, const snapgpu_reads_t *reads,
+                                               const char *ids, const uint64_t *idOffsets, const uint32_t *idLengths,
+                                               const snapgpu_result_t *results, const int32_t *editDistance,
+                                               const uint32_t *nOps, const uint32_t *ops, const char *readGroup,
+                                               const uint32_t *frontClipped, const uint32_t *unclippedLength,
+                                               char *out) {
+    HostLines H;
+    if (int rc = hostLineArgs(H, idx, reads, ids, idOffsets, idLengths, results, editDistance, nOps, ops, readGroup,
+                              frontClipped, unclippedLength))
+        return rc;
+    const samline::Serial g{out};
+    uint64_t at = 0;
+    for (uint64_t i = 0; i < reads->n; i++) {
+        const samline::Fields F = samline::fields(H.A, i, g);
+        samline::write(H.A, i, F, at, g);
+        at += samline::lineLength(H.A, F);
+    }
+    return SNAPGPU_OK;
+}
+
+extern "C" int snapgpu_sam_format_clipped(const snapgpu_index_t *idx, const snapgpu_reads_t *reads, const char *ids,
+                                          const uint64_t *idOffsets, const uint32_t *idLengths,
+                                          const snapgpu_result_t *results, const int32_t *editDistance,
+                                          const uint32_t *nOps, const uint32_t *ops, const char *readGroup,
+                                          const uint32_t *frontClipped, const uint32_t *unclippedLength, char *out,
+                                          uint64_t cap, uint64_t *used) {
+    if (!idx || !reads || !ids || !idOffsets || !idLengths || !results || !editDistance || !nOps || !ops || !used) {
+        setError("sam_format: null argument");
+        return SNAPGPU_EINVAL;
+    }
+    if (int rc = samCheckClips(reads, nOps, &frontClipped, &unclippedLength)) return rc;
     Job J{idx, reads, ids, idOffsets, idLengths, results, editDistance, nOps, ops, readGroup,
           unclippedLength ? frontClipped : nullptr, unclippedLength};
     const uint64_t n = reads->n;

@@ -1,0 +1,200 @@
+// sam_format.hip -- SAM text of single-end records, written in HBM.
+//
+// Three passes over n records whose reads, records and CIGAR ops are device resident:
+//   length  one wave per record computes the exact byte length of its line (sam_line.h);
+//   scan    exclusive scan of the lengths into 64-bit line starts, start[n] = bytes of text;
+//   write   one workgroup per kRecsPerGroup consecutive records.  Their lines are one contiguous
+//           byte range of the text: each wave composes its records' lines in an LDS window of that
+//           range (lanes copy id, SEQ and QUAL bytes in parallel, lane 0 prints the few numbers),
+//           then the workgroup flushes the window with 16-byte lane-contiguous stores (the range's
+//           unaligned head and tail bytewise).  Nothing is stored outside [start[first], start[end)).
+// A last kernel counts the lines that do not end in '\n' where the scan says they end.
+#include "sam_format.h"
+
+namespace samgpu {
+
+using samline::Args;
+using samline::Fields;
+
+namespace {
+
+// A 64-lane wave as sam_line.h's group: bytes go to the LDS window [w0, w1) of the text.
+struct Wave {
+    char *lds;
+    uint64_t w0, w1;
+    uint32_t lane;
+    template <class P>
+    __device__ uint32_t firstOf(uint32_t n, P p) const {
+        for (uint32_t base = 0; base < n; base += 64) {
+            const uint32_t k = base + lane;
+            const bool hit = k < n && p(k);
+            const unsigned long long m = __ballot(hit);
+            if (m) return base + (uint32_t)__ffsll(m) - 1;
+        }
+        return n;
+    }
+    template <class F>
+    __device__ uint32_t sum(uint32_t n, F f) const {
+        uint32_t s = 0;
+        for (uint32_t k = lane; k < n; k += 64) s += f(k);
+        for (int o = 32; o; o >>= 1) s += __shfl_xor(s, o);
+        return s;
+    }
+    template <class F>
+    __device__ void copy(uint64_t at, uint32_t n, F f) const {
+        if (at + n <= w0 || at >= w1) return;
+        for (uint32_t k = lane; k < n; k += 64) put(at + k, f(k));
+    }
+    __device__ void put(uint64_t at, char c) const {
+        if (at >= w0 && at < w1) lds[at - w0] = c;
+    }
+    __device__ bool lead() const { return lane == 0; }
+};
+
+__global__ __launch_bounds__(256) void sam_length_kernel(Args A, uint64_t n, uint32_t *__restrict__ len,
+                                                         samline::Scans *__restrict__ scans) {
+    const Wave g{nullptr, 0, 0, threadIdx.x & 63u};
+    const uint64_t waves = (uint64_t)gridDim.x * 4u;
+    for (uint64_t r = (uint64_t)blockIdx.x * 4u + threadIdx.x / 64u; r < n; r += waves) {
+        const Fields F = samline::fields(A, r, g);
+        if (g.lane == 0) {
+            len[r] = samline::lineLength(A, F);
+            scans[r] = samline::Scans{F.qlen, (uint16_t)F.seqLen, (uint16_t)F.qualLen};   // both <= kMaxSeq
+        }
+    }
+}
+
+constexpr uint32_t kPerThread = kScanTile / 256;
+
+// sums[b] = sum of tile b's lengths
+__global__ __launch_bounds__(256) void sam_scan_sums_kernel(const uint32_t *__restrict__ len, uint64_t n,
+                                                            uint64_t *__restrict__ sums) {
+    __shared__ uint64_t sh[256];
+    const uint64_t base = (uint64_t)blockIdx.x * kScanTile + threadIdx.x * kPerThread;
+    uint64_t s = 0;
+    for (uint32_t j = 0; j < kPerThread; j++)
+        if (base + j < n) s += len[base + j];
+    sh[threadIdx.x] = s;
+    __syncthreads();
+    for (uint32_t o = 128; o; o >>= 1) {
+        if (threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) sums[blockIdx.x] = sh[0];
+}
+
+// inclusive scan of sh[0 .. 256) in place
+__device__ void scan256(uint64_t *sh) {
+    for (uint32_t o = 1; o < 256; o <<= 1) {
+        const uint64_t t = threadIdx.x >= o ? sh[threadIdx.x - o] : 0;
+        __syncthreads();
+        sh[threadIdx.x] += t;
+        __syncthreads();
+    }
+}
+
+// one workgroup: the tile sums become the tiles' first starts; *total = bytes of text
+__global__ __launch_bounds__(256) void sam_scan_tiles_kernel(uint64_t *__restrict__ sums, uint64_t nTiles,
+                                                             uint64_t *__restrict__ total) {
+    __shared__ uint64_t sh[256];
+    uint64_t carry = 0;
+    for (uint64_t b0 = 0; b0 < nTiles; b0 += 256) {
+        const uint64_t i = b0 + threadIdx.x;
+        const uint64_t v = i < nTiles ? sums[i] : 0;
+        sh[threadIdx.x] = v;
+        __syncthreads();
+        scan256(sh);
+        if (i < nTiles) sums[i] = carry + sh[threadIdx.x] - v;
+        carry += sh[255];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) *total = carry;
+}
+
+__global__ __launch_bounds__(256) void sam_scan_starts_kernel(const uint32_t *__restrict__ len, uint64_t n,
+                                                              const uint64_t *__restrict__ sums,
+                                                              uint64_t *__restrict__ start) {
+    __shared__ uint64_t sh[256];
+    const uint64_t base = (uint64_t)blockIdx.x * kScanTile + threadIdx.x * kPerThread;
+    uint32_t v[kPerThread];
+    uint64_t s = 0;
+    for (uint32_t j = 0; j < kPerThread; j++) {
+        v[j] = base + j < n ? len[base + j] : 0u;
+        s += v[j];
+    }
+    sh[threadIdx.x] = s;
+    __syncthreads();
+    scan256(sh);
+    uint64_t at = sums[blockIdx.x] + sh[threadIdx.x] - s;
+    for (uint32_t j = 0; j < kPerThread; j++) {
+        if (base + j < n) start[base + j] = at;
+        at += v[j];
+    }
+}
+
+__global__ __launch_bounds__(256) void sam_write_kernel(Args A, uint64_t n, const uint64_t *__restrict__ start,
+                                                        const samline::Scans *__restrict__ scans,
+                                                        char *__restrict__ out, uint64_t cap) {
+    __shared__ uint4 tile[kTileBytes / 16];
+    char *lds = reinterpret_cast<char *>(tile);
+    const uint64_t first = (uint64_t)blockIdx.x * kRecsPerGroup;
+    const uint64_t end = first + kRecsPerGroup < n ? first + kRecsPerGroup : n;
+    const uint64_t r0 = start[first], r1 = start[end];
+    if (r1 > cap) return;   // the host's bound on the text was too small: sam_check_kernel reports it
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x / 64u;
+    // windows are 16-byte aligned in the text, so an LDS chunk is a 16-byte aligned store
+    for (uint64_t w0 = r0 & ~15ull; w0 < r1; w0 += kTileBytes) {
+        const uint64_t w1 = w0 + kTileBytes < r1 ? w0 + kTileBytes : r1;
+        const Wave g{lds, w0, w1, lane};
+        for (uint64_t r = first + wave; r < end; r += 4) {
+            const uint64_t s = start[r], e = start[r + 1];
+            if (e <= w0 || s >= w1) continue;
+            const samline::Scans known = scans[r];
+            const Fields F = samline::fields(A, r, g, &known);
+            samline::write(A, r, F, s, g);
+        }
+        __syncthreads();
+        const uint32_t chunks = (uint32_t)((w1 - w0 + 15) / 16);
+        for (uint32_t c = threadIdx.x; c < chunks; c += 256) {
+            const uint64_t a = w0 + 16ull * c;
+            if (a >= r0 && a + 16 <= r1) {
+                *reinterpret_cast<uint4 *>(out + a) = tile[c];
+            } else {
+                const uint64_t lo = a > r0 ? a : r0, hi = a + 16 < r1 ? a + 16 : r1;
+                for (uint64_t b = lo; b < hi; b++) out[b] = lds[b - w0];
+            }
+        }
+        __syncthreads();
+    }
+}
+
+__global__ __launch_bounds__(256) void sam_check_kernel(const uint64_t *__restrict__ start, uint64_t n,
+                                                        const char *__restrict__ out, uint64_t cap,
+                                                        uint32_t *bad) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const uint64_t s = start[i], e = start[i + 1];
+    if (e <= s || e > cap || out[e - 1] != '\n') atomicAdd(bad, 1u);
+}
+
+}  // namespace
+
+hipError_t launch(const Args &A, uint64_t n, const Buffers &B, hipStream_t st) {
+    hipError_t e = hipMemsetAsync(B.bad, 0, sizeof(uint32_t), st);
+    if (e != hipSuccess) return e;
+    const uint64_t nTiles = scanTiles(n), nGroups = (n + kRecsPerGroup - 1) / kRecsPerGroup;
+    const uint64_t lenBlocks = (n + 3) / 4 < 65536 ? (n + 3) / 4 : 65536;
+    hipLaunchKernelGGL(sam_length_kernel, dim3((unsigned)lenBlocks), dim3(256), 0, st, A, n, B.len, B.scans);
+    if (B.mid[0] && (e = hipEventRecord(B.mid[0], st)) != hipSuccess) return e;
+    hipLaunchKernelGGL(sam_scan_sums_kernel, dim3((unsigned)nTiles), dim3(256), 0, st, B.len, n, B.sums);
+    hipLaunchKernelGGL(sam_scan_tiles_kernel, dim3(1), dim3(256), 0, st, B.sums, nTiles, B.start + n);
+    hipLaunchKernelGGL(sam_scan_starts_kernel, dim3((unsigned)nTiles), dim3(256), 0, st, B.len, n, B.sums, B.start);
+    if (B.mid[1] && (e = hipEventRecord(B.mid[1], st)) != hipSuccess) return e;
+    hipLaunchKernelGGL(sam_write_kernel, dim3((unsigned)nGroups), dim3(256), 0, st, A, n, B.start, B.scans,
+                       B.text, B.textCap);
+    hipLaunchKernelGGL(sam_check_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, B.start, n, B.text,
+                       B.textCap, B.bad);
+    return hipGetLastError();
+}
+
+}  // namespace samgpu

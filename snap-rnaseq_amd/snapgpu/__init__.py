@@ -282,6 +282,19 @@ class Reads:
         l = (C.c_uint32 * max(1, n))(*lens)
         return cls(_check(lib().snapgpu_reads_from_arrays(n, bytes(bases), bytes(quals), o, l), "reads_from_arrays"))
 
+    @classmethod
+    def from_arrays(cls, bases, quals, offsets, lengths):
+        """snapgpu_reads_from_arrays: read i = bases / quals [offsets[i], + lengths[i]) of two byte
+        buffers, taken as they are (any byte value, 0x00 included)."""
+        b = np.frombuffer(bytes(bases) + b"\0" * 16, dtype=np.uint8)
+        q = np.frombuffer(bytes(quals) + b"\0" * 16, dtype=np.uint8)
+        o = np.ascontiguousarray(np.resize(np.asarray(offsets, dtype=np.uint64), max(1, len(lengths))))
+        l = np.ascontiguousarray(np.resize(np.asarray(lengths, dtype=np.uint32), max(1, len(lengths))))
+        fn = lib().snapgpu_reads_from_arrays
+        return cls(_check(fn(len(lengths), C.cast(b.ctypes.data, C.c_char_p), C.cast(q.ctypes.data, C.c_char_p),
+                             C.cast(o.ctypes.data, C.POINTER(C.c_uint64)), C.cast(l.ctypes.data, C.POINTER(C.c_uint32))),
+                          "reads_from_arrays"))
+
     def slice(self, start, count):
         """A copy of reads [start, start + count) as a new batch."""
         r = self._p.contents
@@ -479,6 +492,32 @@ class BaseAligner:
         return ms.value
 
     # resident path (bench): upload once, time only the GPU passes
+    def sam_format(self, reads, ids, results, cigars, read_group="FASTQ", clip=None):
+        """The module-level sam_format on the GPU (snapgpu_sam_format_gpu: uploads records and
+        CIGARs, runs the resident path's kernels, downloads the text) -> bytes."""
+        args, keep, cap = _sam_inputs(reads, ids, results, cigars, read_group, clip)
+        used = C.c_uint64()
+        buf = np.empty(max(1, cap), dtype=np.uint8)
+        fn = lib().snapgpu_sam_format_gpu
+        rc = fn(self._h, *args, buf.ctypes.data, cap, C.byref(used))
+        if rc != 0 and used.value > cap:
+            buf = np.empty(used.value, dtype=np.uint8)
+            rc = fn(self._h, *args, buf.ctypes.data, used.value, C.byref(used))
+        _check(rc, "sam_format_gpu")
+        return buf[:used.value].tobytes()
+
+    def sam_ms(self):
+        """(kernel ms, download ms) of the last device SAM call (snapgpu_sam_last_ms)."""
+        k, d = C.c_double(), C.c_double()
+        _check(lib().snapgpu_sam_last_ms(self._h, C.byref(k), C.byref(d)), "sam_last_ms")
+        return k.value, d.value
+
+    def sam_pass_ms(self):
+        """(length, scan, write) kernel ms of the last device SAM call (snapgpu_sam_pass_ms)."""
+        v = [C.c_double() for _ in range(3)]
+        _check(lib().snapgpu_sam_pass_ms(self._h, *[C.byref(x) for x in v]), "sam_pass_ms")
+        return tuple(x.value for x in v)
+
     def upload(self, reads):
         return DeviceReads(self, reads)
 
@@ -643,11 +682,42 @@ class DeviceReads:
                                             c.nOps.ctypes.data, c.ops.ctypes.data), "cigar_download")
         return c
 
+    def run_sam(self, reads, ids=None, read_group="FASTQ"):
+        """SAM lines of the records and CIGARs run() + run_cigars() left in HBM, formatted on the
+        GPU (asynchronous).  reads: the batch this was uploaded from; ids: None for its own ids."""
+        rg = None if read_group is None else read_group.encode()
+        if ids is None:
+            self._sam_keep = None
+            args = [None, None, None]
+        else:
+            blob, offs, lens = _id_arrays(ids, reads.n)
+            self._sam_keep = (blob, offs, lens)
+            args = [blob, offs.ctypes.data, lens.ctypes.data]
+        _check(lib().snapgpu_sam_resident(self.aligner._h, self._h, reads._p, *args, rg), "sam_resident")
+
+    def sam(self, timing=None):
+        """The text run_sam() wrote -> bytes (waits).  timing: a dict that receives "done", the
+        time.perf_counter() at which the text was in host memory."""
+        used = C.c_uint64()
+        fn = lib().snapgpu_sam_download
+        rc = fn(self.aligner._h, self._h, None, 0, C.byref(used))
+        if rc != 0 and used.value == 0:
+            _check(rc, "sam_download")
+        buf = np.empty(max(1, used.value), dtype=np.uint8)
+        _check(fn(self.aligner._h, self._h, buf.ctypes.data, used.value, C.byref(used)), "sam_download")
+        if timing is not None:
+            timing["done"] = time.perf_counter()
+        return buf[:used.value].tobytes()
+
     def __del__(self):
         if getattr(self, "_h", None):
             lib().snapgpu_device_reads_free(self._h)
             self._h = None
 
+
+# the device SAM formatter's work split (csrc/sam_format.h: kRecsPerGroup, kScanTile)
+SAM_RECORDS_PER_WORKGROUP = 32
+SAM_SCAN_TILE = 2048
 
 CIGAR_OPS = "MIDNSHP=X"   # BAM op codes (SAM spec; BAMAlignment::CigarToCode)
 
@@ -726,6 +796,69 @@ def sam_format(index, reads, ids, results, cigars, read_group="FASTQ", clip=None
     if timing is not None:
         timing["format_s"] = time.perf_counter() - t0
     return buf[:used.value].tobytes()
+
+
+def _id_arrays(ids, n):
+    """ids (str/bytes) -> (blob, offsets u64, lengths u32) as the C formatters take them."""
+    idb = [i.encode() if isinstance(i, str) else bytes(i) for i in ids]
+    if len(idb) != n:
+        raise ValueError(f"{len(idb)} ids for {n} reads")
+    lens = np.zeros(max(1, n), dtype=np.uint32)
+    lens[:n] = [len(x) for x in idb]
+    offs = np.zeros(max(1, n), dtype=np.uint64)
+    if n > 1:
+        offs[1:n] = np.cumsum(lens[:n - 1], dtype=np.uint64)
+    return b"".join(idb) + b"\0", offs, lens
+
+
+def _sam_inputs(reads, ids, results, cigars, read_group, clip):
+    """The argument list snapgpu_sam_format_clipped takes after the index (and what keeps it alive)."""
+    n = reads.n
+    blob, offs, lens = _id_arrays(ids, n)
+    res = np.ascontiguousarray(results, dtype=RESULT_DTYPE)
+    if res.shape != (n,) or len(cigars.editDistance) != n:
+        raise ValueError("results / cigars do not have one entry per read")
+    ed = np.ascontiguousarray(cigars.editDistance, dtype=np.int32)
+    nops = np.ascontiguousarray(cigars.nOps, dtype=np.uint32)
+    ops = np.ascontiguousarray(cigars.ops, dtype=np.uint32)
+    rg = None if read_group is None else (read_group.encode() if isinstance(read_group, str) else bytes(read_group))
+    front = full = None
+    if clip is not None:
+        front = np.ascontiguousarray(clip[0], dtype=np.uint32)
+        full = np.ascontiguousarray(clip[1], dtype=np.uint32)
+        if front.shape != (n,) or full.shape != (n,):
+            raise ValueError("clip arrays do not have one entry per read")
+    keep = (blob, offs, lens, res, ed, nops, ops, rg, front, full)
+    ptr = lambda a: None if a is None else (a.ctypes.data if a.size else np.zeros(1, a.dtype).ctypes.data)
+    if n == 0:   # zero-size arrays have no address worth passing
+        keep += tuple(np.zeros(1, dtype=t) for t in (RESULT_DTYPE, np.int32, np.uint32, np.uint32))
+        args = [reads._p, blob, offs.ctypes.data, lens.ctypes.data, keep[-4].ctypes.data, keep[-3].ctypes.data,
+                keep[-2].ctypes.data, keep[-1].ctypes.data, rg, None, None]
+    else:
+        args = [reads._p, blob, offs.ctypes.data, lens.ctypes.data, res.ctypes.data, ed.ctypes.data, nops.ctypes.data,
+                ops.ctypes.data, rg, ptr(front), ptr(full)]
+    return args, keep, int(lens[:n].sum()) + 2 * int(reads._p.contents.totalBytes) + n * 512
+
+
+def sam_line_lengths(index, reads, ids, results, cigars, read_group="FASTQ", clip=None):
+    """Byte length of every line sam_format prints (snapgpu_sam_line_lengths: the host side of the
+    device formatter's length pass; needs no GPU) -> np.uint32 array."""
+    args, keep, _ = _sam_inputs(reads, ids, results, cigars, read_group, clip)
+    out = np.zeros(max(1, reads.n), dtype=np.uint32)
+    _check(lib().snapgpu_sam_line_lengths(index._h, *args, out.ctypes.data), "sam_line_lengths")
+    return out[:reads.n]
+
+
+def _sam_line_write(index, reads, ids, results, cigars, read_group="FASTQ", clip=None):
+    """The device write pass's line writer (csrc/sam_line.h) run on one host thread -> bytes (tests)."""
+    args, keep, _ = _sam_inputs(reads, ids, results, cigars, read_group, clip)
+    total = int(sam_line_lengths(index, reads, ids, results, cigars, read_group, clip).sum(dtype=np.uint64))
+    buf = np.empty(max(1, total), dtype=np.uint8)
+    fn = lib().snapgpu_internal_sam_line_write
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_void_p, C.POINTER(_ffi.Reads), C.c_char_p] + [C.c_void_p] * 6 + [C.c_char_p] + [C.c_void_p] * 3
+    _check(fn(index._h, *args, buf.ctypes.data), "sam_line_write")
+    return buf[:total].tobytes()
 
 
 def lv_batch(direction, tasks, device=0, engine="byte"):
