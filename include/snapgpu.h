@@ -409,17 +409,42 @@ int snapgpu_lv_batch(int device, int direction, uint32_t n,
                      const uint32_t *patLen, const int32_t *k,
                      int32_t *outScore, int32_t *outNetIndel, double *outProb);
 
-/* The same calls through the production bit-plane LV of align_kernel<128> / <256> (lv_group /
- * lv_prob_pair in align_score.h) instead of the byte-compare engine: unit parity for the LV
- * that scores every read of <= 256 bases.  Patterns of 1..253 bases: a batch whose patterns
- * are all <= 127 runs on 128-bit masks (align_kernel<128>), any longer pattern puts the whole
- * batch on 256-bit masks (align_kernel<256>); netIndel is reported for direction -1 only
- * (the aligner uses only the reverse call's, BaseAligner.cpp:1232). */
-int snapgpu_lv_group_batch(int device, int direction, uint32_t n,
-                           const char *texts, const uint64_t *textOff, const uint32_t *textLen,
-                           const char *patterns, const char *quals, const uint64_t *patOff,
-                           const uint32_t *patLen, const int32_t *k,
-                           int32_t *outScore, int32_t *outNetIndel, double *outProb);
+/* Diagnostic (no reference equivalent): scoring passes as align_kernel<128> (nw = 2, reads <= 128
+ * bases) and align_kernel<256> (nw = 4, reads <= 256) run them -- unit parity for the production
+ * bit-plane LV (lv_pass' two lv_group calls in every lane group, then lv_prob_groups; align_score.h).
+ * Pass i: the forward read reads/quals[readOff[i] .. +readLen[i]), seedLen[i], the limit k[i] (the
+ * lane-group size is chosen from it as the aligner does: 64/GS = 8, 4, 2, 1 groups at k <= 3, 7,
+ * 15, above) and SNAPGPU_LV_PASS_GROUPS candidate rows of 8 int64 in cand (row i * GROUPS + g is
+ * lane group g; rows beyond the pass's groups must be inactive):
+ *   genOff  offset in `genome` of the candidate's position 0
+ *   before, after  bytes of `genome` that belong to it before position 0 / from position 0 on
+ *           (positions outside never match; the reverse call reads up to MAX_K + 2 before 0, the
+ *           forward one up to 2 past glen)
+ *   dir     0, or 1: the reverse-complemented read, qualities reversed
+ *   s       seed offset in read[dir], 0 <= s <= n - seedLen
+ *   act     0: the group holds no servable candidate
+ *   glen    genome bytes available (BaseAligner.cpp:1161-1185), >= s + seedLen
+ *   rtl     text length of the reverse call (BaseAligner.cpp:1216-1220: s + 31)
+ * Out, per row: the forward and reverse distances (-1: above the limit k / k - e1, or not reached)
+ * and -- where both are >= 0 -- their match probabilities and the reverse path's netIndel. */
+#define SNAPGPU_LV_PASS_GROUPS 8
+int snapgpu_lv_pass_batch(int device, int nw, uint32_t nPasses, const char *reads, const char *quals,
+                          uint64_t readBytes, const uint64_t *readOff, const uint32_t *readLen,
+                          const int32_t *seedLen, const int32_t *k, const char *genome, uint64_t genomeBytes,
+                          const int64_t *cand, int32_t *outE1, int32_t *outE2, double *outP1, double *outP2,
+                          int32_t *outNetIndel);
+
+/* Diagnostic (no reference equivalent): the forced-mode prefilter of align_kernel<128> (forced_filter,
+ * align_score.h; lv_lane.h) on explicit tasks over the aligner's device genome: quad = 0 the lane-pair
+ * form (limits k <= 5), quad != 0 the lane-quad form (k <= 7).  Task i: read reads[readOff[i] ..
+ * +readLen[i]) (<= 128 bases), candidate location loc[i], dir[i] (1: reverse complement), seed offset
+ * s[i] in read[dir], limit k[i], act[i] (0: the lanes sit the pass out).  out[i] = 0 when the task is
+ * inactive or the window [loc, loc + n + 31) is not servable, else 1 << 31 | e1 << 8 | e2 << 11 with 7
+ * for a distance above its limit (e2 also when the reverse call is not reached). */
+int snapgpu_lv_filter_batch(snapgpu_aligner_t *a, int quad, uint32_t nTasks, const char *reads, uint64_t readBytes,
+                            const uint64_t *readOff, const uint32_t *readLen, const uint32_t *loc,
+                            const int32_t *dir, const int32_t *s, const int32_t *k, const int32_t *act,
+                            uint32_t *out);
 
 /* ------------------------------------------------- CIGAR / SAM records */
 /* The SAM writer's per-read work, on the GPU:

@@ -256,71 +256,18 @@ __device__ __forceinline__ int lv_group(GroupLdsT<NW> &G, uint8_t (*rows8)[WAVE]
     return rowsRun;
 }
 
-// Match probabilities of the recorded forward and reverse LV paths of group g
-// (LandauVishkin.h:376-431), lane-parallel: lanes 0..30 take forward path steps
-// 1..31, lanes 32..62 reverse steps.  The reference merges runs of one action
-// (continuing while the matched run between them is empty); an indel run gives one
-// factor indel[cnt], X steps one phred factor each at offset L0 + sum of earlier
-// steps' (+-1 + matched).  Factors are fetched in parallel and multiplied in the
-// reference's order (x * 1.0 == x, so steps without a factor multiply by 1.0).
-template <int NW>
-__device__ __forceinline__ void lv_prob_pair(const DevTables *tab, const GroupLdsT<NW> &G, int g, int pbase, int n, int s0,
-                                             int t0, const char *fwdQ, uint32_t rcRead, double &p1, double &p2, int &net2) {
-    const int lane = lane_id();
-    const int dx = lane >> 5, j = (lane & 31) + 1;               // step j of direction dx
-    const int e = G.plen[dx][g];
-    const int L0 = G.pL0[dx][g];
-    const bool valid = j <= e;
-    const int a = valid ? G.pa[dx][pbase + j] : -1;
-    const int pmv = valid ? G.pm[dx][pbase + j] : 0;
-    const int an = j + 1 <= e ? G.pa[dx][pbase + j + 1] : -2;
-    const bool runEnd = valid && (j == e || pmv != 0 || an != a);
-    // offset before step j: inclusive scan of delta over the half-wave, minus own delta
-    const int delta = valid ? (a == 1 ? -1 : 1) + pmv : 0;
-    // inclusive scan over each half-wave in DPP, no LDS round trips: Hillis-Steele inside each
-    // 16-lane row, then rows 1 and 3 add the last lane of rows 0 and 2 (row_bcast:15)
-    int incl = delta;
-    incl += __builtin_amdgcn_update_dpp(0, incl, 0x111, 0xf, 0xf, true);   // row_shr:1
-    incl += __builtin_amdgcn_update_dpp(0, incl, 0x112, 0xf, 0xf, true);   // row_shr:2
-    incl += __builtin_amdgcn_update_dpp(0, incl, 0x114, 0xf, 0xf, true);   // row_shr:4
-    incl += __builtin_amdgcn_update_dpp(0, incl, 0x118, 0xf, 0xf, true);   // row_shr:8
-    incl += __builtin_amdgcn_update_dpp(0, incl, 0x142, 0xa, 0xf, false);  // row_bcast:15 into rows 1, 3
-    const int offset = L0 + incl - delta;
-    // indel run length = distance to the previous run end of this direction
-    const uint64_t ends = ballot(runEnd);
-    const uint64_t below = (ends >> (lane & 32)) & ((1ull << (lane & 31)) - 1);
-    const int prevEnd = below ? 63 - __builtin_clzll(below) : -1;   // lane index within the half
-    const int cnt = (lane & 31) - prevEnd;
-    const int patternLen = dx ? s0 : n - t0;
-    const int p0 = dx ? s0 - 1 : t0;
-    int qi = offset < 0 ? 0 : offset;
-    if (qi > patternLen - 1) qi = patternLen - 1;
-    const int DIR = dx ? -1 : 1;
-    double f = 1.0;
-    if (valid && a == 0) {   // quality of read[dir] position p: the forward read's, reversed for RC
-        const int p = p0 + DIR * qi;
-        f = g_tab.phred[(uint8_t)fwdQ[rcRead ? n - 1 - p : p]];
-    }
-    else if (runEnd) f = g_tab.indel[cnt];
-    const double perf = lane == 0 || lane == 32 ? g_tab.perfect[patternLen - e] : 1.0;
-    const int e1 = G.plen[0][g], e2 = G.plen[1][g];
-    double q = 1.0;
-    for (int i = 0; i < e1; i++) q *= readlaned(f, i);
-    p1 = q * readlaned(perf, 0);
-    q = 1.0;
-    for (int i = 0; i < e2; i++) q *= readlaned(f, 32 + i);
-    p2 = q * readlaned(perf, 32);
-    const uint64_t ins = ballot(valid && dx == 1 && a == 2), del = ballot(valid && dx == 1 && a == 1);
-    net2 = __popcll(ins) - __popcll(del);
-}
-
-// The same match probabilities for every group of a pass at once, right after its LV calls (verdict
-// r5 #2: the factor loads of all the pass's possible successes are issued together, before the
-// in-order apply, instead of one success at a time inside it).  Lane l: direction dx = l >> 5, path
+// Match probabilities of the recorded forward and reverse LV paths (LandauVishkin.h:376-431) of every
+// group of a pass at once, right after its LV calls (the factor loads of all the pass's possible
+// successes are issued together, before the in-order apply, instead of one success at a time inside
+// it).  The reference merges runs of one action (continuing while the matched run between them is
+// empty); an indel run gives one factor indel[cnt], X steps one phred factor each at offset L0 + sum of
+// earlier steps' (+-1 + matched).  Factors are fetched in parallel and multiplied in the reference's
+// order (x * 1.0 == x, so steps without a factor multiply by 1.0).  Lane l: direction dx = l >> 5, path
 // slot sl = l & 31 of group g = sl / S (S = GS / 2 slots per group, G.pa / G.pm layout), step j = sl % S
-// (steps 1..e; the slot j = 0 is never a step and its lane leads the segment).  Per segment the
-// arithmetic of lv_prob_pair: offsets from a segmented inclusive scan of the step deltas, indel run
-// lengths back to the segment's previous run end, one factor per step, multiplied in step order at the
+// (steps 1..e; the slot j = 0 is never a step and its lane leads the segment).  Per segment: offsets
+// from a segmented inclusive scan of the step deltas, indel run lengths back to the segment's
+// previous run end, one factor per step (the quality of read[dir] position p is the forward read's,
+// reversed for RC), multiplied in step order at the
 // leader (after i wave_shl:1 moves it holds step i's factor), then the perfect-match factor.  gok: the
 // lane's group succeeded in both directions (its paths are recorded); s0 / rcRead: its seed offset and
 // direction.  -> leader lanes: qv = product * perfect (lane g*S forward, 32 + g*S reverse); reverse
@@ -622,7 +569,7 @@ __device__ __forceinline__ bool pass_apply(const KArgs &A, Lds<MAXLEN> &S, Elem6
             const uint32_t ebase = (cKey >> 1) * ELEM;
             const uint32_t elemLoc = ebase + cbit;
             // the nearby element (BaseAligner.cpp:1272-1331) does not depend on the match probability:
-            // found and loaded before lv_prob_pair, so its chain walk and load overlap the product
+            // found and loaded before the probabilities are read, so its chain walk and load overlap the product
             uint32_t nbPre;
             int csPre = -1;
             uint32_t nvPre = 0;
@@ -814,6 +761,57 @@ constexpr uint32_t FILTER_MIN = 2;         // elements left in the order for a f
 constexpr uint32_t FWIN = WAVE / 2;        // pop-order positions per pair filter pass (a lane pair each; quads: FWIN / 2)
 constexpr uint32_t FRES_VALID = 1u << 31;
 
+// forced_filter's masks of one lane, F_x[m] = read[dir][m] != genome[loc + x + m] on the bit planes: pair half h
+// holds forward diagonal x = h ? i : -i at local i; quad lane h holds x = 4h + i - LQ_K at local i.  The genome
+// planes from position loc - KB (160 bits), then per local index the window shifted by KB + x bits against the
+// read's planes.  Statements, not a function, shared by forced_filter and the unit kernel lv_filter_kernel
+// (aligner.hip), so that the unit test runs this very code: as a __forceinline__ function the block changed
+// align_kernel<128>'s register allocation (73 against 77 VGPRs, 12 against 20 B of scratch), as text it
+// compiles to what it was.  From the enclosing scope: QUAD, NM (masks per lane), KB (the window starts at
+// loc - KB), loc, act (a lane that is not active reads plane word 0), h, and uint64_t F[NM][2] to fill.
+// GPL: the genome planes; RP: the read[dir] planes {hi, lo, notACGT}, two 64-bit words each.
+#define SGK_FILTER_MASKS(GPL, RP) \
+    { \
+        const int64_t gp = (int64_t)loc - KB + PACK_GUARD; \
+        const GPlane *src = (GPL) + (act ? (gp >> 5) : 0); \
+        const uint32_t sh = (uint32_t)gp & 31; \
+        uint32_t wh[6], wl[6], wm[6]; \
+_Pragma("unroll") \
+        for (int j = 0; j < 6; j++) { \
+            const GPlane w = src[j]; \
+            wh[j] = w.hi; wl[j] = w.lo; wm[j] = w.nm; \
+        } \
+        uint32_t ah[5], al[5], am[5]; \
+_Pragma("unroll") \
+        for (int j = 0; j < 5; j++) { \
+            ah[j] = __builtin_amdgcn_alignbit(wh[j + 1], wh[j], sh); \
+            al[j] = __builtin_amdgcn_alignbit(wl[j + 1], wl[j], sh); \
+            am[j] = __builtin_amdgcn_alignbit(wm[j + 1], wm[j], sh); \
+        } \
+        const uint64_t *rp = (RP); \
+        uint32_t rh[4], rl_[4], rm[4]; \
+_Pragma("unroll") \
+        for (int j = 0; j < 4; j++) { \
+            rh[j] = (uint32_t)(rp[j / 2] >> (32 * (j & 1))); \
+            rl_[j] = (uint32_t)(rp[2 + j / 2] >> (32 * (j & 1))); \
+            rm[j] = (uint32_t)(rp[4 + j / 2] >> (32 * (j & 1))); \
+        } \
+_Pragma("unroll") \
+        for (int i = 0; i < NM; i++) { \
+            const uint32_t cs = QUAD ? (uint32_t)(4 * h + i) : (uint32_t)(h ? FKM + i : FKM - i); \
+            uint32_t f[4]; \
+_Pragma("unroll") \
+            for (int j = 0; j < 4; j++) { \
+                const uint32_t gh = __builtin_amdgcn_alignbit(ah[j + 1], ah[j], cs); \
+                const uint32_t gl = __builtin_amdgcn_alignbit(al[j + 1], al[j], cs); \
+                const uint32_t gm = __builtin_amdgcn_alignbit(am[j + 1], am[j], cs); \
+                f[j] = (gh ^ rh[j]) | (gl ^ rl_[j]) | gm | rm[j]; \
+            } \
+            F[i][0] = ((uint64_t)f[1] << 32) | f[0]; \
+            F[i][1] = ((uint64_t)f[3] << 32) | f[2]; \
+        } \
+    }
+
 // QUAD: one candidate per lane quad (lv_quad_dist, limits 6 and 7: 16 positions per pass), else per lane
 // pair (lv_pair_dist, limits <= 5: 32 positions).  Distances above the limit are encoded 7; at limit 7 a
 // 7 is also an exact distance, which cand_needs_lv still sends through lv_group (7 <= k), so the
@@ -851,49 +849,8 @@ __device__ __forceinline__ uint32_t forced_filter(const KArgs &A, Lds<MAXLEN> &S
     int s = 0;
     if (act) s = (int)(sp ? (uint32_t)reinterpret_cast<const uint8_t *>(ar + sp)[bit] : slot_offset(h3.x, h3.y, h3.z, h3.w, bit));
     act = act && substring_ok(A, loc, n + MAX_K);
-    // this lane's masks, F_x[m] = read[dir][m] != genome[loc + x + m] on the bit planes: pair half h holds
-    // forward diagonal x = h ? i : -i at local i; quad lane h holds x = 4h + i - LQ_K at local i
     uint64_t F[NM][2];
-    {
-        const int64_t gp = (int64_t)loc - KB + PACK_GUARD;
-        const GPlane *src = A.gpl + (act ? (gp >> 5) : 0);
-        const uint32_t sh = (uint32_t)gp & 31;
-        uint32_t wh[6], wl[6], wm[6];
-#pragma unroll
-        for (int j = 0; j < 6; j++) {
-            const GPlane w = src[j];
-            wh[j] = w.hi; wl[j] = w.lo; wm[j] = w.nm;
-        }
-        uint32_t ah[5], al[5], am[5];   // the genome planes from position loc - KB, 160 bits
-#pragma unroll
-        for (int j = 0; j < 5; j++) {
-            ah[j] = __builtin_amdgcn_alignbit(wh[j + 1], wh[j], sh);
-            al[j] = __builtin_amdgcn_alignbit(wl[j + 1], wl[j], sh);
-            am[j] = __builtin_amdgcn_alignbit(wm[j + 1], wm[j], sh);
-        }
-        const uint64_t *rp = &S.grp[0].rpl[dir][0][0];
-        uint32_t rh[4], rl_[4], rm[4];
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            rh[j] = (uint32_t)(rp[j / 2] >> (32 * (j & 1)));
-            rl_[j] = (uint32_t)(rp[2 + j / 2] >> (32 * (j & 1)));
-            rm[j] = (uint32_t)(rp[4 + j / 2] >> (32 * (j & 1)));
-        }
-#pragma unroll
-        for (int i = 0; i < NM; i++) {   // the window shifted by KB + x bits
-            const uint32_t cs = QUAD ? (uint32_t)(4 * h + i) : (uint32_t)(h ? FKM + i : FKM - i);
-            uint32_t f[4];
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-                const uint32_t gh = __builtin_amdgcn_alignbit(ah[j + 1], ah[j], cs);
-                const uint32_t gl = __builtin_amdgcn_alignbit(al[j + 1], al[j], cs);
-                const uint32_t gm = __builtin_amdgcn_alignbit(am[j + 1], am[j], cs);
-                f[j] = (gh ^ rh[j]) | (gl ^ rl_[j]) | gm | rm[j];
-            }
-            F[i][0] = ((uint64_t)f[1] << 32) | f[0];
-            F[i][1] = ((uint64_t)f[3] << 32) | f[2];
-        }
-    }
+    SGK_FILTER_MASKS(A.gpl, &S.grp[0].rpl[dir][0][0])
     const int t = s + (int)A.seedLen;
     int e1, e2 = -1;
     if constexpr (QUAD) e1 = lv_quad_dist<1>(F, h, act, t, (int)n - t, (int)n + MAX_K - t, k);

@@ -797,93 +797,165 @@ __global__ __launch_bounds__(64) void lv_kernel(const LvTask *tasks, const char 
     if (lane == 0) { outScore[blockIdx.x] = r.score; outNet[blockIdx.x] = r.netIndel; outProb[blockIdx.x] = r.prob; }
 }
 
-// Unit-test kernel of the production bit-plane LV (align_score.h): one task per wave, group 0
-// of lv_group<DIR, GS> (GS chosen from k as score_batched does) on the mismatch mask a pass
-// would build, then lv_prob_pair for the match probability.  The task's text and pattern are
-// mapped onto a virtual read and genome window exactly as lv_pass sees them:
-//   forward: read = pattern, genome[loc + y] = text[y]; pattern index i = read position i;
-//   reverse: read[m] = pattern[pl-1-m], genome[loc + y] = text[tl - pl + y], and the reverse LV
-//            runs on the bit-reversed mask with q0 = 127 - (pl - 1), as lv_pass calls it.
-struct LvgTask {
-    uint64_t pOff, tOff;   // pattern/quals offset, text offset
-    int32_t pl, tl, k, dir;
+// Unit-test kernel of a scoring pass as production runs it (align_score.h lv_pass + the probability
+// step of pass_apply): one wave is one pass of one read, its 64/GS groups filled with different
+// candidates (GS chosen from k as score_batched does).  From the masks on it makes exactly lv_pass'
+// calls -- the forward lv_group<1, GS, NW, UNIFORM_K> at (k, k), kmax2 by max_reduce32, the reverse
+// lv_group<-1, GS, NW> on mk_reverse(F) with each group's k2 = k - e1 -- then pass_apply's gok packing
+// and lv_prob_groups.  The masks are built by byte comparison on diagonal x = li - c from the
+// candidate's own genome bytes (positions outside the bytes given never match); lv_pass' funnel-shift
+// mask build from the bit planes is left to end-to-end parity.  rtl is the reverse call's text length,
+// s + MAX_K in lv_pass (the reference's LV vectors carry other lengths).
+constexpr int LVP_G = 8;                  // groups of a pass at GS = 8
+struct LvpCand {
+    int64_t genOff;                        // genome buffer offset of the candidate's position 0
+    int32_t before, after;                 // bytes held before position 0 / from position 0 on
+    int32_t dir, s, act, glen;
+    int32_t rtl, pad;
+};
+struct LvpTask {
+    uint64_t readOff;                      // into the reads / quals buffers (forward read)
+    int32_t n, seedLen, k, pad;
+    LvpCand c[LVP_G];
 };
 
-template <int GS, int DIR, int NW>
-__device__ __forceinline__ void lvg_run(Lds<64 * NW> &S, const LvgTask &T, const char *pats, const char *texts,
-                                        int32_t *outScore, int32_t *outNet, double *outProb) {
+template <int GS, int NW>
+__device__ __forceinline__ void lvp_run(Lds<64 * NW> &S, const LvpTask *T, const char *reads, const char *gbuf,
+                                        int32_t *outE1, int32_t *outE2, double *outP1, double *outP2, int32_t *outNet) {
     auto &G = S.grp[0];
     const int lane = lane_id();
     const int li = lane & (GS - 1), gi = lane / GS, c = GS / 2 - 1;
-    const bool act = gi == 0;
-    const int pl = T.pl, tl = T.tl;
-    // F_x[m] = read[m] != genome[loc + x + m], x = li - c; mismatch past the read or the text
+    const LvpCand C = T->c[gi];
+    const int n = T->n, k = T->k, seedLen = T->seedLen;
+    const bool act = C.act != 0;
+    // F_x[m] = read[dir][m] != genome[x + m], x = li - c; mismatch past the read (the read planes' zero slack)
     MaskW<NW> F;
     uint32_t f[2 * NW];
 #pragma unroll
     for (int j = 0; j < 2 * NW; j++) f[j] = 0xffffffffu;
-    if (act) {
+    {
         const int x = li - c;
-        for (int m = 0; m < 64 * NW; m++) {
-            bool mm = true;
-            if (m < pl) {
-                const char r = DIR > 0 ? pats[T.pOff + m] : pats[T.pOff + pl - 1 - m];
-                const int y = DIR > 0 ? x + m : tl - pl + x + m;
-                if (y >= 0 && y < tl) {
-                    const char g = texts[T.tOff + y];
-                    const uint32_t rc = packed_code((uint8_t)r), gc = packed_code((uint8_t)g);
-                    mm = rc > 3 || gc > 3 || rc != gc;
-                }
-            }
-            if (!mm) f[m >> 5] &= ~(1u << (m & 31));
+        for (int m = 0; m < n; m++) {
+            const int y = x + m;
+            if (y < -C.before || y >= C.after) continue;
+            uint32_t rc = packed_code((uint8_t)reads[T->readOff + (uint64_t)(C.dir ? n - 1 - m : m)]);
+            if (C.dir && rc < 4) rc ^= 3u;   // read[RC][m] = complement of read[FORWARD][n-1-m]
+            const uint32_t gc = packed_code((uint8_t)gbuf[C.genOff + y]);
+            if (rc < 4 && rc == gc) f[m >> 5] &= ~(1u << (m & 31));
         }
     }
 #pragma unroll
     for (int j = 0; j < NW; j++) F.w[j] = ((uint64_t)f[2 * j + 1] << 32) | f[2 * j];
-    int e = -1;
-    if (DIR > 0) lv_group<1, GS, NW>(G, lv_rows(S), F, act, 0, pl, tl, T.k, T.k, e);
-    else lv_group<-1, GS, NW>(G, lv_rows(S), mk_reverse(F), act, 64 * NW - 1 - (pl - 1), pl, tl, T.k, T.k, e);
-    e = readlane(e, 0);
-    wave_sync();
-    double p1 = 1.0, p2 = 1.0;
-    int net2 = 0;
-    if (e >= 0) {
-        if (lane == 0) G.plen[DIR > 0 ? 1 : 0][0] = 0;   // only this direction's path
-        wave_sync();
-        // forward: patternLen = n - t0 = pl (t0 = 0); reverse: patternLen = s0 = pl (t0 = n)
-        lv_prob_pair(nullptr, G, 0, 0, pl, DIR > 0 ? 0 : pl, DIR > 0 ? 0 : pl, S.fwdQ, 0u, p1, p2, net2);
+    int e1 = -1, e2 = -1;
+    const int t = C.s + seedLen;
+    lv_group<1, GS, NW, true>(G, lv_rows(S), F, act, t, n - t, C.glen - t, k, k, e1);
+    const int k2 = k - e1;
+    const bool ract = act && e1 >= 0;
+    const int kmax2 = (int)max_reduce32(ract ? (uint32_t)(k2 + 1) : 0u) - 1;   // largest reverse limit
+    if (kmax2 >= 0) {
+        const MaskW<NW> R = mk_reverse(F);
+        lv_group<-1, GS, NW>(G, lv_rows(S), R, ract, 64 * NW - 1 - (C.s - 1), C.s, C.rtl, k2, kmax2, e2);
     }
-    if (lane == 0) {
-        outScore[blockIdx.x] = e;
-        outNet[blockIdx.x] = DIR > 0 ? 0 : net2;
-        outProb[blockIdx.x] = e >= 0 ? (DIR > 0 ? p1 : p2) : 1.0;
+    double qv = 1.0;
+    int netv = 0;
+    if (ballot(act && e1 >= 0 && e2 >= 0) != 0) {
+        const int gsrc = ((lane_id() & 31) / (GS / 2)) * GS;
+        const int gpk = shfl_idx((e1 + 1) | (e2 + 1) << 5 | (act ? 1 << 10 : 0) | C.dir << 11 | C.s << 12, gsrc);
+        const bool gok = (gpk & 31) != 0 && ((gpk >> 5) & 31) != 0 && ((gpk >> 10) & 1) != 0;
+        lv_prob_groups<GS, NW>(G, gok, n, gpk >> 12, seedLen, (uint32_t)(gpk >> 11) & 1u, S.fwdQ, qv, netv);
+    }
+    const size_t base = (size_t)blockIdx.x * LVP_G;
+    if (li == 0) { outE1[base + gi] = e1; outE2[base + gi] = e2; }
+    const int sl = lane & 31;
+    if (sl % (GS / 2) == 0) {   // the segment leaders: forward qv at lane g * S, reverse qv and netv at 32 + g * S
+        const int g = sl / (GS / 2);
+        if (lane < 32) outP1[base + g] = qv;
+        else { outP2[base + g] = qv; outNet[base + g] = netv; }
     }
 }
 
 template <int NW>
-__global__ __launch_bounds__(64) void lv_group_kernel(const LvgTask *tasks, const char *pats, const char *quals,
-                                                      const char *texts, int32_t *outScore, int32_t *outNet,
-                                                      double *outProb) {
+__global__ __launch_bounds__(64) void lv_pass_kernel(const LvpTask *tasks, const char *reads, const char *quals,
+                                                     const char *gbuf, int32_t *outE1, int32_t *outE2, double *outP1,
+                                                     double *outP2, int32_t *outNet) {
     __shared__ Lds<64 * NW> S;
     const int lane = lane_id();
-    const LvgTask T = tasks[blockIdx.x];
-    // qualities in read coordinates (reverse: read[m] = pattern[pl-1-m])
-    for (int m = lane; m < Lds<64 * NW>::RL; m += WAVE)
-        S.fwdQ[m] = m < T.pl ? (T.dir > 0 ? quals[T.pOff + m] : quals[T.pOff + T.pl - 1 - m]) : 0;
+    const LvpTask *T = tasks + blockIdx.x;
+    const int n = T->n;
+    for (int m = lane; m < Lds<64 * NW>::RL; m += WAVE) S.fwdQ[m] = m < n ? quals[T->readOff + m] : 0;
     wave_sync();
-    const int k = T.k < MAX_K - 1 ? T.k : MAX_K - 1;
+    const int k = T->k;   // <= MAX_K - 1 (the host clamps it, as pass_apply's kNow is)
     const int GS = k <= 3 ? 8 : (k <= 7 ? 16 : (k <= 15 ? 32 : 64));   // score_batched's choice
-    if (T.dir > 0) {
-        if (GS == 8) lvg_run<8, 1, NW>(S, T, pats, texts, outScore, outNet, outProb);
-        else if (GS == 16) lvg_run<16, 1, NW>(S, T, pats, texts, outScore, outNet, outProb);
-        else if (GS == 32) lvg_run<32, 1, NW>(S, T, pats, texts, outScore, outNet, outProb);
-        else lvg_run<64, 1, NW>(S, T, pats, texts, outScore, outNet, outProb);
-    } else {
-        if (GS == 8) lvg_run<8, -1, NW>(S, T, pats, texts, outScore, outNet, outProb);
-        else if (GS == 16) lvg_run<16, -1, NW>(S, T, pats, texts, outScore, outNet, outProb);
-        else if (GS == 32) lvg_run<32, -1, NW>(S, T, pats, texts, outScore, outNet, outProb);
-        else lvg_run<64, -1, NW>(S, T, pats, texts, outScore, outNet, outProb);
+    if (GS == 8) lvp_run<8, NW>(S, T, reads, gbuf, outE1, outE2, outP1, outP2, outNet);
+    else if (GS == 16) lvp_run<16, NW>(S, T, reads, gbuf, outE1, outE2, outP1, outP2, outNet);
+    else if (GS == 32) lvp_run<32, NW>(S, T, reads, gbuf, outE1, outE2, outP1, outP2, outNet);
+    else lvp_run<64, NW>(S, T, reads, gbuf, outE1, outE2, outP1, outP2, outNet);
+}
+
+// Unit-test kernel of the forced-mode prefilter (align_score.h forced_filter, lv_lane.h): a wave takes 32
+// tasks, one per lane pair (limits <= 5), or 16, one per lane quad (QUAD).  From the task's values on it
+// does what forced_filter does: substring_ok on the n + MAX_K window, SGK_FILTER_MASKS on the aligner's genome
+// planes, lv_*_dist<1>, the ballot, lv_*_dist<-1> at k - e1, the FRES encoding (bit 0).  The read planes
+// are restated per task (every alignment exercises the kernels' own at every position); element fetch,
+// pop order and the lps test are left to end-to-end parity.
+struct LvfTask {
+    uint64_t readOff;
+    uint32_t loc;
+    int32_t n, dir, s, k, act;
+};
+struct LvfArgs {   // substring_ok's fields and the planes
+    const GPlane *gpl;
+    const uint32_t *pieces;
+    int32_t nPieces;
+    uint32_t nBases, padding, seedLen;
+};
+
+template <bool QUAD>
+__global__ __launch_bounds__(64) void lv_filter_kernel(LvfArgs A, const LvfTask *tasks, uint32_t nTasks, const char *reads,
+                                                       uint32_t *out) {
+    constexpr int LPC = QUAD ? 4 : 2;          // lanes per task
+    constexpr int NM = QUAD ? 4 : FKM + 1;     // masks per lane
+    constexpr int KB = QUAD ? LQ_K : FKM;      // the window starts at loc - KB
+    constexpr int PER = WAVE / LPC;            // tasks per wave
+    __shared__ uint64_t rpl[PER][6];           // per task: read[dir] planes {hi, lo, notACGT} x 2 words
+    const int lane = lane_id();
+    const int c = lane / LPC, h = lane % LPC;
+    const uint32_t ti = blockIdx.x * PER + (uint32_t)c;
+    const bool have = ti < nTasks;
+    LvfTask T;
+    T.readOff = 0; T.loc = 0; T.n = 0; T.dir = 0; T.s = 0; T.k = 0; T.act = 0;
+    if (have) T = tasks[ti];
+    if (h == 0) {
+        uint64_t bh[2] = {0, 0}, bl[2] = {0, 0}, bm[2] = {0, 0};
+        for (int m = 0; m < 128; m++) {
+            uint32_t code = 4u;
+            if (m < T.n) {
+                code = packed_code((uint8_t)reads[T.readOff + (uint64_t)(T.dir ? T.n - 1 - m : m)]);
+                if (T.dir && code < 4) code ^= 3u;
+            }
+            const uint64_t b = 1ull << (m & 63);
+            if (code > 3) bm[m >> 6] |= b;
+            else { if (code & 2) bh[m >> 6] |= b; if (code & 1) bl[m >> 6] |= b; }
+        }
+        rpl[c][0] = bh[0]; rpl[c][1] = bh[1]; rpl[c][2] = bl[0]; rpl[c][3] = bl[1]; rpl[c][4] = bm[0]; rpl[c][5] = bm[1];
     }
+    __syncthreads();
+    const int n = T.n, s = T.s, k = T.k;
+    const uint32_t loc = T.loc;
+    bool act = have && T.act != 0;
+    act = act && substring_ok(A, loc, (uint32_t)n + MAX_K);
+    uint64_t F[NM][2];
+    SGK_FILTER_MASKS(A.gpl, &rpl[c][0])
+    const int t = s + (int)A.seedLen;
+    int e1, e2 = -1;
+    if constexpr (QUAD) e1 = lv_quad_dist<1>(F, h, act, t, n - t, n + MAX_K - t, k);
+    else e1 = lv_pair_dist<FKM, 1>(F, h, act, t, n - t, n + MAX_K - t, k);
+    if (ballot(e1 >= 0)) {
+        if constexpr (QUAD) e2 = lv_quad_dist<-1>(F, h, e1 >= 0, 127 - (s - 1), s, s + MAX_K, k - e1);
+        else e2 = lv_pair_dist<FKM, -1>(F, h, e1 >= 0, 127 - (s - 1), s, s + MAX_K, k - e1);
+    }
+    const uint32_t res = act ? FRES_VALID | (uint32_t)(e1 < 0 ? 7 : e1) << 8 | (uint32_t)(e2 < 0 ? 7 : e2) << 11 : 0u;
+    if (have && h == 0) out[ti] = res;
 }
 
 }  // namespace sgk
@@ -2901,58 +2973,128 @@ int snapgpu_lv_batch(int device, int direction, uint32_t n, const char *texts, c
     return SNAPGPU_OK;
 }
 
-// The production bit-plane LV (lv_group + lv_prob_pair) on explicit tasks: unit parity for
-// LandauVishkin<dir>::computeEditDistance as align_kernel<128> runs it (patterns <= 127 bases:
-// 128-bit masks) and as align_kernel<256> runs it (a batch with a longer pattern, <= 253 bases:
-// 256-bit masks).
-int snapgpu_lv_group_batch(int device, int direction, uint32_t n, const char *texts, const uint64_t *textOff,
-                           const uint32_t *textLen, const char *patterns, const char *quals, const uint64_t *patOff,
-                           const uint32_t *patLen, const int32_t *k, int32_t *outScore, int32_t *outNetIndel,
-                           double *outProb) {
-    if (n == 0) return SNAPGPU_OK;
+// Scoring passes as align_kernel<128> (nw = 2) / align_kernel<256> (nw = 4) run them (lv_pass_kernel):
+// unit parity for lv_group in every group of a pass, with UNIFORM_K and per-group reverse limits, and
+// for lv_prob_groups.
+int snapgpu_lv_pass_batch(int device, int nw, uint32_t nPasses, const char *reads, const char *quals,
+                          uint64_t readBytes, const uint64_t *readOff, const uint32_t *readLen, const int32_t *seedLen,
+                          const int32_t *k, const char *genome, uint64_t genomeBytes, const int64_t *cand,
+                          int32_t *outE1, int32_t *outE2, double *outP1, double *outP2, int32_t *outNet) {
+    if (nPasses == 0) return SNAPGPU_OK;
+    if (nw != 2 && nw != 4) { snapgpu::setError("lv_pass_batch: nw must be 2 or 4"); return SNAPGPU_EINVAL; }
     int ndev = snapgpu_device_count();
     if (ndev <= 0 || device >= ndev) { snapgpu::setError("no such HIP device"); return SNAPGPU_EDEVICE; }
-    HIPCHK(hipSetDevice(device));
-    HIPCHK(ensureDeviceTables(device));
-    std::vector<LvgTask> tasks(n);
-    uint64_t pBytes = 0, tBytes = 0;
-    bool wide = false;
-    for (uint32_t i = 0; i < n; i++) {
-        if (patLen[i] == 0 || patLen[i] > 253 || k[i] < 0) {
-            snapgpu::setError("lv_group_batch: pattern length must be 1..253 and k >= 0");
+    std::vector<LvpTask> tasks(nPasses);
+    for (uint32_t i = 0; i < nPasses; i++) {
+        LvpTask &T = tasks[i];
+        memset(&T, 0, sizeof(T));
+        const int64_t n = readLen[i];
+        if (n < 1 || n > 64 * nw || readOff[i] + (uint64_t)n > readBytes || k[i] < 0 || seedLen[i] < 0 || seedLen[i] > n) {
+            snapgpu::setError("lv_pass_batch: read length must be 1..64*nw inside the buffer, k >= 0, 0 <= seedLen <= n");
             return SNAPGPU_EINVAL;
         }
-        wide |= patLen[i] > 127;
-        pBytes = std::max<uint64_t>(pBytes, patOff[i] + patLen[i]);
-        tBytes = std::max<uint64_t>(tBytes, textOff[i] + textLen[i]);
-        tasks[i] = LvgTask{patOff[i], textOff[i], (int32_t)patLen[i], (int32_t)textLen[i], k[i], direction > 0 ? 1 : -1};
+        T.readOff = readOff[i];
+        T.n = (int32_t)n;
+        T.seedLen = seedLen[i];
+        T.k = k[i] < MAX_K - 1 ? k[i] : MAX_K - 1;
+        const int Gn = 64 / (T.k <= 3 ? 8 : (T.k <= 7 ? 16 : (T.k <= 15 ? 32 : 64)));
+        for (int g = 0; g < LVP_G; g++) {
+            const int64_t *c = cand + ((size_t)i * LVP_G + g) * 8;   // genOff, before, after, dir, s, act, glen, rtl
+            LvpCand &C = T.c[g];
+            if (g >= Gn) {
+                if (c[5] != 0) { snapgpu::setError("lv_pass_batch: an active candidate beyond the pass's 64/GS groups"); return SNAPGPU_EINVAL; }
+                continue;
+            }
+            if (c[5] == 0 && c[1] == 0 && c[2] == 0) continue;   // an empty group: no bytes, every position a mismatch
+            const int64_t s = c[4];
+            if (c[1] < 0 || c[2] < 0 || c[1] > (1 << 20) || c[2] > (1 << 20) || c[0] - c[1] < 0 ||
+                (uint64_t)(c[0] + c[2]) > genomeBytes || (c[3] != 0 && c[3] != 1) || s < 0 || s + T.seedLen > n ||
+                c[6] < s + T.seedLen || c[6] > (1 << 20) || c[7] < 0 || c[7] > (1 << 20)) {
+                snapgpu::setError("lv_pass_batch: candidate outside its buffers, or s / glen / rtl out of range");
+                return SNAPGPU_EINVAL;
+            }
+            C.genOff = c[0]; C.before = (int32_t)c[1]; C.after = (int32_t)c[2]; C.dir = (int32_t)c[3]; C.s = (int32_t)s;
+            C.act = c[5] != 0; C.glen = (int32_t)c[6]; C.rtl = (int32_t)c[7];
+        }
     }
-    LvgTask *dT = nullptr; char *dP = nullptr, *dQ = nullptr, *dX = nullptr;
-    int32_t *dS = nullptr, *dN = nullptr; double *dPr = nullptr;
+    HIPCHK(hipSetDevice(device));
+    HIPCHK(ensureDeviceTables(device));
+    const size_t no = (size_t)nPasses * LVP_G;
+    LvpTask *dT = nullptr; char *dR = nullptr, *dQ = nullptr, *dG = nullptr;
+    int32_t *dE1 = nullptr, *dE2 = nullptr, *dN = nullptr; double *dP1 = nullptr, *dP2 = nullptr;
     int rc = SNAPGPU_OK;
-    if (hipMalloc(&dT, n * sizeof(LvgTask)) != hipSuccess || hipMalloc(&dP, pBytes + 64) != hipSuccess ||
-        hipMalloc(&dQ, pBytes + 64) != hipSuccess || hipMalloc(&dX, tBytes + 64) != hipSuccess ||
-        hipMalloc(&dS, n * 4) != hipSuccess || hipMalloc(&dN, n * 4) != hipSuccess || hipMalloc(&dPr, n * 8) != hipSuccess) {
-        snapgpu::setError("lv_group_batch: hipMalloc");
+    if (hipMalloc(&dT, nPasses * sizeof(LvpTask)) != hipSuccess || hipMalloc(&dR, readBytes + 64) != hipSuccess ||
+        hipMalloc(&dQ, readBytes + 64) != hipSuccess || hipMalloc(&dG, genomeBytes + 64) != hipSuccess ||
+        hipMalloc(&dE1, no * 4) != hipSuccess || hipMalloc(&dE2, no * 4) != hipSuccess || hipMalloc(&dN, no * 4) != hipSuccess ||
+        hipMalloc(&dP1, no * 8) != hipSuccess || hipMalloc(&dP2, no * 8) != hipSuccess) {
+        snapgpu::setError("lv_pass_batch: hipMalloc");
         rc = SNAPGPU_ENOMEM;
     }
     if (!rc) {
-        hipMemcpy(dT, tasks.data(), n * sizeof(LvgTask), hipMemcpyHostToDevice);
-        hipMemcpy(dP, patterns, pBytes, hipMemcpyHostToDevice);
-        hipMemcpy(dQ, quals, pBytes, hipMemcpyHostToDevice);
-        hipMemcpy(dX, texts, tBytes, hipMemcpyHostToDevice);
-        if (wide) hipLaunchKernelGGL(lv_group_kernel<4>, dim3(n), dim3(64), 0, 0, dT, dP, dQ, dX, dS, dN, dPr);
-        else hipLaunchKernelGGL(lv_group_kernel<2>, dim3(n), dim3(64), 0, 0, dT, dP, dQ, dX, dS, dN, dPr);
+        hipMemcpy(dT, tasks.data(), nPasses * sizeof(LvpTask), hipMemcpyHostToDevice);
+        hipMemcpy(dR, reads, readBytes, hipMemcpyHostToDevice);
+        hipMemcpy(dQ, quals, readBytes, hipMemcpyHostToDevice);
+        if (genomeBytes) hipMemcpy(dG, genome, genomeBytes, hipMemcpyHostToDevice);
+        if (nw == 4) hipLaunchKernelGGL(lv_pass_kernel<4>, dim3(nPasses), dim3(64), 0, 0, dT, dR, dQ, dG, dE1, dE2, dP1, dP2, dN);
+        else hipLaunchKernelGGL(lv_pass_kernel<2>, dim3(nPasses), dim3(64), 0, 0, dT, dR, dQ, dG, dE1, dE2, dP1, dP2, dN);
         if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
-            snapgpu::setError("lv_group_kernel failed");
+            snapgpu::setError("lv_pass_kernel failed");
             rc = SNAPGPU_EDEVICE;
         } else {
-            hipMemcpy(outScore, dS, n * 4, hipMemcpyDeviceToHost);
-            hipMemcpy(outNetIndel, dN, n * 4, hipMemcpyDeviceToHost);
-            hipMemcpy(outProb, dPr, n * 8, hipMemcpyDeviceToHost);
+            hipMemcpy(outE1, dE1, no * 4, hipMemcpyDeviceToHost);
+            hipMemcpy(outE2, dE2, no * 4, hipMemcpyDeviceToHost);
+            hipMemcpy(outNet, dN, no * 4, hipMemcpyDeviceToHost);
+            hipMemcpy(outP1, dP1, no * 8, hipMemcpyDeviceToHost);
+            hipMemcpy(outP2, dP2, no * 8, hipMemcpyDeviceToHost);
         }
     }
-    hipFree(dT); hipFree(dP); hipFree(dQ); hipFree(dX); hipFree(dS); hipFree(dN); hipFree(dPr);
+    hipFree(dT); hipFree(dR); hipFree(dQ); hipFree(dG); hipFree(dE1); hipFree(dE2); hipFree(dN); hipFree(dP1); hipFree(dP2);
+    return rc;
+}
+
+// The forced-mode prefilter (lv_filter_kernel) on explicit tasks over the aligner's genome planes:
+// quad = 0: lane pairs (limits <= 5), 32 tasks per wave; quad != 0: lane quads (limits <= 7), 16 per wave.
+int snapgpu_lv_filter_batch(snapgpu_aligner_t *a, int quad, uint32_t nTasks, const char *reads, uint64_t readBytes,
+                            const uint64_t *readOff, const uint32_t *readLen, const uint32_t *loc, const int32_t *dir,
+                            const int32_t *s, const int32_t *k, const int32_t *act, uint32_t *out) {
+    if (!a || !a->dGPlanes) { snapgpu::setError("lv_filter_batch: no aligner"); return SNAPGPU_EINVAL; }
+    if (nTasks == 0) return SNAPGPU_OK;
+    const snapgpu_index_t *idx = a->idx;
+    const int seedLen = (int)idx->seedLen;
+    std::vector<LvfTask> tasks(nTasks);
+    for (uint32_t i = 0; i < nTasks; i++) {
+        const int64_t n = readLen[i];
+        if (n < 1 || n > 128 || readOff[i] + (uint64_t)n > readBytes || (dir[i] != 0 && dir[i] != 1) || s[i] < 0 ||
+            s[i] + seedLen > n || k[i] < 0 || k[i] > (quad ? LQ_K : FKM)) {
+            snapgpu::setError("lv_filter_batch: read length 1..128, 0 <= s <= n - seedLen, 0 <= k <= 5 (pairs) / 7 (quads)");
+            return SNAPGPU_EINVAL;
+        }
+        tasks[i] = LvfTask{readOff[i], loc[i], (int32_t)n, dir[i], s[i], k[i], act[i] != 0};
+    }
+    HIPCHK(hipSetDevice(a->device));
+    LvfArgs A;
+    A.gpl = a->dGPlanes; A.pieces = a->dPieces; A.nPieces = (int32_t)idx->genome->pieceOffsets.size();
+    A.nBases = idx->genome->nBases; A.padding = idx->genome->chromosomePadding; A.seedLen = (uint32_t)seedLen;
+    LvfTask *dT = nullptr; char *dR = nullptr; uint32_t *dO = nullptr;
+    int rc = SNAPGPU_OK;
+    if (hipMalloc(&dT, nTasks * sizeof(LvfTask)) != hipSuccess || hipMalloc(&dR, readBytes + 64) != hipSuccess ||
+        hipMalloc(&dO, (size_t)nTasks * 4) != hipSuccess) {
+        snapgpu::setError("lv_filter_batch: hipMalloc");
+        rc = SNAPGPU_ENOMEM;
+    }
+    if (!rc) {
+        hipMemcpy(dT, tasks.data(), nTasks * sizeof(LvfTask), hipMemcpyHostToDevice);
+        hipMemcpy(dR, reads, readBytes, hipMemcpyHostToDevice);
+        const uint32_t per = quad ? 16u : 32u;
+        const dim3 grid((nTasks + per - 1) / per);
+        if (quad) hipLaunchKernelGGL(lv_filter_kernel<true>, grid, dim3(64), 0, 0, A, dT, nTasks, dR, dO);
+        else hipLaunchKernelGGL(lv_filter_kernel<false>, grid, dim3(64), 0, 0, A, dT, nTasks, dR, dO);
+        if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
+            snapgpu::setError("lv_filter_kernel failed");
+            rc = SNAPGPU_EDEVICE;
+        } else hipMemcpy(out, dO, (size_t)nTasks * 4, hipMemcpyDeviceToHost);
+    }
+    hipFree(dT); hipFree(dR); hipFree(dO);
     return rc;
 }
 

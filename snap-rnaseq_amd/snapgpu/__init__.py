@@ -861,12 +861,122 @@ def _sam_line_write(index, reads, ids, results, cigars, read_group="FASTQ", clip
     return buf[:total].tobytes()
 
 
+LV_PASS_GROUPS = 8      # SNAPGPU_LV_PASS_GROUPS: lane groups of a pass at the smallest group size
+LV_MAX_K = 31           # LandauVishkin.h MAX_K
+FRES_VALID = 1 << 31    # snapgpu_lv_filter_batch: the task's window was servable
+
+
+def lv_group_size(k):
+    """Lanes per candidate of a scoring pass at limit k (score_batched's choice)."""
+    k = min(k, LV_MAX_K - 1)
+    return 8 if k <= 3 else 16 if k <= 7 else 32 if k <= 15 else 64
+
+
+def lv_pass_batch(passes, device=0, nw=None):
+    """Scoring passes as align_kernel<128> / <256> run them (snapgpu_lv_pass_batch): one wave per pass.
+
+    passes: list of dicts {read, quals, seedLen, k, cands}; cands lists the pass's lane groups in order, each
+    None (no candidate) or a dict {genome, before, dir, s, act, glen[, rtl]}: `genome` holds the candidate's
+    bytes, position 0 at offset `before`.  nw: 64-bit mask words (2 or 4; default 4 when a read is longer than
+    128 bases).  -> per pass, per group: (e1, e2, p1, p2, netIndel)."""
+    n = len(passes)
+    if nw is None:
+        nw = 4 if any(len(p["read"]) > 128 for p in passes) else 2
+    reads, quals, genome = bytearray(), bytearray(), bytearray()
+    roff, rlen, sl, ks = [], [], [], []
+    cand = np.zeros((max(1, n), LV_PASS_GROUPS, 8), dtype=np.int64)
+    for i, p in enumerate(passes):
+        r = p["read"].encode() if isinstance(p["read"], str) else bytes(p["read"])
+        q = p["quals"].encode() if isinstance(p["quals"], str) else bytes(p["quals"])
+        roff.append(len(reads)); rlen.append(len(r)); reads += r; quals += q[:len(r)].ljust(len(r), b"!")
+        sl.append(p["seedLen"]); ks.append(p["k"])
+        if len(p["cands"]) > LV_PASS_GROUPS:
+            raise ValueError("more candidates than lane groups")
+        for g, c in enumerate(p["cands"]):
+            if c is None:
+                continue
+            gb = c["genome"].encode() if isinstance(c["genome"], str) else bytes(c["genome"])
+            cand[i, g] = (len(genome) + c["before"], c["before"], len(gb) - c["before"], c["dir"], c["s"],
+                          1 if c["act"] else 0, c["glen"], c.get("rtl", c["s"] + LV_MAX_K))
+            genome += gb
+    reads += b"\0" * 16; quals += b"\0" * 16; genome += b"\0" * 16
+    A64, A32, AI = C.c_uint64 * n, C.c_uint32 * n, C.c_int32 * n
+    no = max(1, n) * LV_PASS_GROUPS
+    e1, e2, net = (C.c_int32 * no)(), (C.c_int32 * no)(), (C.c_int32 * no)()
+    p1, p2 = (C.c_double * no)(), (C.c_double * no)()
+    _check(lib().snapgpu_lv_pass_batch(device, nw, n, bytes(reads), bytes(quals), len(reads) - 16, A64(*roff),
+                                       A32(*rlen), AI(*sl), AI(*ks), bytes(genome), len(genome) - 16,
+                                       cand.ctypes.data_as(C.POINTER(C.c_int64)), e1, e2, p1, p2, net), "lv_pass_batch")
+    return [[(e1[j], e2[j], p1[j], p2[j], net[j]) for j in range(i * LV_PASS_GROUPS, i * LV_PASS_GROUPS + len(p["cands"]))]
+            for i, p in enumerate(passes)]
+
+
+def lv_filter_batch(aligner, quad, tasks):
+    """The forced-mode prefilter on explicit tasks (snapgpu_lv_filter_batch) over `aligner`'s device genome.
+
+    tasks: list of (read, loc, dir, s, k, act); quad False: lane pairs (k <= 5), True: lane quads (k <= 7).
+    -> uint32 array of encoded results (0, or FRES_VALID | e1 << 8 | e2 << 11; 7 = above the limit)."""
+    n = len(tasks)
+    reads = bytearray()
+    roff, rlen = [], []
+    for t in tasks:
+        r = t[0].encode() if isinstance(t[0], str) else bytes(t[0])
+        roff.append(len(reads)); rlen.append(len(r)); reads += r
+    reads += b"\0" * 16
+    A64, A32, AI = C.c_uint64 * n, C.c_uint32 * n, C.c_int32 * n
+    out = np.zeros(max(1, n), dtype=np.uint32)
+    _check(lib().snapgpu_lv_filter_batch(aligner._h, 1 if quad else 0, n, bytes(reads), len(reads) - 16, A64(*roff),
+                                         A32(*rlen), A32(*[t[1] for t in tasks]), AI(*[t[2] for t in tasks]),
+                                         AI(*[t[3] for t in tasks]), AI(*[t[4] for t in tasks]),
+                                         AI(*[1 if t[5] else 0 for t in tasks]),
+                                         out.ctypes.data_as(C.POINTER(C.c_uint32))), "lv_filter_batch")
+    return out[:n]
+
+
+def _lv_batch_bitplane(direction, tasks, device):
+    """LV tasks as scoring passes (lv_pass_batch): task i sits in lane group i % (64 / GS) of its own pass,
+    the other groups inactive.  A forward task is a read with an empty seed at offset 0 (the forward call
+    scores the whole read against the text); a reverse task is the reversed pattern as a read whose empty
+    seed sits at its end (the reverse call scores it backwards against the text's end).  Texts are padded
+    with 'n' as the reference harness pads them."""
+    PAD = 64
+    passes, where = [], []
+    for i, (t, p, q, k) in enumerate(tasks):
+        t = t.encode() if isinstance(t, str) else bytes(t)
+        p = p.encode() if isinstance(p, str) else bytes(p)
+        q = (q.encode() if isinstance(q, str) else bytes(q))[:len(p)].ljust(len(p), b"!")
+        pl, tl = len(p), len(t)
+        g = i % (64 // lv_group_size(k))
+        gen = b"n" * PAD + t + b"n" * PAD
+        if direction > 0:
+            c = dict(genome=gen, before=PAD, dir=0, s=0, act=1, glen=tl)
+            ps = dict(read=p, quals=q, seedLen=0, k=k)
+        else:   # genome[y] = text[tl - pl + y]; the forward call sees an empty pattern
+            c = dict(genome=gen, before=PAD + tl - pl, dir=0, s=pl, act=1, glen=pl, rtl=tl)
+            ps = dict(read=p[::-1], quals=q[::-1], seedLen=0, k=k)
+        ps["cands"] = [None] * g + [c]
+        passes.append(ps)
+        where.append(g)
+    nw = 4 if any(len(ps["read"]) > 127 for ps in passes) else 2
+    out = []
+    for ps, g, r in zip(passes, where, lv_pass_batch(passes, device, nw)):
+        e1, e2, p1, p2, net = r[g]
+        if direction > 0:
+            out.append((e1, 0, p1 if e1 >= 0 else 1.0))
+        else:
+            out.append((e2, net if e2 >= 0 else 0, p2 if e2 >= 0 else 1.0))
+    return out
+
+
 def lv_batch(direction, tasks, device=0, engine="byte"):
     """LandauVishkin<direction>::computeEditDistance on the GPU.
 
     tasks: list of (text, pattern, quals, k) (str/bytes).  -> list of (score, netIndel, prob).
     engine "byte": the byte-compare LV of align_kernel<512>; "bitplane": the production LV of
-    align_kernel<128> (patterns of 1..127 bases)."""
+    align_kernel<128> / <256> through the pass kernel (patterns of 1..253 bases; any pattern longer than
+    127 bases puts the batch on 256-bit masks; netIndel for direction -1 only)."""
+    if engine != "byte":
+        return _lv_batch_bitplane(direction, tasks, device)
     n = len(tasks)
     texts, pats, quals = bytearray(), bytearray(), bytearray()
     toff, tlen, poff, plen, ks = [], [], [], [], []
@@ -880,9 +990,8 @@ def lv_batch(direction, tasks, device=0, engine="byte"):
     texts += b"\0" * 16; pats += b"\0" * 16; quals += b"\0" * 16
     A64, A32, AI = C.c_uint64 * n, C.c_uint32 * n, C.c_int32 * n
     os_, on, op = AI(), AI(), (C.c_double * n)()
-    fn = lib().snapgpu_lv_batch if engine == "byte" else lib().snapgpu_lv_group_batch
-    _check(fn(device, direction, n, bytes(texts), A64(*toff), A32(*tlen), bytes(pats),
-              bytes(quals), A64(*poff), A32(*plen), AI(*ks), os_, on, op), "lv_batch")
+    _check(lib().snapgpu_lv_batch(device, direction, n, bytes(texts), A64(*toff), A32(*tlen), bytes(pats),
+                                  bytes(quals), A64(*poff), A32(*plen), AI(*ks), os_, on, op), "lv_batch")
     return [(os_[i], on[i], op[i]) for i in range(n)]
 
 

@@ -198,6 +198,23 @@ def oracle_lv(direction, text, pattern, quals, k):
     return e, net.value, prob.value
 
 
+def oracle_lv_at(direction, buf, pos, text_len, pattern, quals, k):
+    """oracle_lv on a caller-supplied buffer, as BaseAligner::score calls LV: the text pointer is
+    buf + pos -- a forward text is buf[pos], buf[pos + 1], ..., a reverse text buf[pos - 1], buf[pos - 2],
+    ... -- so the bytes before and after the text are the caller's, not 'n' padding (LV looks at up to two
+    bytes past text_len).  pattern / quals: the pattern in LV order (a reverse pattern already reversed).
+    -> (distance or -1, netIndel, probability)."""
+    assert isinstance(buf, bytes) and 0 <= pos <= len(buf)
+    p = pattern + b"\0" * 16
+    q = quals + b"\0" * 16
+    prob = C.c_double()
+    net = C.c_int()
+    base = C.cast(C.c_char_p(buf), C.c_void_p).value + pos
+    e = oracle_lib().oracle_lv(direction, C.cast(base, C.c_char_p), text_len, p, q, len(pattern), k, C.byref(prob),
+                               C.byref(net))
+    return e, net.value, prob.value
+
+
 # Every record field, bitwise -- except nProbes: on the device it counts the 64-B lines of the
 # seed tables' bucket image a read's lookups loaded (include/snapgpu.h), in the oracle the
 # reference's SNAPHashTable probes; neither is an AlignRead output.

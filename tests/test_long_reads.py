@@ -96,7 +96,8 @@ def test_gpu_long_reads_match_reference(gpu_available, small_index, long_reads, 
 @pytest.mark.gpu
 @pytest.mark.parametrize("direction,fn", [(1, "lv_long_fwd.tsv"), (-1, "lv_long_rev.tsv")])
 def test_gpu_bitplane_lv256_matches_reference(gpu_available, direction, fn):
-    """lv_group on 256-bit masks (a batch holding a pattern > 127 bases runs on them) against the
+    """lv_group + lv_prob_groups on 256-bit masks (a batch holding a pattern > 127 bases runs on them; scoring
+    passes through lv_pass_kernel, vector i in lane group i mod 64/GS) against the
     reference's LandauVishkin<dir> vectors: distance, reverse netIndel, probability bits."""
     rows = _lv_rows(fn)
     tasks = [(t, p, q, int(k)) for _, k, t, p, q, _, _, _ in rows]

@@ -127,8 +127,9 @@ def test_gpu_seed_lengths(gpu_available, small_reads, seed_len):
 @pytest.mark.gpu
 @pytest.mark.parametrize("direction,fn", [(1, "lv_fwd.tsv"), (-1, "lv_rev.tsv")])
 def test_gpu_bitplane_lv_matches_reference(gpu_available, direction, fn):
-    """lv_group + lv_prob_pair (the LV that scores every read of <= 128 bases) against the
-    reference's LandauVishkin<dir> vectors: distance, reverse netIndel, probability bits."""
+    """lv_group + lv_prob_groups (the LV that scores every read of <= 128 bases), run as a scoring pass
+    (lv_pass_kernel, vector i in lane group i mod 64/GS), against the reference's LandauVishkin<dir>
+    vectors: distance, reverse netIndel, probability bits."""
     rows = [line.rstrip("\n").split("\t") for line in open(os.path.join(G, fn))]
     rows = [r for r in rows if 0 < len(r[3]) <= 127]
     assert len(rows) >= 600
