@@ -364,6 +364,10 @@ typedef struct snapgpu_timing {
     uint64_t nUnwritten;     /* records no pass wrote (the device output is pre-filled with 0xff
                                 and every read must get exactly one record): always 0, else the
                                 call fails with SNAPGPU_EDEVICE */
+    uint64_t nForcedSettled; /* pass 1, forced mode: elements the lane prefilter settled (one pending
+                                candidate whose distances fail), counted without being fetched */
+    uint64_t nForcedLimitSpans; /* ...batches in which a success lowered the score limit ahead of such
+                                elements, which were then counted with the limit at their turn */
 } snapgpu_timing_t;
 int snapgpu_last_timing(snapgpu_aligner_t *a, snapgpu_timing_t *t);
 

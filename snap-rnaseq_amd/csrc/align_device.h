@@ -204,6 +204,8 @@ struct KArgs {
     // atomic per 4-read wave that holds any, and counts them in longCount; pass 1 (longCount set)
     // then skips them instead of deferring them one by one, and ends at once when every read is long
     uint32_t *longCount;
+    // align_kernel<128>'s forced-mode counters {nForcedSettled, nForcedLimitSpans}, or nullptr
+    uint32_t *forcedStats;
     // longest-first order of pass 2 (SNAPGPU_ORDER_LONG, default on): pass 0 writes its long reads
     // here as read | class << 28 (class = log2 of the summed hit counts of their first seeds) and
     // order_long_kernel moves them onto deferList heaviest class first; nullptr: straight onto deferList
@@ -348,6 +350,8 @@ struct GroupLdsT {
     int8_t pa[2][32];
     int16_t pL0[2][8];                   //   exact prefix L[0][0] per group
     int8_t plen[2][8];                   //   path length (0: exact match, prob = perfect[patternLen])
+    uint32_t limAfter[EB + 1];           // forced mode: the score limit set by a success in the batch slot's element;
+                                         //   [EB]: the limit before the batch
 };
 using GroupLds = GroupLdsT<2>;
 // A candidate list entry: bit [5:0], the element's slot in the popped batch [8:6], and -- for a
@@ -825,7 +829,10 @@ struct ReadState {
 };
 
 // per-read statistics: lane SV_x of ReadState::statv
-enum : int { SV_LOOKUPS = 0, SV_SCORED = 1, SV_POPULAR = 2, SV_PROBES = 3, SV_HITWORDS = 4, SV_OVF = 5 };
+enum : int { SV_LOOKUPS = 0, SV_SCORED = 1, SV_POPULAR = 2, SV_PROBES = 3, SV_HITWORDS = 4, SV_OVF = 5,
+             // forced mode of align_kernel<128> (align_score.h): elements retired without a fetch, and batches
+             // whose limit changed ahead of such elements in their span
+             SV_FSETTLED = 6, SV_FSPANS = 7 };
 __device__ __forceinline__ void sv_add(ReadState &st, int lane, int idx, uint32_t v) { st.statv += lane == idx ? v : 0u; }
 __device__ __forceinline__ uint32_t sv_get(const ReadState &st, int idx) { return readlaneu(st.statv, idx); }
 

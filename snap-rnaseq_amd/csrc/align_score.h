@@ -12,7 +12,8 @@
 // Order.  In forced mode the reference pops the head of the highest non-empty weight
 // list until all lists are empty (BaseAligner.cpp:1071-1396); no insertion happens
 // meanwhile and scoring never relinks an element, so the pop order is fixed when
-// forced mode starts.  A batch pops up to EB elements (selection touches only the
+// forced mode starts.  (Elements the forced-mode prefilter settles are counted in that order and
+// never popped: forced_filter, below.)  A batch pops up to EB elements (selection touches only the
 // LDS sort keys), fetches them from the HBM arena in one round trip, lists their
 // unscored candidates (element order, then ascending bit, BaseAligner.cpp:1133) and
 // scores the list in passes.
@@ -652,7 +653,10 @@ __device__ __forceinline__ bool pass_apply(const KArgs &A, Lds<MAXLEN> &S, Elem6
                 st.outMapq = 0;
                 return true;
             }
-            st.scoreLimit = (st.bestScore < A.maxK ? st.bestScore : A.maxK) + A.extra;
+            const uint32_t newLimit = (st.bestScore < A.maxK ? st.bestScore : A.maxK) + A.extra;
+            // (score_batched counts the settled positions after this slot's element with it)
+            if (newLimit != st.scoreLimit && lane == 0) G.limAfter[csl] = newLimit;
+            st.scoreLimit = newLimit;
             PH_ADD(A, S, PH_SUCC, tsu);
         }
     }
@@ -751,15 +755,32 @@ __device__ __forceinline__ bool forced_sort(const KArgs &A, Lds<MAXLEN> &S, Elem
 // per lane; round 6: forced mode's LV calls at those limits were 5.0 per C2 read and 10.4 per C3 read).  The limit only shrinks, so a distance above it fails at every later limit too: those
 // candidates are applied as failures without an LV pass (pass_apply); the rest -- possible successes,
 // which need their LV path for the match probability -- still go through lv_group.  Result per lane:
-// FRES_VALID | bit | e1 << 8 | e2 << 11 (7: above the limit), 0 when the lane's element has no
-// candidate the filter can settle (none unscored, lps above the limit, or a window short of n + MAX_K
-// bases at a contig end, whose text bound lv_group handles).
+// FRES_VALID | bit | e1 << 8 | e2 << 11 (7: above the limit), none of these when the lane's element has
+// no candidate the filter can settle (none unscored, lps above the limit, or a window short of n + MAX_K
+// bases at a contig end, whose text bound lv_group handles); and, at the position's first lane, the
+// element's lps and class (FRES_SETTLED / FRES_LIVE below).
 constexpr int FKM = 5;                     // lv_lane.h KM: the pair filter runs at limits k <= 5 (6 and 7 on pairs
                                            // spill more than they save: prefilter_range_r05m.txt); limits 6 and 7
                                            // take the quad form (LQ_K)
 constexpr uint32_t FILTER_MIN = 2;         // elements left in the order for a filter pass to pay off
 constexpr uint32_t FWIN = WAVE / 2;        // pop-order positions per pair filter pass (a lane pair each; quads: FWIN / 2)
 constexpr uint32_t FRES_VALID = 1u << 31;
+// The class of a window position, in the result word of its first lane (the other lanes, and lanes past the
+// window's positions, hold none of these bits):
+//   settled  the filter computed the element's only pending candidate and its distances fail at the limit.  Forced
+//            mode ends the read, so all that can still be observed of the element is nLocationsScored += 1, and
+//            only if its lps is <= the score limit in force at its turn: a failure leaves bestScore = FAIL_SCORE
+//            and prob = 0 (or, with candidates scored before, just one more scored bit), which a later success's
+//            nearby-element step (pass_apply) treats exactly as an element it does not find -- it subtracts 0.0
+//            from pAll and zeroes a zero prob.  score_batched counts such positions and never fetches them.
+//   void     lps above the limit at filter time; the limit only shrinks, so the element is never scored.
+//   live     everything else: goes through a batch.
+// With stopOnFirstHit a success ends the read mid-batch, where the settled positions before it would have to be
+// told from those after it: nothing is classified settled then.
+constexpr uint32_t FRES_ONE = 1u << 6;         // (inside forced_filter only) a single pending candidate
+constexpr int FRES_LPS_SHIFT = 16;             // the element's lps, 8 bits
+constexpr uint32_t FRES_SETTLED = 1u << 24;
+constexpr uint32_t FRES_LIVE = 1u << 25;
 
 // forced_filter's masks of one lane, F_x[m] = read[dir][m] != genome[loc + x + m] on the bit planes: pair half h
 // holds forward diagonal x = h ? i : -i at local i; quad lane h holds x = 4h + i - LQ_K at local i.  The genome
@@ -842,8 +863,14 @@ __device__ __forceinline__ uint32_t forced_filter(const KArgs &A, Lds<MAXLEN> &S
         h3 = reinterpret_cast<const uint4 *>(hp)[3];
     }
     const uint64_t pend = (((uint64_t)h0.y << 32) | h0.x) & ~(((uint64_t)h0.w << 32) | h0.z);
-    act = act && pend != 0 && ((w11 >> 8) & 0xffu) <= st.scoreLimit;
+    const uint32_t lps = (w11 >> 8) & 0xffu;
+    // the result word so far (one register across the distance calls): at the position's first lane its lps
+    // and FRES_LIVE unless the lps is above the limit (void); FRES_ONE: a single pending candidate
+    uint32_t rw = act && h == 0 && lps <= st.scoreLimit ? FRES_LIVE | lps << FRES_LPS_SHIFT : 0u;
+    act = act && pend != 0 && lps <= st.scoreLimit;
     const uint32_t bit = act ? (uint32_t)__builtin_ctzll(pend) : 0u;
+    rw |= bit | (act && (pend & (pend - 1)) == 0 ? FRES_ONE : 0u);
+    __asm__ volatile("" : "+v"(rw));   // packed here: the header words it came from are not kept live instead
     const uint32_t loc = (key >> 1) * ELEM + bit, dir = key & 1u;
     const uint32_t sp = spill_index(w11);
     int s = 0;
@@ -860,7 +887,11 @@ __device__ __forceinline__ uint32_t forced_filter(const KArgs &A, Lds<MAXLEN> &S
         if constexpr (QUAD) e2 = lv_quad_dist<-1>(F, h, e1 >= 0, 127 - (s - 1), s, s + MAX_K, k - e1);
         else e2 = lv_pair_dist<FKM, -1>(F, h, e1 >= 0, 127 - (s - 1), s, s + MAX_K, k - e1);
     }
-    return act ? FRES_VALID | bit | (uint32_t)(e1 < 0 ? 7 : e1) << 8 | (uint32_t)(e2 < 0 ? 7 : e2) << 11 : 0u;
+    const int a = e1 < 0 ? 7 : e1, b = e2 < 0 ? 7 : e2;
+    // settled: its only pending candidate fails at k (the test of cand_needs_lv), so at every later limit too
+    const bool settled = act && (rw & FRES_ONE) && !(a <= k && b <= k - a) && !A.stopOnFirst;
+    const uint32_t cls = rw & FRES_LIVE ? (settled ? FRES_SETTLED : FRES_LIVE) | (rw & 0xffu << FRES_LPS_SHIFT) : 0u;
+    return (act ? FRES_VALID | (rw & 63u) | (uint32_t)a << 8 | (uint32_t)b << 11 : 0u) | cls;
 }
 
 // BaseAligner::score (BaseAligner.cpp:977-1399) over batches of popped elements.
@@ -888,6 +919,10 @@ __device__ __forceinline__ bool score_batched(const KArgs &A, Lds<MAXLEN> &S, El
     const uint64_t *fSorted = nullptr;   // radix-sorted pop order (reads with >= A.radixMin elements)
     // forced_filter's window over pop-order positions [wBase, wEnd): lanes j << fShift .. hold position wBase + j
     uint32_t fres = 0, wBase = 0, wEnd = 0, fShift = 1;   // fShift: log2 of the lanes per position (pairs 1, quads 2)
+    // limAfter[slot]: the score limit a success in that slot's element last set.  The limit only shrinks, so an
+    // entry left from an earlier batch of this read is >= the limit before any later batch and changes no minimum
+    // taken with it; only another read's entries have to go.
+    if (forced && lane < EB) G.limAfter[lane] = NONE;   // (entry EB: the limit before the current window batch)
     for (uint32_t guard = 0;; guard++) {
         // lane id re-read per batch (volatile asm): masks and addresses derived from it are
         // recomputed in the batch instead of hoisted and kept live, spilled, across the pass loop
@@ -899,7 +934,8 @@ __device__ __forceinline__ bool score_batched(const KArgs &A, Lds<MAXLEN> &S, El
         if (overdue(A, st, 1)) return true;
         PH_T(A, tpop);
         // ---- pop in weight-list order (head of the highest list first); LDS only
-        uint32_t nb = 0, posb = 0;   // batch size, its first pop-order position (forced mode)
+        uint32_t nb = 0;             // batch size
+        bool inW = false;            // forced mode: the batch comes from the filter window
         if (!forced) {
             // sort keys are unique: reduce the 32-bit keys, then take the owner lane's index
             const uint64_t lm = S.laneMax[lane];
@@ -979,12 +1015,41 @@ __device__ __forceinline__ bool score_batched(const KArgs &A, Lds<MAXLEN> &S, El
 #endif
                 }
             }
-            posb = fDone;
-            nb = fAvail - fDone < (uint32_t)EB ? fAvail - fDone : (uint32_t)EB;
-            if ((uint32_t)lane < nb)
-                G.eidx[lane] = fSorted ? (uint32_t)fSorted[fAvail - 1 - (fDone + (uint32_t)lane)]
-                                       : (uint32_t)order[fDone - ordBase + lane];
-            fDone += nb;
+            inW = fDone < wEnd;
+            if (inW) {
+                // the batch is the next <= EB live positions of the window, compacted in pop order.  fDone moves
+                // on after the batch, once the settled positions of the batch's span are counted (below).
+                const uint32_t start = (fDone - wBase) << fShift;   // first lane of position fDone
+                const bool live = (fres & FRES_LIVE) != 0u && (uint32_t)lane >= start;
+                const uint64_t lm = ballot(live);
+                const uint32_t rank = (uint32_t)__popcll(lm & ((1ull << lane) - 1));
+                const uint32_t nl = (uint32_t)__popcll(lm);
+                nb = nl < (uint32_t)EB ? nl : (uint32_t)EB;
+                if (live && rank < (uint32_t)EB) {
+                    const uint32_t pos = wBase + ((uint32_t)lane >> fShift);
+                    G.eidx[rank] = fSorted ? (uint32_t)fSorted[fAvail - 1 - pos] : (uint32_t)order[pos - ordBase];
+                    // the filter's distances of the element's first pending candidate, in cand_* form, for the
+                    // list build below (which reads its slot's entry before it writes the list)
+                    G.cand[rank] = (uint16_t)(fres & FRES_VALID ? (fres & 63u) | 1u << 9 | ((fres >> 8) & 63u) << 10 : 0u);
+                }
+                if (nb == 0) {
+                    // no live position left: the window's remaining settled positions, at the limit in force
+                    const bool sp = (fres & FRES_SETTLED) != 0u && (uint32_t)lane >= start;
+                    const uint32_t ns = (uint32_t)__popcll(ballot(sp));
+                    const uint32_t nsc = (uint32_t)__popcll(ballot(sp && ((fres >> FRES_LPS_SHIFT) & 0xffu) <= st.scoreLimit));
+                    st.statv += lane == SV_SCORED ? nsc : (lane == SV_FSETTLED ? ns : 0u);
+                    fDone = wEnd;
+                    PH_ADD(A, S, PH_POP, tpop);
+                    continue;
+                }
+                if (lane == 0) G.limAfter[EB] = st.scoreLimit;   // the limit before the batch
+            } else {
+                nb = fAvail - fDone < (uint32_t)EB ? fAvail - fDone : (uint32_t)EB;
+                if ((uint32_t)lane < nb)
+                    G.eidx[lane] = fSorted ? (uint32_t)fSorted[fAvail - 1 - (fDone + (uint32_t)lane)]
+                                           : (uint32_t)order[fDone - ordBase + lane];
+                fDone += nb;
+            }
             wave_sync();
         }
         if (nb == 0) {
@@ -1027,13 +1092,9 @@ __device__ __forceinline__ bool score_batched(const KArgs &A, Lds<MAXLEN> &S, El
                     pend = (((uint64_t)ec[1] << 32) | ec[0]) & ~(((uint64_t)ec[3] << 32) | ec[2]);
             }
             const uint32_t cnt = (uint32_t)__popcll(pend);
-            // the filter's result for this element (pop-order position posb + lane), if in its window
-            const uint32_t wl = posb + (uint32_t)lane - wBase;
-            const uint32_t fr = (uint32_t)shfl_idx((int)fres, (int)((wl << fShift) & 63u));
-            const bool inWin = forced && posb + (uint32_t)lane >= wBase && posb + (uint32_t)lane < wEnd &&
-                               (uint32_t)lane < nb && (fr & FRES_VALID);
-            const uint32_t known = inWin ? (1u << 9) | ((fr >> 8) & 7u) << 10 | ((fr >> 11) & 7u) << 13 : 0u;
-            const uint32_t kbit = fr & 63u;
+            // the filter's result for this element, if it came from the window (the pop left it in cand[slot])
+            const uint32_t kw = inW && (uint32_t)lane < nb ? (uint32_t)G.cand[lane] : 0u;
+            const uint32_t known = kw & 0xfe00u, kbit = kw & 63u;
             // exclusive prefix sum over lanes 0..EB-1
             uint32_t pos = 0;
 #pragma unroll
@@ -1124,6 +1185,35 @@ __device__ __forceinline__ bool score_batched(const KArgs &A, Lds<MAXLEN> &S, El
         wave_sync();
         PH_ADD(A, S, PH_WB, twb);
         if (!forced) return false;
+        if (fDone < wEnd) {   // (a window batch: the others have moved fDone past the window)
+            // ---- the settled positions of the batch's span, which ends at the next live position after the batch
+            // (the window's end when there is none): each counts as a scored location if its lps is <= the limit
+            // in force at its turn -- the limit before the batch, lowered by the successes of the batch's
+            // elements before it in pop order (limAfter, written by pass_apply's success step)
+            const int lane = lane_id();
+            const uint32_t start = (fDone - wBase) << fShift;
+            const bool live = (fres & FRES_LIVE) != 0u && (uint32_t)lane >= start;
+            uint64_t lm = ballot(live);
+            const bool more = (uint32_t)__popcll(lm) > (uint32_t)EB;   // live positions left for the next batch
+            const uint32_t rank = (uint32_t)__popcll(lm & ((1ull << lane) - 1));
+            const uint32_t end = more ? (uint32_t)__builtin_ctzll(ballot(live && rank == (uint32_t)EB)) : (uint32_t)WAVE;
+            const bool sp = (fres & FRES_SETTLED) != 0u && (uint32_t)lane >= start && (uint32_t)lane < end;
+            const uint32_t lim0 = uni(G.limAfter[EB]);   // the limit before the batch (kept in LDS, not in a register)
+            uint32_t lim = lim0, spans = 0;
+            if (st.scoreLimit != lim0) {
+                for (uint32_t j = 0; j < nb; j++) {   // slot j is the j-th live position
+                    const int lj = (int)__builtin_ctzll(lm);
+                    lm &= lm - 1;
+                    const uint32_t v = G.limAfter[j];
+                    lim = lane > lj && v < lim ? v : lim;
+                }
+                spans = ballot(sp && lim != lim0) != 0 ? 1u : 0u;
+            }
+            const uint32_t ns = (uint32_t)__popcll(ballot(sp));
+            const uint32_t nsc = (uint32_t)__popcll(ballot(sp && ((fres >> FRES_LPS_SHIFT) & 0xffu) <= lim));
+            st.statv += lane == SV_SCORED ? nsc : (lane == SV_FSETTLED ? ns : (lane == SV_FSPANS ? spans : 0u));
+            fDone = more ? wBase + (end >> fShift) : wEnd;
+        }
     }
 }
 

@@ -732,6 +732,13 @@ __device__ __forceinline__ void align_one(const KArgs &A, Lds<MAXLEN> &S, ElemOf
         A.out[r] = o;
     }
     if constexpr (EXT) { if (A.maxHitsToGet) fill_hits(A, r, run && fillHits); }
+    if constexpr (MAXLEN == 128) {   // the forced-mode counters of the call (reads that retired elements only)
+        const uint32_t svSettled = sv_get(st, SV_FSETTLED), svSpans = sv_get(st, SV_FSPANS);
+        if (svSettled != 0 && lane_id() == 0) {
+            atomicAdd(A.forcedStats, svSettled);
+            if (svSpans) atomicAdd(A.forcedStats + 1, svSpans);
+        }
+    }
     wave_sync();
     PH_ADD(A, S, PH_OUT, tout);
     PH_ADD(A, S, PH_READCYC, tsetup);
@@ -2095,6 +2102,7 @@ static int launch_passes(snapgpu_aligner_t *a, int li, const PassIO &io, const A
     A.counter = L.counter; A.arena = L.arena; A.arenaElems = a->arenaCap;
     if (a->arenaCap < a->arenaElems) { A.ovfList = io.ovf; A.ovfCount = L.counter + 6; }
     A.deferList = io.defer; A.deferCount = L.counter + 2; A.readList = nullptr;
+    A.forcedStats = L.counter + 10;
     A.search = x.search; A.maxHitsToGet = x.maxHitsToGet;
     A.hitSlot = x.maxHitsToGet < 512 ? x.maxHitsToGet : 512;
     A.hitStride = multiHitStride(x.maxHitsToGet);
@@ -2169,7 +2177,7 @@ static int launch_passes(snapgpu_aligner_t *a, int li, const PassIO &io, const A
         HIPCHK(hipGetLastError());
     }
     HIPCHK(hipEventRecord(ev.e[2], L.stream));
-    HIPCHK(hipMemcpyAsync(ev.hCounter, L.counter, 32, hipMemcpyDeviceToHost, L.stream));
+    HIPCHK(hipMemcpyAsync(ev.hCounter, L.counter, 48, hipMemcpyDeviceToHost, L.stream));
     return SNAPGPU_OK;
 }
 
@@ -2235,6 +2243,8 @@ static int accountEvSet(snapgpu_aligner_t *a, const EvSet &v) {
     a->timing.nSpilled += v.hCounter[2];
     a->timing.nByteReads += v.hCounter[4];
     a->timing.nArenaOverflow += v.hCounter[6];
+    a->timing.nForcedSettled += v.hCounter[10];
+    a->timing.nForcedLimitSpans += v.hCounter[11];
     return SNAPGPU_OK;
 }
 

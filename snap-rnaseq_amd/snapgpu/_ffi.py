@@ -159,6 +159,8 @@ class Timing(C.Structure):
         ("nArenaOverflow", C.c_uint64),
         ("nNulReads", C.c_uint64),
         ("nUnwritten", C.c_uint64),
+        ("nForcedSettled", C.c_uint64),
+        ("nForcedLimitSpans", C.c_uint64),
     ]
 
 
