@@ -30,6 +30,7 @@
 #include <type_traits>
 
 #include "snapgpu.h"
+#include "small_div.h"
 
 namespace sgk {
 
@@ -63,6 +64,7 @@ struct DevTables {
     // The first 16 seed offsets of the seed sequence (BaseAligner.cpp:686-746) of a read of length n
     // whose bases are all ACGT: the sequence then depends on n and seedLen only (0xff: not reached)
     uint8_t seedSeq[129][16];
+    uint32_t rcp16[SDIV_MAX_D + 1];   // rcp16_of(d) (small_div.h): the lps quotient's reciprocal, read when the seeds wrap
 };
 // The seedLen-independent tables (indel, phred, perfect, mapqT), one copy per device, set
 // once by the host: a global's address is a constant the compiler rematerializes, where a
@@ -815,7 +817,8 @@ __device__ __forceinline__ void diag_report(uint32_t *d, uint32_t code, uint32_t
 }
 
 struct ReadState {
-    uint32_t lps[2], mostSeeds[2], nSeedsApplied[2];
+    uint32_t lps[2], nSeedsApplied[2];
+    uint32_t seedsRcp;           // rcp16_of(mostSeedsContainingAnyParticularBase), the same in both directions
     uint32_t bestScore, bestLoc, scoreLimit;
     double pAll, pBest;
     uint32_t outLoc, outDir;
@@ -827,6 +830,15 @@ struct ReadState {
     uint32_t tick;               // overdue(): calls left until the next clock read
     uint64_t t0;                 // s_memrealtime at read start
 };
+
+// lowerBoundPerSeed at the head of score (BaseAligner.cpp:993-996): max(lps, nSeedsApplied /
+// mostSeedsContainingAnyParticularBase), all wave-uniform, the quotient by small_div.h
+__device__ __forceinline__ void lps_update(ReadState &st) {
+    for (int d = 0; d < 2; d++) {
+        const uint32_t v = quot_rcp16(st.nSeedsApplied[d], st.seedsRcp);
+        if (v > st.lps[d]) st.lps[d] = v;
+    }
+}
 
 // per-read statistics: lane SV_x of ReadState::statv
 enum : int { SV_LOOKUPS = 0, SV_SCORED = 1, SV_POPULAR = 2, SV_PROBES = 3, SV_HITWORDS = 4, SV_OVF = 5,

@@ -895,17 +895,16 @@ __device__ __forceinline__ uint32_t forced_filter(const KArgs &A, Lds<MAXLEN> &S
 }
 
 // BaseAligner::score (BaseAligner.cpp:977-1399) over batches of popped elements.
+// Returns true when the read's result is final.  The scorer's LV rows overlay the insertion table
+// (Lds::u), so a call that scored a batch and hands the read back to the seed loop clears the table
+// again; a call that finds no linked element -- most non-forced calls -- has written none of it.
 template <bool EXT, int MAXLEN>
 __device__ __forceinline__ bool score_batched(const KArgs &A, Lds<MAXLEN> &S, Elem64 *ar, ReadState &st, bool force,
                                            uint32_t n, int *result, uint32_t *flags) {
     const int lane = lane_id();
     auto &G = S.grp[0];
     const DevTables *tab = A.tab;
-    for (int d = 0; d < 2; d++)
-        if (st.mostSeeds[d]) {
-            const uint32_t v = uni(st.nSeedsApplied[d] / st.mostSeeds[d]);   // (VALU division: back to an SGPR)
-            if (v > st.lps[d]) st.lps[d] = v;
-        }
+    lps_update(st);
     const uint32_t minLps = st.lps[0] < st.lps[1] ? st.lps[0] : st.lps[1];
     const bool forced = force || minLps > st.scoreLimit;
     PH_CNT(A, S, PH_NSCORECALL, 1);
@@ -936,6 +935,7 @@ __device__ __forceinline__ bool score_batched(const KArgs &A, Lds<MAXLEN> &S, El
         // ---- pop in weight-list order (head of the highest list first); LDS only
         uint32_t nb = 0;             // batch size
         bool inW = false;            // forced mode: the batch comes from the filter window
+        uint32_t nc = 0;             // candidates listed from the batch
         if (!forced) {
             // sort keys are unique: reduce the 32-bit keys, then take the owner lane's index
             const uint64_t lm = S.laneMax[lane];
@@ -944,10 +944,28 @@ __device__ __forceinline__ bool score_batched(const KArgs &A, Lds<MAXLEN> &S, El
                 const int owner = (int)__builtin_ctzll(ballot((uint32_t)(lm >> 32) == kmax));
                 const uint32_t e = readlaneu((uint32_t)lm, owner);
                 sk_set(A, S, ar, e, 0);                       // unlink (BaseAligner.cpp:1391-1394)
-                wave_sync();
-                recompute_lane_max(A, S, ar, owner);
+                if (uni(S.nElems) <= (uint32_t)WAVE) {
+                    // a lane owns the elements e == lane mod 64: with at most 64 of them this was its only one
+                    if (lane == owner) S.laneMax[owner] = 0;
+                } else {
+                    wave_sync();
+                    recompute_lane_max(A, S, ar, owner);
+                }
                 if (lane == 0) G.eidx[0] = e;
                 nb = 1;
+                // Fetch and candidate list of the one element, whose index is wave-uniform: lane i loads
+                // dword i, the header fields come back through v_readlane, and candidate `bit` is written
+                // by lane `bit` at the rank of its bit among the pending ones (the list order: ascending
+                // bit).  No read-back of eidx or ecache, no prefix sum over batch slots.
+                constexpr int ED = Elem64::DWORDS;
+                uint32_t w = 0;
+                if (e < ELCAP) { if (lane < ED) w = S.eloc[e][lane]; }
+                else if (lane < ED) w = ((const uint32_t *)(ar + e))[lane];
+                if (lane < ED) G.ecache[0][lane] = w;
+                uint64_t pend = 0;
+                if (((rl(w, 11) >> 8) & 0xff) <= st.scoreLimit) pend = rl64(w, 0) & ~rl64(w, 2);   // (as below)
+                nc = (uint32_t)__popcll(pend);
+                if ((pend >> lane) & 1ull) G.cand[__popcll(pend & ((1ull << lane) - 1))] = (uint16_t)lane;   // slot 0, not known
                 wave_sync();
             }
         } else {
@@ -1055,62 +1073,63 @@ __device__ __forceinline__ bool score_batched(const KArgs &A, Lds<MAXLEN> &S, El
         if (nb == 0) {
             PH_ADD(A, S, PH_POP, tpop);
             if (forced) { finalize_read(A, st, result, flags); return true; }
-            return false;
+            return false;   // (nothing was linked: Lds::u still holds the clean insertion table)
         }
         PH_ADD(A, S, PH_SEL, tpop);
         PH_T(A, tfe);
         // ---- fetch the batch from the arena in one round trip.  (Loading the next forced batch
         // during this one's passes measured 1% slower: the 9 VGPRs it holds across the pass loop,
         // profiles/r03/ab/micro_opts_ab.txt.)
-        {
-            constexpr int ED = Elem64::DWORDS;
-            const uint32_t tot = nb * ED;
-            uint32_t v[FETCH_NLD];
+        if (forced) {   // (the non-forced pop has fetched and listed its one element)
+            {
+                constexpr int ED = Elem64::DWORDS;
+                const uint32_t tot = nb * ED;
+                uint32_t v[FETCH_NLD];
 #pragma unroll
-            for (int j = 0; j < FETCH_NLD; j++) {
-                const uint32_t idx = (uint32_t)(j * WAVE + lane);
-                const uint32_t e = idx < tot ? G.eidx[idx / ED] : 0u;
-                v[j] = idx >= tot ? 0u : (e < ELCAP ? S.eloc[e][idx % ED] : ((const uint32_t *)(ar + e))[idx % ED]);
-            }
+                for (int j = 0; j < FETCH_NLD; j++) {
+                    const uint32_t idx = (uint32_t)(j * WAVE + lane);
+                    const uint32_t e = idx < tot ? G.eidx[idx / ED] : 0u;
+                    v[j] = idx >= tot ? 0u : (e < ELCAP ? S.eloc[e][idx % ED] : ((const uint32_t *)(ar + e))[idx % ED]);
+                }
 #pragma unroll
-            for (int j = 0; j < FETCH_NLD; j++) {
-                const uint32_t idx = (uint32_t)(j * WAVE + lane);
-                if (idx < tot) G.ecache[idx / ED][idx % ED] = v[j];
+                for (int j = 0; j < FETCH_NLD; j++) {
+                    const uint32_t idx = (uint32_t)(j * WAVE + lane);
+                    if (idx < tot) G.ecache[idx / ED][idx % ED] = v[j];
+                }
+                wave_sync();
             }
-            wave_sync();
+            PH_ADD(A, S, PH_FETCH, tfe);
+            // ---- candidate list: elements in pop order, ascending bit; lane sl owns element sl
+            PH_T(A, tcl);
+            {
+                uint64_t pend = 0;
+                if ((uint32_t)lane < nb) {
+                    const uint32_t *ec = G.ecache[lane];
+                    if (((ec[11] >> 8) & 0xff) <= st.scoreLimit)   // cannot be scored (the limit only shrinks)
+                        pend = (((uint64_t)ec[1] << 32) | ec[0]) & ~(((uint64_t)ec[3] << 32) | ec[2]);
+                }
+                const uint32_t cnt = (uint32_t)__popcll(pend);
+                // the filter's result for this element, if it came from the window (the pop left it in cand[slot])
+                const uint32_t kw = inW && (uint32_t)lane < nb ? (uint32_t)G.cand[lane] : 0u;
+                const uint32_t known = kw & 0xfe00u, kbit = kw & 63u;
+                // exclusive prefix sum over lanes 0..EB-1
+                uint32_t pos = 0;
+#pragma unroll
+                for (int j = 0; j < EB; j++) {
+                    const uint32_t cj = (uint32_t)__builtin_amdgcn_readlane((int)cnt, j);
+                    if (j < lane) pos += cj;
+                }
+                nc = (uint32_t)__builtin_amdgcn_readlane((int)(pos + cnt), EB - 1);
+                while (pend) {
+                    const int bit = __builtin_ctzll(pend);
+                    pend &= pend - 1;
+                    G.cand[pos++] = (uint16_t)((uint32_t)bit | (uint32_t)lane << 6 | ((uint32_t)bit == kbit ? known : 0u));
+                }
+                wave_sync();
+            }
+            PH_ADD(A, S, PH_CANDL, tcl);
         }
-        PH_ADD(A, S, PH_FETCH, tfe);
-        // ---- candidate list: elements in pop order, ascending bit; lane sl owns element sl
         PH_CNT(A, S, PH_NBATCH, 1);
-        PH_T(A, tcl);
-        uint32_t nc;
-        {
-            uint64_t pend = 0;
-            if ((uint32_t)lane < nb) {
-                const uint32_t *ec = G.ecache[lane];
-                if (((ec[11] >> 8) & 0xff) <= st.scoreLimit)   // cannot be scored (the limit only shrinks)
-                    pend = (((uint64_t)ec[1] << 32) | ec[0]) & ~(((uint64_t)ec[3] << 32) | ec[2]);
-            }
-            const uint32_t cnt = (uint32_t)__popcll(pend);
-            // the filter's result for this element, if it came from the window (the pop left it in cand[slot])
-            const uint32_t kw = inW && (uint32_t)lane < nb ? (uint32_t)G.cand[lane] : 0u;
-            const uint32_t known = kw & 0xfe00u, kbit = kw & 63u;
-            // exclusive prefix sum over lanes 0..EB-1
-            uint32_t pos = 0;
-#pragma unroll
-            for (int j = 0; j < EB; j++) {
-                const uint32_t cj = (uint32_t)__builtin_amdgcn_readlane((int)cnt, j);
-                if (j < lane) pos += cj;
-            }
-            nc = (uint32_t)__builtin_amdgcn_readlane((int)(pos + cnt), EB - 1);
-            while (pend) {
-                const int bit = __builtin_ctzll(pend);
-                pend &= pend - 1;
-                G.cand[pos++] = (uint16_t)((uint32_t)bit | (uint32_t)lane << 6 | ((uint32_t)bit == kbit ? known : 0u));
-            }
-            wave_sync();
-        }
-        PH_ADD(A, S, PH_CANDL, tcl);
         PH_ADD(A, S, PH_POP, tpop);
         PH_CNT(A, S, PH_NCAND, nc);
         PH_CNT(A, S, PH_NPOPPED, nb);
@@ -1128,18 +1147,28 @@ __device__ __forceinline__ bool score_batched(const KArgs &A, Lds<MAXLEN> &S, El
             // the next Gn candidates that need LV (unknown distances, or filter distances that can still
             // succeed at k); the pass applies everything up to the last of them (the end when fewer)
             int m = 0;
-            for (uint32_t c0 = i0; c0 < nc && m < Gn; c0 += WAVE) {
+            uint32_t iEnd;
+            if (!forced) {
+                // no candidate has filter distances outside forced mode: the next Gn of the list, as they stand
                 const int lane = lane_id();
-                const uint32_t p = c0 + (uint32_t)lane;
-                const bool need = p < nc && cand_needs_lv(G.cand[p], k);
-                const uint64_t nm = ballot(need);
-                const int r = m + __popcll(nm & ((1ull << lane) - 1));
-                if (need && r < Gn) lvIdx[r] = (uint16_t)p;
-                m += __popcll(nm);
-                m = m < Gn ? m : Gn;
+                m = nc - i0 < (uint32_t)Gn ? (int)(nc - i0) : Gn;
+                if (lane < m) lvIdx[lane] = (uint16_t)(i0 + (uint32_t)lane);
+                iEnd = i0 + (uint32_t)m;
+                wave_sync();
+            } else {
+                for (uint32_t c0 = i0; c0 < nc && m < Gn; c0 += WAVE) {
+                    const int lane = lane_id();
+                    const uint32_t p = c0 + (uint32_t)lane;
+                    const bool need = p < nc && cand_needs_lv(G.cand[p], k);
+                    const uint64_t nm = ballot(need);
+                    const int r = m + __popcll(nm & ((1ull << lane) - 1));
+                    if (need && r < Gn) lvIdx[r] = (uint16_t)p;
+                    m += __popcll(nm);
+                    m = m < Gn ? m : Gn;
+                }
+                wave_sync();
+                iEnd = m == Gn ? (uint32_t)lvIdx[Gn - 1] + 1u : nc;
             }
-            wave_sync();
-            const uint32_t iEnd = m == Gn ? (uint32_t)lvIdx[Gn - 1] + 1u : nc;
             if (m > 0) {
                 PH_CNT(A, S, PH_NPASS, 1);
                 if (forced) PH_CNT(A, S, PH_NPASSF, 1);
@@ -1184,7 +1213,11 @@ __device__ __forceinline__ bool score_batched(const KArgs &A, Lds<MAXLEN> &S, El
         }
         wave_sync();
         PH_ADD(A, S, PH_WB, twb);
-        if (!forced) return false;
+        if (!forced) {
+            for (int i = lane; i < BT; i += WAVE) { S.u.ins.btKey[i] = NONE; S.u.ins.btMask[i] = 0; }
+            wave_sync();
+            return false;
+        }
         if (fDone < wEnd) {   // (a window batch: the others have moved fDone past the window)
             // ---- the settled positions of the batch's span, which ends at the next live position after the batch
             // (the window's end when there is none): each counts as a scored location if its lps is <= the limit

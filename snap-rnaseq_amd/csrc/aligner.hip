@@ -38,11 +38,7 @@ __device__ __forceinline__ bool score_wave(const KArgs &A, Lds<MAXLEN> &S, Elem5
     constexpr int NB = MAXLEN / 64;
     const int lane = lane_id();
     const DevTables *tab = A.tab;
-    for (int d = 0; d < 2; d++)
-        if (st.mostSeeds[d]) {
-            uint32_t v = uni(st.nSeedsApplied[d] / st.mostSeeds[d]);
-            if (v > st.lps[d]) st.lps[d] = v;
-        }
+    lps_update(st);
     do {
         if (overdue(A, st, 4)) return true;
         // head of the highest non-empty weight list == max sortkey over linked elements
@@ -222,6 +218,10 @@ __device__ __forceinline__ void insert_hits(const KArgs &A, Lds<MAXLEN> &S, Elem
     constexpr bool C64 = std::is_same<ElemOf<MAXLEN>, Elem64>::value;
     const int lane = lane_id();
     const uint32_t lim = lim0 + lim1;
+    // A seed with no overflow list has at most one hit per direction: wave-uniform values in lanes 0
+    // and 1, of different keys (the direction is part of the key), so each is its own group's leader
+    // and nothing is staged or compared.
+    const bool singles = !list0 && !list1;
     for (uint32_t b0 = 0; b0 < lim; b0 += WAVE) {
         if (overdue(A, st, 5)) break;
         const uint32_t i = b0 + lane;
@@ -237,44 +237,50 @@ __device__ __forceinline__ void insert_hits(const KArgs &A, Lds<MAXLEN> &S, Elem
         valid = valid && h >= offset;
         if constexpr (EXT) valid = valid && loc >= minLoc && loc <= maxLoc;   // BaseAligner.cpp:849-853
         uint32_t key = ((loc / ELEM) << 1) | dir;
-        S.u.ins.scrLoc[lane] = loc;
         uint32_t slot = 0;
-        // Group the batch's hits by element.  A seed's hits come in descending location order (the
-        // index keeps overflow lists sorted), so the hits of one element are neighbours among the valid
-        // lanes: a lane leads its group when its key differs from the previous valid lane's, and the
-        // group runs to the next leader.  A batch whose keys are not ordered that way (within each
-        // direction) takes the LDS hash table instead.
-        const uint64_t vm = ballot(valid);
-        const uint64_t lowV = vm & ((1ull << lane) - 1);
-        const bool hasPrev = lowV != 0;
-        const uint32_t pkey = (uint32_t)shfl_idx((int)key, hasPrev ? 63 - (int)__builtin_clzll(lowV) : lane);
-        const bool useTab = ballot(valid && hasPrev && ((pkey ^ key) & 1u) == 0 && key > pkey) != 0;
+        bool useTab = false;
         uint64_t grp;
         bool leader;
-        if (!useTab) {
-            leader = valid && (!hasPrev || pkey != key);
-            const uint64_t lm = ballot(leader);
-            const uint64_t above = lm & ~((2ull << lane) - 1);              // leaders after this lane
-            const uint64_t upto = above ? (above & (~above + 1)) - 1 : ~0ull;  // lanes before the next one
-            grp = leader ? vm & upto & ~((1ull << lane) - 1) : 0ull;
-            wave_sync();
+        if (singles) {
+            leader = valid;
+            grp = valid ? 1ull << lane : 0ull;
         } else {
-            if (valid) {
-                uint32_t s = (key * 2654435761u) >> 25;
-                for (int probe = 0;; probe++) {
-                    uint32_t old = atomicCAS(&S.u.ins.btKey[s], NONE, key);
-                    if (old == NONE || old == key) break;
-                    if (probe >= BT) { diag_report(A.diag, DIAG_BATCH_TABLE, st.rid, key); valid = false; break; }
-                    s = (s + 1) & (BT - 1);
+            S.u.ins.scrLoc[lane] = loc;
+            // Group the batch's hits by element.  A seed's hits come in descending location order (the
+            // index keeps overflow lists sorted), so the hits of one element are neighbours among the valid
+            // lanes: a lane leads its group when its key differs from the previous valid lane's, and the
+            // group runs to the next leader.  A batch whose keys are not ordered that way (within each
+            // direction) takes the LDS hash table instead.
+            const uint64_t vm = ballot(valid);
+            const uint64_t lowV = vm & ((1ull << lane) - 1);
+            const bool hasPrev = lowV != 0;
+            const uint32_t pkey = (uint32_t)shfl_idx((int)key, hasPrev ? 63 - (int)__builtin_clzll(lowV) : lane);
+            useTab = ballot(valid && hasPrev && ((pkey ^ key) & 1u) == 0 && key > pkey) != 0;
+            if (!useTab) {
+                leader = valid && (!hasPrev || pkey != key);
+                const uint64_t lm = ballot(leader);
+                const uint64_t above = lm & ~((2ull << lane) - 1);              // leaders after this lane
+                const uint64_t upto = above ? (above & (~above + 1)) - 1 : ~0ull;  // lanes before the next one
+                grp = leader ? vm & upto & ~((1ull << lane) - 1) : 0ull;
+                wave_sync();
+            } else {
+                if (valid) {
+                    uint32_t s = (key * 2654435761u) >> 25;
+                    for (int probe = 0;; probe++) {
+                        uint32_t old = atomicCAS(&S.u.ins.btKey[s], NONE, key);
+                        if (old == NONE || old == key) break;
+                        if (probe >= BT) { diag_report(A.diag, DIAG_BATCH_TABLE, st.rid, key); valid = false; break; }
+                        s = (s + 1) & (BT - 1);
+                    }
+                    slot = s;
                 }
-                slot = s;
+                wave_sync();
+                if (valid) atomicOr((unsigned long long *)&S.u.ins.btMask[slot], 1ull << lane);
+                wave_sync();
+                grp = valid ? S.u.ins.btMask[slot] : 0;
+                leader = valid && (__builtin_ctzll(grp) == lane);
+                wave_sync();
             }
-            wave_sync();
-            if (valid) atomicOr((unsigned long long *)&S.u.ins.btMask[slot], 1ull << lane);
-            wave_sync();
-            grp = valid ? S.u.ins.btMask[slot] : 0;
-            leader = valid && (__builtin_ctzll(grp) == lane);
-            wave_sync();
         }
         bool overflow = false;   // element arena exhausted (cannot happen at (maxSeeds+2)*maxHits; guarded)
         if (leader) {
@@ -308,7 +314,7 @@ __device__ __forceinline__ void insert_hits(const KArgs &A, Lds<MAXLEN> &S, Elem
                 while (m) {
                     int j = __builtin_ctzll(m);
                     m &= m - 1;
-                    uint32_t bit = S.u.ins.scrLoc[j] % ELEM;
+                    uint32_t bit = (singles ? loc : S.u.ins.scrLoc[j]) % ELEM;
                     uint32_t t = st.ts + b0 + j;
                     const uint64_t cb = 1ull << bit;
                     const bool had = (used & cb) != 0;
@@ -524,7 +530,7 @@ __device__ __forceinline__ void align_one(const KArgs &A, Lds<MAXLEN> &S, ElemOf
     PH_ADD(A, S, PH_SETUP, tsetup);
     if (run) {
         st.lps[0] = st.lps[1] = 0;
-        st.mostSeeds[0] = st.mostSeeds[1] = 1;
+        st.seedsRcp = rcp16_of(1);
         st.bestScore = UNUSED_SCORE;
         st.bestLoc = 0;
         st.scoreLimit = A.maxK + A.extra;
@@ -563,7 +569,7 @@ __device__ __forceinline__ void align_one(const KArgs &A, Lds<MAXLEN> &S, ElemOf
                 if (wrapCount >= seedLen) { force = true; wrapForced = true; }
                 else {
                     next = A.tab->wrap[wrapCount];
-                    st.mostSeeds[0] = st.mostSeeds[1] = wrapCount + 1;
+                    st.seedsRcp = A.tab->rcp16[wrapCount + 1];   // mostSeedsContainingAnyParticularBase = wrapCount + 1
                 }
             }
             if (!force) {
@@ -686,13 +692,7 @@ __device__ __forceinline__ void align_one(const KArgs &A, Lds<MAXLEN> &S, ElemOf
             PH_T(A, tsc);
             bool fin;
             if constexpr (Lds<MAXLEN>::BYTE_PATH) fin = score_wave<MAXLEN, EXT>(A, S, ar, st, force, n, rbF, rbR, &result, &flags);
-            else {
-                fin = score_batched<EXT, MAXLEN>(A, S, ar, st, force, n, &result, &flags);
-                if (!fin && !force) {   // the scorer's LV rows overlay the insertion table
-                    for (int i = lane; i < BT; i += WAVE) { S.u.ins.btKey[i] = NONE; S.u.ins.btMask[i] = 0; }
-                    wave_sync();
-                }
-            }
+            else fin = score_batched<EXT, MAXLEN>(A, S, ar, st, force, n, &result, &flags);   // (clears the insertion table it overlaid)
             PH_ADD(A, S, PH_SCORE, tsc);
             if (fin || force) { fillHits = !wrapForced; break; }
             if (overdue(A, st, 8)) break;
@@ -1032,6 +1032,7 @@ void fillTables(DevTables &t, uint32_t seedLen) {
     for (int q = 0; q < 72; q++) t.mapqT[q] = q < 70 ? pow(10.0, -q / 10.0) : 0.0;
     if (seedLen >= 16 && seedLen <= 25)
         for (int i = 0; i < 25; i++) t.wrap[i] = kWrap[seedLen - 16][i];
+    for (uint32_t d = 1; d <= SDIV_MAX_D; d++) t.rcp16[d] = rcp16_of(d);
     // seed_lookup_kernel's walk (seed_lookup.h) on an all-ACGT read of each length: rounds 0,
     // seedLen, ... then the wrap table's starts, skipping used offsets (BaseAligner.cpp:686-746)
     memset(t.seedSeq, 0xff, sizeof(t.seedSeq));
