@@ -368,6 +368,9 @@ typedef struct snapgpu_timing {
                                 candidate whose distances fail), counted without being fetched */
     uint64_t nForcedLimitSpans; /* ...batches in which a success lowered the score limit ahead of such
                                 elements, which were then counted with the limit at their turn */
+    uint64_t nSimpleReads;   /* records written by the simple pass (simple_align_kernel: reads whose
+                                seeds all point at one candidate), ahead of pass 1 */
+    uint64_t nSimpleBailed;  /* reads <= 128 bases the simple pass handed on to pass 1 */
 } snapgpu_timing_t;
 int snapgpu_last_timing(snapgpu_aligner_t *a, snapgpu_timing_t *t);
 
@@ -386,6 +389,10 @@ int snapgpu_aligner_max_k(const snapgpu_aligner_t *a);           /* getMaxK() */
  * environment variable SNAPGPU_OVERLAP sets the initial value).  0 serialises the kernels
  * (copies and host work still overlap them): each launch's duration is then its own. */
 int snapgpu_aligner_set_overlap(snapgpu_aligner_t *a, int overlap);
+/* Whether the simple pass runs ahead of pass 1 (default 1; SNAPGPU_SIMPLE_PASS sets the initial
+ * value).  It never runs with stopOnFirstHit, explorePopularSeeds, maxHitsToConsider >= 0xffff, a
+ * search window or multi-hit export.  Results do not depend on it. */
+int snapgpu_aligner_set_simple_pass(snapgpu_aligner_t *a, int on);
 /* Test hook (no reference equivalent): the aligner's next calls trip its device watchdog when
  * the batch's read `read_index` starts (0xffffffff: never), so the call fails with
  * SNAPGPU_EDEVICE.  Each aligner has its own watchdog record: a trip in one aligner neither

@@ -761,6 +761,11 @@ enum : int { PH_SETUP = 0, PH_LOOKUP, PH_INSERT, PH_SCORE, PH_POP, PH_NLVFU, PH_
              PH_RANK, PH_NELEMSF, PH_CANDL, PH_SUCC, PH_NEARBY, PH_PROB, PH_FAILS, PH_NFAILSTEP, PH_SUCCWB,
              PH_NPASSF, PH_PASSLOOPF, PH_HEAVYCYC, PH_NHEAVY, PH_NCANDF, PH_READCYC, PH_NFILTER, PH_NLVF, PH_NLVFK, PH_NFRES,
              PH_SLOTS = 48 };
+// -DSNAPGPU_PHASE_TIMERS=2 (`make PHASE_TIMERS=2`) is the timer build with six slots relabelled: the
+// wave cycles and the number of the reads that end with one element and one scored location, by their
+// lookups (<= 5, 6 .. 16, more).  The slots' usual counts are compiled out of that build.
+enum : int { PH_SIMPLE5CYC = PH_HEAVYCYC, PH_NSIMPLE5 = PH_NHEAVY, PH_SIMPLE16CYC = PH_NLVF, PH_NSIMPLE16 = PH_NLVFK,
+             PH_SIMPLEMORECYC = PH_NLVFU, PH_NSIMPLEMORE = PH_NLVF2 };
 __device__ __forceinline__ uint64_t clk() { return __builtin_amdgcn_s_memtime(); }
 #if SNAPGPU_PHASE_TIMERS
 #define PH_T(A, v) const uint64_t v = (A).phaseBuf ? sgk::clk() : 0

@@ -1172,7 +1172,7 @@ __device__ __forceinline__ bool score_batched(const KArgs &A, Lds<MAXLEN> &S, El
             if (m > 0) {
                 PH_CNT(A, S, PH_NPASS, 1);
                 if (forced) PH_CNT(A, S, PH_NPASSF, 1);
-#if SNAPGPU_PHASE_TIMERS
+#if SNAPGPU_PHASE_TIMERS == 1
                 if (forced) {   // LV'd candidates of forced passes, and those with filter distances (possible successes)
                     const int ln = lane_id();
                     const uint32_t lp = lvIdx[ln < m ? ln : 0];

@@ -16,6 +16,7 @@
 #include "align_device.h"
 #include "align_score.h"
 #include "seed_lookup.h"
+#include "simple_align.h"
 #include "cigar.h"
 #include "internal.h"
 #include "large_copy.h"
@@ -742,7 +743,15 @@ __device__ __forceinline__ void align_one(const KArgs &A, Lds<MAXLEN> &S, ElemOf
     wave_sync();
     PH_ADD(A, S, PH_OUT, tout);
     PH_ADD(A, S, PH_READCYC, tsetup);
+#if SNAPGPU_PHASE_TIMERS == 2
+    if (run && S.nElems == 1 && svScored == 1) {   // what a single-candidate pass could take, at the most
+        if (svLookups <= 5) { PH_ADD(A, S, PH_SIMPLE5CYC, tsetup); PH_CNT(A, S, PH_NSIMPLE5, 1); }
+        else if (svLookups <= (uint32_t)SEEDS_PER_READ) { PH_ADD(A, S, PH_SIMPLE16CYC, tsetup); PH_CNT(A, S, PH_NSIMPLE16, 1); }
+        else { PH_ADD(A, S, PH_SIMPLEMORECYC, tsetup); PH_CNT(A, S, PH_NSIMPLEMORE, 1); }
+    }
+#else
     if (run && S.nElems >= 64) { PH_ADD(A, S, PH_HEAVYCYC, tsetup); PH_CNT(A, S, PH_NHEAVY, 1); }
+#endif
 }
 
 template <int MAXLEN, bool EXT>
@@ -1217,6 +1226,8 @@ struct snapgpu_aligner {
     // forced mode: reads with at least this many elements get a radix-sorted pop order instead of
     // windowed ranks (SNAPGPU_RADIX_MIN; beyond SKCAP the ranks stage keys from HBM per window)
     uint32_t radixMin = SKCAP + 1;
+    bool simplePass = true;       // simple_align_kernel ahead of pass 1 (SNAPGPU_SIMPLE_PASS=0: off)
+    int gridSimple = 0;
     bool orderLong = true;        // pass 2's list longest-first (SNAPGPU_ORDER_LONG=0: pass 0's order)
     uint32_t tripRead = 0xffffffffu;   // test hook (snapgpu_aligner_debug_trip): trip the watchdog at this read
     snapgpu_timing_t timing{};
@@ -1858,6 +1869,7 @@ snapgpu_aligner_t *snapgpu_aligner_create(int device, const snapgpu_index_t *idx
     if (const char *t = getenv("SNAPGPU_RADIX_MIN"); t && atoll(t) > 0) a->radixMin = (uint32_t)atoll(t);
     if (const char *t = getenv("SNAPGPU_OVERLAP")) a->overlapKernels = atoi(t) != 0;
     if (const char *t = getenv("SNAPGPU_ORDER_LONG")) a->orderLong = atoi(t) != 0;
+    if (const char *t = getenv("SNAPGPU_SIMPLE_PASS")) a->simplePass = atoi(t) != 0;
     auto fail = [&](const char *what, hipError_t e) {
         snapgpu::setError(std::string(what) + ": " + hipGetErrorString(e));
         snapgpu_aligner_free(a);
@@ -1944,6 +1956,11 @@ snapgpu_aligner_t *snapgpu_aligner_create(int device, const snapgpu_index_t *idx
     // (the same code, LDS caps and registers; only the persistent grid shrinks)
     if (const char *t = getenv("SNAPGPU_WAVES_PER_CU"); t && atoi(t) > 0) perCU = std::min(perCU, atoi(t));
     a->grid = prop.multiProcessorCount * perCU;
+    {
+        int perCUs = 0;
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCUs, (const void *)simple_align_kernel, 64, 0);
+        a->gridSimple = prop.multiProcessorCount * (perCUs > 0 ? perCUs : 8);
+    }
     uint32_t maxSeeds = params->maxSeedsToUse ? params->maxSeedsToUse
                                               : (uint32_t)(params->maxSeedCoverage * params->maxReadSize / idx->seedLen);
     a->arenaElems = (uint64_t)(maxSeeds + 2) * params->maxHitsToConsider + 64;
@@ -2136,10 +2153,25 @@ static int launch_passes(snapgpu_aligner_t *a, int li, const PassIO &io, const A
     A.seedRecs = reinterpret_cast<const uint4 *>(io.seeds);
     HIPCHK(hipEventRecord(ev.e[0], L.stream));
     const bool ext = x.search || x.maxHitsToGet;
+    // the simple pass (simple_align.h) takes the single-candidate reads; pass 1 then runs over the
+    // list of the reads it left.  The list is pass 2's defer list: free from order_long_kernel's end
+    // until pass 2 writes it, and pass 1 has read it by then.  (The phase diagnostics time pass 1.)
+    if (a->simplePass && !ext && !A.stopOnFirst && !A.explore && A.maxHits >= 1 && A.maxHits < 0xffffu && A.seedRecs &&
+        !A.phaseBuf) {
+        KArgs Q = A;
+        Q.counter = L.counter + 8;
+        int gridS = a->gridSimple;
+        if ((uint64_t)gridS > io.n) gridS = (int)io.n;
+        hipLaunchKernelGGL(simple_align_kernel, dim3(gridS), dim3(64), 0, L.stream, Q, io.defer2, L.counter + 9,
+                           L.counter + 12);
+        HIPCHK(hipGetLastError());
+        A.readList = io.defer2; A.readCount = L.counter + 9;
+    }
     if (ext) hipLaunchKernelGGL((align_kernel<128, true>), dim3(grid), dim3(64), 0, L.stream, A);
     else hipLaunchKernelGGL((align_kernel<128, false>), dim3(grid), dim3(64), 0, L.stream, A);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(ev.e[1], L.stream));
+    A.readList = nullptr; A.readCount = nullptr;
     // pass 2: reads of 129..256 bases (bit planes, 256-bit masks)
     KArgs M = A;
     M.counter = L.counter + 3;
@@ -2178,7 +2210,7 @@ static int launch_passes(snapgpu_aligner_t *a, int li, const PassIO &io, const A
         HIPCHK(hipGetLastError());
     }
     HIPCHK(hipEventRecord(ev.e[2], L.stream));
-    HIPCHK(hipMemcpyAsync(ev.hCounter, L.counter, 48, hipMemcpyDeviceToHost, L.stream));
+    HIPCHK(hipMemcpyAsync(ev.hCounter, L.counter, 64, hipMemcpyDeviceToHost, L.stream));
     return SNAPGPU_OK;
 }
 
@@ -2246,6 +2278,8 @@ static int accountEvSet(snapgpu_aligner_t *a, const EvSet &v) {
     a->timing.nArenaOverflow += v.hCounter[6];
     a->timing.nForcedSettled += v.hCounter[10];
     a->timing.nForcedLimitSpans += v.hCounter[11];
+    a->timing.nSimpleBailed += v.hCounter[9];
+    a->timing.nSimpleReads += v.hCounter[12];
     return SNAPGPU_OK;
 }
 
@@ -2909,6 +2943,11 @@ int snapgpu_aligner_get_params(const snapgpu_aligner_t *a, snapgpu_aligner_param
 int snapgpu_aligner_set_overlap(snapgpu_aligner_t *a, int overlap) {
     if (!a) return SNAPGPU_EINVAL;
     a->overlapKernels = overlap != 0;
+    return SNAPGPU_OK;
+}
+int snapgpu_aligner_set_simple_pass(snapgpu_aligner_t *a, int on) {
+    if (!a) return SNAPGPU_EINVAL;
+    a->simplePass = on != 0;
     return SNAPGPU_OK;
 }
 int snapgpu_aligner_debug_trip(snapgpu_aligner_t *a, uint32_t read_index) {

@@ -476,6 +476,10 @@ class BaseAligner:
         """Let the pass sets of the two streams run concurrently (default) or one after the other."""
         _check(lib().snapgpu_aligner_set_overlap(self._h, int(bool(overlap))), "set_overlap")
 
+    def set_simple_pass(self, on):
+        """Run the single-candidate pass ahead of pass 1 (default) or not; results do not depend on it."""
+        _check(lib().snapgpu_aligner_set_simple_pass(self._h, int(bool(on))), "set_simple_pass")
+
     def debug_trip(self, read_index=0xffffffff):
         """Test hook: trip this aligner's device watchdog when read `read_index` of a batch starts."""
         _check(lib().snapgpu_aligner_debug_trip(self._h, int(read_index)), "debug_trip")

@@ -161,6 +161,8 @@ class Timing(C.Structure):
         ("nUnwritten", C.c_uint64),
         ("nForcedSettled", C.c_uint64),
         ("nForcedLimitSpans", C.c_uint64),
+        ("nSimpleReads", C.c_uint64),
+        ("nSimpleBailed", C.c_uint64),
     ]
 
 
@@ -295,6 +297,7 @@ _PROTOS = [
     ("snapgpu_aligner_get_stats", C.c_int, [C.c_void_p, C.POINTER(AlignerStats)]),
     ("snapgpu_aligner_max_k", C.c_int, [C.c_void_p]),
     ("snapgpu_aligner_set_overlap", C.c_int, [C.c_void_p, C.c_int]),
+    ("snapgpu_aligner_set_simple_pass", C.c_int, [C.c_void_p, C.c_int]),
     ("snapgpu_aligner_debug_trip", C.c_int, [C.c_void_p, C.c_uint32]),
     ("snapgpu_source_sha256", C.c_char_p, []),
     ("snapgpu_phase_cycles", C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_uint32, C.c_int]),

@@ -20,7 +20,7 @@ import shutil
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-KERNELS = {"align": "align_kernel<128, false>", "lookup": "seed_lookup_kernel", "copy": "copy_peak_kernel",
+KERNELS = {"align": "align_kernel<128, false>", "simple": "simple_align_kernel", "lookup": "seed_lookup_kernel", "copy": "copy_peak_kernel",
            "paired": "paired_kernel<128>",
            "gather": "gather_peak_kernel", "cigar": "cigar_kernel", "align512": "align_kernel<512, false>"}
 
@@ -123,12 +123,19 @@ def main(src, dst):
                         "uncorrected (MI355X_MICROARCH.md calibrates it for 16-B streaming reads only)"}
     a = out["kernels"].get("align", {})
     if "counters_per_dispatch" in a:
-        c = a["counters_per_dispatch"]
+        c = dict(a["counters_per_dispatch"])
+        hb = dict(a.get("hbm_bytes_per_dispatch_raw", {}))
+        # the simple pass runs once per align_kernel<128> dispatch over the same reads: per-read figures
+        # are the sums over both kernels (comparable with the rounds before it)
+        s = out["kernels"].get("simple", {})
+        for x, v in s.get("counters_per_dispatch", {}).items():
+            c[x] = c.get(x, 0) + v
+        for x, v in s.get("hbm_bytes_per_dispatch_raw", {}).items():
+            hb[x] = hb.get(x, 0) + v
         per_read = {x: c[x] / reads_per_launch for x in c}
         a["per_read"] = per_read
-        hb = a.get("hbm_bytes_per_dispatch_raw", {})
         traffic = {"lib_sha256": out["lib_sha256"], "kernel_source_sha256": out["kernel_source_sha256"],
-                   "kernel": KERNELS["align"], "reads_per_dispatch": reads_per_launch,
+                   "kernel": KERNELS["align"] + (" + " + KERNELS["simple"] if s else ""), "reads_per_dispatch": reads_per_launch,
                    "hbm_bytes_per_read": (hb.get("fetch", 0) + hb.get("write", 0)) / reads_per_launch,
                    "fetch_bytes_per_read": hb.get("fetch", 0) / reads_per_launch,
                    "write_bytes_per_read": hb.get("write", 0) / reads_per_launch,
@@ -143,6 +150,7 @@ def main(src, dst):
                    # share of the waves' lifetime (SQ_WAVE_CYCLES) each state takes: issuing VALU / any
                    # instruction, waiting on a counter (memory), waiting for a dependency to issue
                    "wave_state": a.get("wave_state"),
+                   "simple_wave_state": s.get("wave_state"),
                    "source": os.path.join(dst, "summary.json"),
                    "note": "rocprofv3 FETCH_SIZE + WRITE_SIZE (KiB x 1024) per dispatch / reads per dispatch; "
                            "uncorrected (random 4-16 B gathers: the guide's x2 streaming factor does not apply)"}
