@@ -534,10 +534,45 @@ int snapgpu_sam_format_gpu(snapgpu_aligner_t *a, const snapgpu_reads_t *reads, c
                            const int32_t *editDistance, const uint32_t *nOps, const uint32_t *ops,
                            const char *readGroup, const uint32_t *frontClipped, const uint32_t *unclippedLength,
                            char *out, uint64_t cap, uint64_t *used);
-/* kernel time (length + scan + write, HIP events) and download time of the last call */
+/* kernel time (length + scan + write, HIP events; a sorted call's sort step included) and download
+ * time of the last call */
 int snapgpu_sam_last_ms(snapgpu_aligner_t *a, double *kernelMs, double *downloadMs);
-/* Diagnostic: the kernel time of the last call by pass -- length, scan, write (with the check). */
+/* Diagnostic: the kernel time of the last call by pass -- length, scan, write (with the check).  A
+ * sorted call's sort step is in none of the three (snapgpu_sam_sort_ms). */
 int snapgpu_sam_pass_ms(snapgpu_aligner_t *a, double *lengthMs, double *scanMs, double *writeMs);
+
+/* `-so` on the device: the same lines in coordinate order (@HD SO:coordinate, snapgpu_sam_header with
+ * sorted = 1).  The sort key is SAMFormat::getSortInfo's location (SAM.cpp:639-685) of the line,
+ * computed from the record by the length pass, not parsed from text: 0xffffffff when RNAME is "*"
+ * or the piece's name is empty or begins with '*', else the offset of the first piece of that name
+ * + POS - 1.  A stable radix sort of (key, record index) follows the length pass; the scan and the
+ * write pass then run over output slots.  One call is one sort block, as in the product paths.
+ * Contract: the text is byte-identical to snapgpu_sam_sort_records(idx, <the unsorted text of the
+ * same call>) whenever no QNAME (the id up to its first space) holds a tab or a line feed.  With
+ * such a byte in a QNAME the host sorter reads shifted fields; the device order still follows the
+ * record's own key and is the one to trust.  There is no refusal and no scan of the ids. */
+/* snapgpu_sam_resident in coordinate order: same arguments, checks, asynchrony and ordering against
+ * the next snapgpu_align_resident; snapgpu_sam_download then returns the sorted text. */
+int snapgpu_sam_resident_sorted(snapgpu_aligner_t *a, snapgpu_device_reads_t *d, const snapgpu_reads_t *reads,
+                                const char *ids, const uint64_t *idOffsets, const uint32_t *idLengths,
+                                const char *readGroup);
+/* Waits; order[j] = the record (read index) whose line is the j-th of the sorted text, n entries: a
+ * caller reorders whatever else it keeps per read by it.  SNAPGPU_EINVAL when the batch's last SAM
+ * call was not snapgpu_sam_resident_sorted, or there was none. */
+int snapgpu_sam_order_download(snapgpu_aligner_t *a, snapgpu_device_reads_t *d, uint32_t *order);
+/* The batch form of the sorted call: snapgpu_sam_format_gpu's arguments, then order (n entries as
+ * above, or NULL). */
+int snapgpu_sam_format_gpu_sorted(snapgpu_aligner_t *a, const snapgpu_reads_t *reads, const char *ids,
+                                  const uint64_t *idOffsets, const uint32_t *idLengths, const snapgpu_result_t *results,
+                                  const int32_t *editDistance, const uint32_t *nOps, const uint32_t *ops,
+                                  const char *readGroup, const uint32_t *frontClipped, const uint32_t *unclippedLength,
+                                  char *out, uint64_t cap, uint64_t *used, uint32_t *order);
+/* The sort keys above of n records, computed on the host by the code the device length pass runs.
+ * Needs no GPU.  A stable argsort of them is the order of the sorted calls. */
+int snapgpu_sam_sort_keys(const snapgpu_index_t *idx, uint64_t n, const snapgpu_result_t *results, uint32_t *keys);
+/* HIP-event time of the sort step of the last device SAM call (order fill, radix sort, gather of the
+ * lengths); 0 after an unsorted call. */
+int snapgpu_sam_sort_ms(snapgpu_aligner_t *a, double *sortMs);
 /* The exact byte length of every line snapgpu_sam_format_clipped prints (same arguments, same
  * validation; NULL clip arrays mean the batch's own clip state, or unclipped), computed on the host
  * by the code the device length pass runs.  Needs no GPU. */

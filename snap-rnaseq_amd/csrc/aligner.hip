@@ -1153,6 +1153,11 @@ struct SamState {
     Buf len, scans, start, sums, text, bad;
     Buf bases, quals;   // the reads where the unclipped extents pass the resident upload (or the batch form's reads)
     Buf res, ed, nOps, ops;   // batch form: records and CIGARs from the host
+    // coordinate-sorted calls (samgpu::SortBuffers): keys, their sorted copy, 0 .. n - 1, the output
+    // order, the lengths in that order, rocPRIM's temporary storage
+    Buf key, keySorted, iota, order, slotLen, sortTemp;
+    bool sorted = false;      // the last call was a sorted one: `order` holds its n record indices
+    samline::SortArgs sortArgs{};   // samline::sortKey's per-piece tables in aux (samPrepare)
     std::vector<char> hAux;   // host copy of aux (alive while its upload may be in flight)
     uint64_t fullBytes = 0;   // bytes of bases / quals valid in `bases` / `quals` (resident: 0 = the batch's own)
     bool idsCached = false;   // aux holds the batch's own ids (reads->ids), with this read group:
@@ -1160,7 +1165,8 @@ struct SamState {
     bool cachedHasRg = false;
     uint64_t n = 0, textBound = 0;
     bool ran = false;
-    hipEvent_t ev[4] = {};    // before the length pass, after the check; after the length pass, after the scan
+    // before the length pass, after the check; after the length pass, after the scan; after the sort step
+    hipEvent_t ev[5] = {};
     double downloadMs = 0;
 };
 
@@ -1589,7 +1595,8 @@ void devFree(const snapgpu_aligner_t *a, void *p) {
 void hostPinnedFree(void *p) { if (p) hipHostFree(p); }
 
 void samStateFree(const snapgpu_aligner_t *a, SamState &S) {
-    for (auto *b : {&S.aux, &S.len, &S.scans, &S.start, &S.sums, &S.text, &S.bad, &S.bases, &S.quals, &S.res, &S.ed, &S.nOps, &S.ops}) {
+    for (auto *b : {&S.aux, &S.len, &S.scans, &S.start, &S.sums, &S.text, &S.bad, &S.bases, &S.quals, &S.res, &S.ed, &S.nOps, &S.ops,
+                    &S.key, &S.keySorted, &S.iota, &S.order, &S.slotLen, &S.sortTemp}) {
         devFree(a, b->p);
         b->p = nullptr;
         b->cap = 0;
@@ -3264,6 +3271,9 @@ static int samPrepare(snapgpu_aligner_t *a, SamState &S, const SamHostIn &H, boo
     std::vector<uint32_t> nameOff;
     std::string names;
     snapgpu::samPieceNames(g, nameOff, names);
+    std::vector<uint32_t> sortBase;
+    std::vector<uint8_t> sortNone;
+    snapgpu::samSortBases(g, sortBase, sortNone);
     const uint32_t rgLen = H.rg ? (uint32_t)strlen(H.rg) : 0u;
     uint64_t idBytes = 0, bound = 0;
     uint32_t maxName = 1;
@@ -3281,7 +3291,8 @@ static int samPrepare(snapgpu_aligner_t *a, SamState &S, const SamHostIn &H, boo
     const uint64_t oIdOff = 0, oIdLen = al16(oIdOff + n * 8), oFront = al16(oIdLen + n * 4),
                    oFull = al16(oFront + (H.unclipped ? n * 4 : 0)), oOff = al16(oFull + (H.unclipped ? n * 4 : 0)),
                    oLen = al16(oOff + (H.offsets ? n * 8 : 0)), oNameOff = al16(oLen + (H.offsets ? n * 4 : 0)),
-                   oNames = al16(oNameOff + nameOff.size() * 4), oRg = al16(oNames + names.size()),
+                   oNames = al16(oNameOff + nameOff.size() * 4), oSortBase = al16(oNames + names.size()),
+                   oSortNone = al16(oSortBase + sortBase.size() * 4), oRg = al16(oSortNone + sortNone.size()),
                    oIds = al16(oRg + rgLen), bytes = al16(oIds + idBytes) + 16;
     if (!skip) {
         if (S.ran && S.ev[1]) HIPCHK(hipEventSynchronize(S.ev[1]));   // an earlier call's kernels may still read aux
@@ -3296,6 +3307,8 @@ static int samPrepare(snapgpu_aligner_t *a, SamState &S, const SamHostIn &H, boo
         }
         memcpy(h + oNameOff, nameOff.data(), nameOff.size() * 4);
         memcpy(h + oNames, names.data(), names.size());
+        memcpy(h + oSortBase, sortBase.data(), sortBase.size() * 4);
+        memcpy(h + oSortNone, sortNone.data(), sortNone.size());
         if (rgLen) memcpy(h + oRg, H.rg, rgLen);
         if (idBytes) memcpy(h + oIds, H.ids, idBytes);
         // on the otherwise idle copy stream, and waited for: the host copy may go, and the side
@@ -3312,6 +3325,7 @@ static int samPrepare(snapgpu_aligner_t *a, SamState &S, const SamHostIn &H, boo
     A.pieceOffsets = a->dPieces;
     A.pieceNameOff = (const uint32_t *)(d + oNameOff);
     A.pieceNames = d + oNames;
+    S.sortArgs = samline::SortArgs{(const uint32_t *)(d + oSortBase), (const uint8_t *)(d + oSortNone)};
     A.nPieces = (int32_t)g.pieceOffsets.size();
     A.rg = H.rg ? d + oRg : nullptr;
     A.rgLen = rgLen;
@@ -3319,12 +3333,14 @@ static int samPrepare(snapgpu_aligner_t *a, SamState &S, const SamHostIn &H, boo
     return SNAPGPU_OK;
 }
 
-// Length pass, scan, write pass and check of n records on the side stream, into S's buffers.
-static int samLaunch(snapgpu_aligner_t *a, SamState &S, const samline::Args &A, uint64_t n) {
+// Length pass, scan, write pass and check of n records on the side stream, into S's buffers;
+// sorted: in the stable order of the records' coordinate-sort keys (S.order keeps that order).
+static int samLaunch(snapgpu_aligner_t *a, SamState &S, const samline::Args &A, uint64_t n, bool sorted) {
     for (auto &e : S.ev)
         if (!e) HIPCHK(hipEventCreate(&e));
     S.n = n;
     S.ran = true;
+    S.sorted = sorted;
     a->samLast = &S;
     if (n == 0) return SNAPGPU_OK;
     if (n > 0xffffffffull) { snapgpu::setError("batch too large"); return SNAPGPU_EINVAL; }
@@ -3336,8 +3352,20 @@ static int samLaunch(snapgpu_aligner_t *a, SamState &S, const samline::Args &A, 
     HIPCHK(samGrow(a, S.text, S.textBound + 16));
     const samgpu::Buffers B{(uint32_t *)S.len.p, (samline::Scans *)S.scans.p, (uint64_t *)S.start.p, (uint64_t *)S.sums.p, (char *)S.text.p,
                             S.textBound, (uint32_t *)S.bad.p, {S.ev[2], S.ev[3]}};
+    samgpu::SortBuffers SB{};
+    if (sorted) {
+        HIPCHK(samgpu::sortTempBytes(n, a->sideStream, &SB.tempBytes));
+        for (SamState::Buf *b : {&S.key, &S.keySorted, &S.iota, &S.order, &S.slotLen}) HIPCHK(samGrow(a, *b, n * 4));
+        HIPCHK(samGrow(a, S.sortTemp, SB.tempBytes));
+        SB.key = (uint32_t *)S.key.p; SB.keySorted = (uint32_t *)S.keySorted.p;
+        SB.iota = (uint32_t *)S.iota.p; SB.order = (uint32_t *)S.order.p;
+        SB.slotLen = (uint32_t *)S.slotLen.p;
+        SB.temp = S.sortTemp.p;
+        SB.keys = S.sortArgs;
+        SB.done = S.ev[4];
+    }
     HIPCHK(hipEventRecord(S.ev[0], a->sideStream));
-    HIPCHK(samgpu::launch(A, n, B, a->sideStream));
+    HIPCHK(samgpu::launch(A, n, B, a->sideStream, sorted ? &SB : nullptr));
     HIPCHK(hipEventRecord(S.ev[1], a->sideStream));
     return SNAPGPU_OK;
 }
@@ -3391,9 +3419,10 @@ static int samDownload(snapgpu_aligner_t *a, SamState &S, char *out, uint64_t ca
     return SNAPGPU_OK;
 }
 
-int snapgpu_sam_resident(snapgpu_aligner_t *a, snapgpu_device_reads_t *d, const snapgpu_reads_t *reads,
-                         const char *ids, const uint64_t *idOffsets, const uint32_t *idLengths,
-                         const char *readGroup) {
+// snapgpu_sam_resident and snapgpu_sam_resident_sorted
+static int samResident(snapgpu_aligner_t *a, snapgpu_device_reads_t *d, const snapgpu_reads_t *reads,
+                       const char *ids, const uint64_t *idOffsets, const uint32_t *idLengths,
+                       const char *readGroup, bool sorted) {
     if (!a || !d || !reads) { snapgpu::setError("sam_resident: null argument"); return SNAPGPU_EINVAL; }
     if (a->failed) { snapgpu::setError("aligner failed earlier (device timeout)"); return SNAPGPU_EDEVICE; }
     if (d->owner != a) { snapgpu::setError("sam_resident: the resident batch belongs to another aligner"); return SNAPGPU_EINVAL; }
@@ -3471,11 +3500,43 @@ int snapgpu_sam_resident(snapgpu_aligner_t *a, snapgpu_device_reads_t *d, const 
         HIPCHK(hipEventRecord(L.done, L.stream));
         HIPCHK(hipStreamWaitEvent(st, L.done, 0));
     }
-    if (int rc = samLaunch(a, S, A, reads->n)) return rc;
+    if (int rc = samLaunch(a, S, A, reads->n, sorted)) return rc;
     // the next pass set over these reads rewrites the records: it waits for the SAM kernels
     HIPCHK(hipEventRecord(a->residentSideDone, st));
     a->residentSidePending = true;
     return SNAPGPU_OK;
+}
+
+int snapgpu_sam_resident(snapgpu_aligner_t *a, snapgpu_device_reads_t *d, const snapgpu_reads_t *reads,
+                         const char *ids, const uint64_t *idOffsets, const uint32_t *idLengths,
+                         const char *readGroup) {
+    return samResident(a, d, reads, ids, idOffsets, idLengths, readGroup, false);
+}
+
+int snapgpu_sam_resident_sorted(snapgpu_aligner_t *a, snapgpu_device_reads_t *d, const snapgpu_reads_t *reads,
+                                const char *ids, const uint64_t *idOffsets, const uint32_t *idLengths,
+                                const char *readGroup) {
+    return samResident(a, d, reads, ids, idOffsets, idLengths, readGroup, true);
+}
+
+// Wait for S's kernels and copy the output order of its last (sorted) call to the host.
+static int samOrderDownload(snapgpu_aligner_t *a, SamState &S, uint32_t *order) {
+    if (S.n == 0) return SNAPGPU_OK;
+    if (int rc = waitEvent(a, S.ev[1])) return rc;
+    HIPCHK(hipMemcpy(order, S.order.p, S.n * 4, hipMemcpyDeviceToHost));
+    return SNAPGPU_OK;
+}
+
+int snapgpu_sam_order_download(snapgpu_aligner_t *a, snapgpu_device_reads_t *d, uint32_t *order) {
+    if (!a || !d) { snapgpu::setError("sam_order_download: null argument"); return SNAPGPU_EINVAL; }
+    if (a->failed) { snapgpu::setError("aligner failed earlier (device timeout)"); return SNAPGPU_EDEVICE; }
+    if (!d->sam.ran || !d->sam.sorted) {
+        snapgpu::setError("sam_order_download: the batch's last SAM call was not snapgpu_sam_resident_sorted (or there was none)");
+        return SNAPGPU_EINVAL;
+    }
+    if (!order && d->sam.n) { snapgpu::setError("sam_order_download: null argument"); return SNAPGPU_EINVAL; }
+    HIPCHK(hipSetDevice(a->device));
+    return samOrderDownload(a, d->sam, order);
 }
 
 int snapgpu_sam_download(snapgpu_aligner_t *a, snapgpu_device_reads_t *d, char *out, uint64_t cap, uint64_t *used) {
@@ -3486,11 +3547,12 @@ int snapgpu_sam_download(snapgpu_aligner_t *a, snapgpu_device_reads_t *d, char *
     return samDownload(a, d->sam, out, cap, used);
 }
 
-int snapgpu_sam_format_gpu(snapgpu_aligner_t *a, const snapgpu_reads_t *reads, const char *ids,
-                           const uint64_t *idOffsets, const uint32_t *idLengths, const snapgpu_result_t *results,
-                           const int32_t *editDistance, const uint32_t *nOps, const uint32_t *ops,
-                           const char *readGroup, const uint32_t *frontClipped, const uint32_t *unclippedLength,
-                           char *out, uint64_t cap, uint64_t *used) {
+// snapgpu_sam_format_gpu and snapgpu_sam_format_gpu_sorted (order: the output order, or null)
+static int samFormatBatch(snapgpu_aligner_t *a, const snapgpu_reads_t *reads, const char *ids,
+                          const uint64_t *idOffsets, const uint32_t *idLengths, const snapgpu_result_t *results,
+                          const int32_t *editDistance, const uint32_t *nOps, const uint32_t *ops,
+                          const char *readGroup, const uint32_t *frontClipped, const uint32_t *unclippedLength,
+                          char *out, uint64_t cap, uint64_t *used, bool sorted, uint32_t *order) {
     if (!a || !reads || !ids || !idOffsets || !idLengths || !results || !editDistance || !nOps || !ops || !used) {
         snapgpu::setError("sam_format: null argument");
         return SNAPGPU_EINVAL;
@@ -3528,8 +3590,27 @@ int snapgpu_sam_format_gpu(snapgpu_aligner_t *a, const snapgpu_reads_t *reads, c
     H.ids = ids; H.idOffsets = idOffsets; H.idLengths = idLengths;
     H.front = frontClipped; H.unclipped = unclippedLength; H.rg = readGroup;
     if (int rc = samPrepare(a, S, H, false, A)) return rc;
-    if (int rc = samLaunch(a, S, A, n)) return rc;
-    return samDownload(a, S, out, cap, used);
+    if (int rc = samLaunch(a, S, A, n, sorted)) return rc;
+    if (int rc = samDownload(a, S, out, cap, used)) return rc;
+    return sorted && order ? samOrderDownload(a, S, order) : SNAPGPU_OK;
+}
+
+int snapgpu_sam_format_gpu(snapgpu_aligner_t *a, const snapgpu_reads_t *reads, const char *ids,
+                           const uint64_t *idOffsets, const uint32_t *idLengths, const snapgpu_result_t *results,
+                           const int32_t *editDistance, const uint32_t *nOps, const uint32_t *ops,
+                           const char *readGroup, const uint32_t *frontClipped, const uint32_t *unclippedLength,
+                           char *out, uint64_t cap, uint64_t *used) {
+    return samFormatBatch(a, reads, ids, idOffsets, idLengths, results, editDistance, nOps, ops, readGroup, frontClipped,
+                          unclippedLength, out, cap, used, false, nullptr);
+}
+
+int snapgpu_sam_format_gpu_sorted(snapgpu_aligner_t *a, const snapgpu_reads_t *reads, const char *ids,
+                                  const uint64_t *idOffsets, const uint32_t *idLengths, const snapgpu_result_t *results,
+                                  const int32_t *editDistance, const uint32_t *nOps, const uint32_t *ops,
+                                  const char *readGroup, const uint32_t *frontClipped, const uint32_t *unclippedLength,
+                                  char *out, uint64_t cap, uint64_t *used, uint32_t *order) {
+    return samFormatBatch(a, reads, ids, idOffsets, idLengths, results, editDistance, nOps, ops, readGroup, frontClipped,
+                          unclippedLength, out, cap, used, true, order);
 }
 
 int snapgpu_sam_last_ms(snapgpu_aligner_t *a, double *kernelMs, double *downloadMs) {
@@ -3558,12 +3639,27 @@ int snapgpu_sam_pass_ms(snapgpu_aligner_t *a, double *lengthMs, double *scanMs, 
     if (S.n) {
         HIPCHK(hipEventSynchronize(S.ev[1]));
         HIPCHK(hipEventElapsedTime(&f[0], S.ev[0], S.ev[2]));
-        HIPCHK(hipEventElapsedTime(&f[1], S.ev[2], S.ev[3]));
+        HIPCHK(hipEventElapsedTime(&f[1], S.sorted ? S.ev[4] : S.ev[2], S.ev[3]));   // the sort step is not the scan's
         HIPCHK(hipEventElapsedTime(&f[2], S.ev[3], S.ev[1]));
     }
     *lengthMs = f[0];
     *scanMs = f[1];
     *writeMs = f[2];
+    return SNAPGPU_OK;
+}
+
+int snapgpu_sam_sort_ms(snapgpu_aligner_t *a, double *sortMs) {
+    if (!a || !sortMs) return SNAPGPU_EINVAL;
+    if (!a->samLast) { snapgpu::setError("sam_sort_ms: no device SAM call on this aligner"); return SNAPGPU_EINVAL; }
+    if (a->failed) { snapgpu::setError("aligner failed earlier (device timeout)"); return SNAPGPU_EDEVICE; }
+    HIPCHK(hipSetDevice(a->device));
+    SamState &S = *a->samLast;
+    float f = 0;
+    if (S.n && S.sorted) {
+        HIPCHK(hipEventSynchronize(S.ev[1]));
+        HIPCHK(hipEventElapsedTime(&f, S.ev[2], S.ev[4]));
+    }
+    *sortMs = f;
     return SNAPGPU_OK;
 }
 

@@ -149,6 +149,10 @@ void samPieceNames(const Genome &g, std::vector<uint32_t> &nameOff, std::string 
 // SAMFormat::getSortInfo, SAM.cpp:639-685): the records of `parts` (whole lines, in write order)
 // stable-sorted by their location key, concatenated
 std::string samSortRecords(const Genome &g, const std::vector<std::string> &parts);
+// what samline::sortKey (sam_line.h) needs per piece to give samSortRecords' key without the text:
+// base[p] = the offset of the first piece named as p (the sorter's name -> offset map keeps the
+// first of equal names), none[p] = 1 where the name is empty or begins with '*' ("no location")
+void samSortBases(const Genome &g, std::vector<uint32_t> &base, std::vector<uint8_t> &none);
 // bam.cpp: BAMFormat::writeRead of a read without mate, the BAM header, a BGZF writer
 bool bamAppendRecord(std::string &o, const Genome &g, const SamLine &L, int32_t nm);
 std::string bamHeader(const Genome &g, const std::string &samText);

@@ -580,7 +580,46 @@ std::string samSortRecords(const Genome &g, const std::vector<std::string> &part
     return out;
 }
 
+void samSortBases(const Genome &g, std::vector<uint32_t> &base, std::vector<uint8_t> &none) {
+    std::map<std::string, uint32_t> pieces;   // as samSortRecords builds it: the first of equal names stays
+    const size_t np = g.pieceNames.size();
+    base.assign(np, 0u);
+    none.assign(np, 0);
+    for (size_t i = 0; i < np; i++) {
+        base[i] = pieces.emplace(g.pieceNames[i], g.pieceOffsets[i]).first->second;
+        none[i] = g.pieceNames[i].empty() || g.pieceNames[i][0] == '*';
+    }
+}
+
 }  // namespace snapgpu
+
+// samline::sortKey of every record on the host (what the sorted device length pass stores)
+extern "C" int snapgpu_sam_sort_keys(const snapgpu_index_t *idx, uint64_t n, const snapgpu_result_t *results,
+                                     uint32_t *keys) {
+    if (!idx || !idx->genome || ((!results || !keys) && n)) {
+        setError("sam_sort_keys: null argument");
+        return SNAPGPU_EINVAL;
+    }
+    const Genome &g = *idx->genome;
+    std::vector<uint32_t> nameOff, base;
+    std::vector<uint8_t> none;
+    std::string names;
+    samPieceNames(g, nameOff, names);
+    samSortBases(g, base, none);
+    samline::Args A{};
+    A.res = results;
+    A.pieceOffsets = g.pieceOffsets.data();
+    A.pieceNameOff = nameOff.data();
+    A.pieceNames = names.data();
+    A.nPieces = (int32_t)g.pieceOffsets.size();
+    const samline::SortArgs K{base.data(), none.data()};
+    for (uint64_t i = 0; i < n; i++) {
+        samline::Fields F;
+        samline::locate(A, i, F);
+        keys[i] = samline::sortKey(K, F);
+    }
+    return SNAPGPU_OK;
+}
 
 extern "C" int snapgpu_sam_sort_records(const snapgpu_index_t *idx, const char *in, uint64_t n, char *out, uint64_t cap,
                                         uint64_t *used) {

@@ -9,7 +9,15 @@
 //           then the workgroup flushes the window with 16-byte lane-contiguous stores (the range's
 //           unaligned head and tail bytewise).  Nothing is stored outside [start[first], start[end)).
 // A last kernel counts the lines that do not end in '\n' where the scan says they end.
+//
+// Coordinate-sorted output (-so) is the same passes over output slots: the length pass also stores
+// each record's sort key, a stable radix sort of (key, record index) gives order[slot] = record, the
+// scan runs over the lengths gathered in that order, and the write pass formats record order[j]
+// into slot j.  A workgroup still owns kRecsPerGroup consecutive slots, one contiguous byte range.
 #include "sam_format.h"
+
+#include <cstring>
+#include <rocprim/rocprim.hpp>
 
 namespace samgpu {
 
@@ -51,8 +59,30 @@ struct Wave {
     __device__ bool lead() const { return lane == 0; }
 };
 
+// What only the sorted instances of the length and write kernels take, as their last argument: the
+// unsorted instances get an empty one, and keep the arguments they had before there was a sorted
+// launch (and with them their registers and code).
+template <bool Sorted>
+struct KeyOut {};
+template <>
+struct KeyOut<true> {
+    samline::SortArgs tables;
+    uint32_t *key;   // [n] out: samline::sortKey per record
+};
+template <bool Sorted>
+struct SlotOrder {
+    __device__ uint64_t record(uint64_t j) const { return j; }
+};
+template <>
+struct SlotOrder<true> {
+    const uint32_t *order;   // [n] output slot -> record
+    __device__ uint64_t record(uint64_t j) const { return order[j]; }
+};
+
+// Sorted: key[r] = the record's coordinate-sort key as well
+template <bool Sorted>
 __global__ __launch_bounds__(256) void sam_length_kernel(Args A, uint64_t n, uint32_t *__restrict__ len,
-                                                         samline::Scans *__restrict__ scans) {
+                                                         samline::Scans *__restrict__ scans, KeyOut<Sorted> K) {
     const Wave g{nullptr, 0, 0, threadIdx.x & 63u};
     const uint64_t waves = (uint64_t)gridDim.x * 4u;
     for (uint64_t r = (uint64_t)blockIdx.x * 4u + threadIdx.x / 64u; r < n; r += waves) {
@@ -60,8 +90,26 @@ __global__ __launch_bounds__(256) void sam_length_kernel(Args A, uint64_t n, uin
         if (g.lane == 0) {
             len[r] = samline::lineLength(A, F);
             scans[r] = samline::Scans{F.qlen, (uint16_t)F.seqLen, (uint16_t)F.qualLen};   // both <= kMaxSeq
+            if constexpr (Sorted) K.key[r] = samline::sortKey(K.tables, F);
         }
     }
+}
+
+// the sort's values before it runs: record j in slot j
+__global__ __launch_bounds__(256) void sam_iota_kernel(uint32_t *__restrict__ iota, uint64_t n) {
+    const uint64_t j = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (j < n) iota[j] = (uint32_t)j;
+}
+
+// slotLen[j] = len[order[j]]: the scan's input in output order (order holds a permutation of 0 .. n - 1;
+// an index that is not below n -- never -- reads nothing and gives a length the check kernel reports)
+__global__ __launch_bounds__(256) void sam_gather_len_kernel(const uint32_t *__restrict__ len,
+                                                             const uint32_t *__restrict__ order, uint64_t n,
+                                                             uint32_t *__restrict__ slotLen) {
+    const uint64_t j = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (j >= n) return;
+    const uint32_t r = order[j];
+    slotLen[j] = r < n ? len[r] : 0u;
 }
 
 constexpr uint32_t kPerThread = kScanTile / 256;
@@ -132,9 +180,12 @@ __global__ __launch_bounds__(256) void sam_scan_starts_kernel(const uint32_t *__
     }
 }
 
+// Sorted: start[] is over output slots and slot j prints record O.order[j] (scans[] stays per
+// record), else slot j prints record j.
+template <bool Sorted>
 __global__ __launch_bounds__(256) void sam_write_kernel(Args A, uint64_t n, const uint64_t *__restrict__ start,
                                                         const samline::Scans *__restrict__ scans,
-                                                        char *__restrict__ out, uint64_t cap) {
+                                                        char *__restrict__ out, uint64_t cap, SlotOrder<Sorted> O) {
     __shared__ uint4 tile[kTileBytes / 16];
     char *lds = reinterpret_cast<char *>(tile);
     const uint64_t first = (uint64_t)blockIdx.x * kRecsPerGroup;
@@ -146,9 +197,11 @@ __global__ __launch_bounds__(256) void sam_write_kernel(Args A, uint64_t n, cons
     for (uint64_t w0 = r0 & ~15ull; w0 < r1; w0 += kTileBytes) {
         const uint64_t w1 = w0 + kTileBytes < r1 ? w0 + kTileBytes : r1;
         const Wave g{lds, w0, w1, lane};
-        for (uint64_t r = first + wave; r < end; r += 4) {
-            const uint64_t s = start[r], e = start[r + 1];
+        for (uint64_t j = first + wave; j < end; j += 4) {
+            const uint64_t s = start[j], e = start[j + 1];
             if (e <= w0 || s >= w1) continue;
+            const uint64_t r = O.record(j);
+            if (Sorted && r >= n) continue;   // not a record (never): the slot is empty, the check reports it
             const samline::Scans known = scans[r];
             const Fields F = samline::fields(A, r, g, &known);
             samline::write(A, r, F, s, g);
@@ -179,21 +232,48 @@ __global__ __launch_bounds__(256) void sam_check_kernel(const uint64_t *__restri
 
 }  // namespace
 
-hipError_t launch(const Args &A, uint64_t n, const Buffers &B, hipStream_t st) {
+// rocPRIM's radix sort is stable in each of its algorithms (one workgroup, a merge of block-sorted
+// runs, onesweep passes): equal keys keep their input order, as std::stable_sort does in the host sorter.
+static hipError_t sortPairs(void *temp, size_t &bytes, const SortBuffers *S, uint64_t n, hipStream_t st) {
+    return rocprim::radix_sort_pairs(temp, bytes, S ? S->key : (uint32_t *)nullptr, S ? S->keySorted : (uint32_t *)nullptr,
+                                     S ? S->iota : (uint32_t *)nullptr, S ? S->order : (uint32_t *)nullptr, (size_t)n,
+                                     0u, 32u, st);
+}
+
+hipError_t sortTempBytes(uint64_t n, hipStream_t st, size_t *bytes) {
+    *bytes = 0;
+    return sortPairs(nullptr, *bytes, nullptr, n, st);
+}
+
+hipError_t launch(const Args &A, uint64_t n, const Buffers &B, hipStream_t st, const SortBuffers *S) {
     hipError_t e = hipMemsetAsync(B.bad, 0, sizeof(uint32_t), st);
     if (e != hipSuccess) return e;
     const uint64_t nTiles = scanTiles(n), nGroups = (n + kRecsPerGroup - 1) / kRecsPerGroup;
     const uint64_t lenBlocks = (n + 3) / 4 < 65536 ? (n + 3) / 4 : 65536;
-    hipLaunchKernelGGL(sam_length_kernel, dim3((unsigned)lenBlocks), dim3(256), 0, st, A, n, B.len, B.scans);
+    const dim3 perItem((unsigned)((n + 255) / 256));
+    if (S) hipLaunchKernelGGL(sam_length_kernel<true>, dim3((unsigned)lenBlocks), dim3(256), 0, st, A, n, B.len, B.scans,
+                              KeyOut<true>{S->keys, S->key});
+    else hipLaunchKernelGGL(sam_length_kernel<false>, dim3((unsigned)lenBlocks), dim3(256), 0, st, A, n, B.len, B.scans,
+                            KeyOut<false>{});
     if (B.mid[0] && (e = hipEventRecord(B.mid[0], st)) != hipSuccess) return e;
-    hipLaunchKernelGGL(sam_scan_sums_kernel, dim3((unsigned)nTiles), dim3(256), 0, st, B.len, n, B.sums);
+    const uint32_t *len = B.len;
+    if (S) {
+        hipLaunchKernelGGL(sam_iota_kernel, perItem, dim3(256), 0, st, S->iota, n);
+        size_t bytes = S->tempBytes;
+        if ((e = sortPairs(S->temp, bytes, S, n, st)) != hipSuccess) return e;
+        hipLaunchKernelGGL(sam_gather_len_kernel, perItem, dim3(256), 0, st, B.len, S->order, n, S->slotLen);
+        if (S->done && (e = hipEventRecord(S->done, st)) != hipSuccess) return e;
+        len = S->slotLen;
+    }
+    hipLaunchKernelGGL(sam_scan_sums_kernel, dim3((unsigned)nTiles), dim3(256), 0, st, len, n, B.sums);
     hipLaunchKernelGGL(sam_scan_tiles_kernel, dim3(1), dim3(256), 0, st, B.sums, nTiles, B.start + n);
-    hipLaunchKernelGGL(sam_scan_starts_kernel, dim3((unsigned)nTiles), dim3(256), 0, st, B.len, n, B.sums, B.start);
+    hipLaunchKernelGGL(sam_scan_starts_kernel, dim3((unsigned)nTiles), dim3(256), 0, st, len, n, B.sums, B.start);
     if (B.mid[1] && (e = hipEventRecord(B.mid[1], st)) != hipSuccess) return e;
-    hipLaunchKernelGGL(sam_write_kernel, dim3((unsigned)nGroups), dim3(256), 0, st, A, n, B.start, B.scans,
-                       B.text, B.textCap);
-    hipLaunchKernelGGL(sam_check_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, B.start, n, B.text,
-                       B.textCap, B.bad);
+    if (S) hipLaunchKernelGGL(sam_write_kernel<true>, dim3((unsigned)nGroups), dim3(256), 0, st, A, n, B.start, B.scans,
+                              B.text, B.textCap, SlotOrder<true>{S->order});
+    else hipLaunchKernelGGL(sam_write_kernel<false>, dim3((unsigned)nGroups), dim3(256), 0, st, A, n, B.start, B.scans,
+                            B.text, B.textCap, SlotOrder<false>{});
+    hipLaunchKernelGGL(sam_check_kernel, perItem, dim3(256), 0, st, B.start, n, B.text, B.textCap, B.bad);
     return hipGetLastError();
 }
 

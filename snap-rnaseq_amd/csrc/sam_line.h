@@ -48,6 +48,14 @@ struct Args {
     const char *rg;                      // null: no RG:Z: tag
 };
 
+// What the coordinate-sort key (sortKey below) needs beside Args, per piece: the offset of the first
+// piece that carries its name, and 1 where the name gives no location (empty, or it begins with '*').
+// Kept out of Args: the unsorted kernels take Args by value and keep their arguments and their code.
+struct SortArgs {
+    const uint32_t *base;
+    const uint8_t *none;
+};
+
 // What fields() decides about one line; write() places bytes by it.
 struct Fields {
     uint64_t readStart;   // first byte of the unclipped read in bases / quals
@@ -99,6 +107,36 @@ struct Scans {
     uint32_t qlen;
     uint16_t seqLen, qualLen;
 };
+
+// RNAME and POS of record i alone (F.piece, F.pieceLen, F.pos) -> the location getSAMData prints
+// them from: NotFound -> unmapped (kInvalid).  Reads A.res and the pieces only, for a caller that
+// has no reads or ids (snapgpu_sam_sort_keys).  fields() below sets the same three members by the
+// same statements, inline as they always were: the device kernels' code depends on their order.
+SAM_HD uint32_t locate(const Args &A, uint64_t i, Fields &F) {
+    uint32_t loc = A.res[i].location;
+    if (A.res[i].result == SNAPGPU_NOT_FOUND) loc = kInvalid;
+    F.piece = -1;
+    F.pieceLen = 1;
+    F.pos = 0;
+    if (loc != kInvalid) {
+        const int32_t p = pieceAt(A.pieceOffsets, A.nPieces, loc);
+        if (p >= 0) {
+            F.piece = p;
+            F.pieceLen = A.pieceNameOff[p + 1] - A.pieceNameOff[p];
+            F.pos = loc - A.pieceOffsets[p] + 1;
+        }
+    }
+    return loc;
+}
+
+// The coordinate-sort key of the line F prints: SAMFormat::getSortInfo's location (SAM.cpp:639-685),
+// as the host sorter (samSortKey, host/sam.cpp) reads it back from RNAME and POS -- kInvalid for
+// RNAME "*" and for a piece name that is empty or begins with '*', else the offset of the first
+// piece of that name + POS - 1 (uint32_t arithmetic).  F needs locate() only.
+SAM_HD uint32_t sortKey(const SortArgs &K, const Fields &F) {
+    if (F.piece < 0 || K.none[F.piece]) return kInvalid;
+    return K.base[F.piece] + F.pos - 1u;
+}
 
 template <class G>
 SAM_HD Fields fields(const Args &A, uint64_t i, const G &g, const Scans *known = nullptr) {

@@ -496,19 +496,28 @@ class BaseAligner:
         return ms.value
 
     # resident path (bench): upload once, time only the GPU passes
-    def sam_format(self, reads, ids, results, cigars, read_group="FASTQ", clip=None):
+    def sam_format(self, reads, ids, results, cigars, read_group="FASTQ", clip=None, sorted_output=False,
+                   return_order=False):
         """The module-level sam_format on the GPU (snapgpu_sam_format_gpu: uploads records and
-        CIGARs, runs the resident path's kernels, downloads the text) -> bytes."""
+        CIGARs, runs the resident path's kernels, downloads the text) -> bytes.  sorted_output: the
+        lines in coordinate order (`-so`, snapgpu_sam_format_gpu_sorted); return_order (with it):
+        -> (bytes, order uint32[n]), order[j] = the read whose line is the j-th."""
+        if return_order and not sorted_output:
+            raise ValueError("return_order needs sorted_output")
         args, keep, cap = _sam_inputs(reads, ids, results, cigars, read_group, clip)
         used = C.c_uint64()
         buf = np.empty(max(1, cap), dtype=np.uint8)
-        fn = lib().snapgpu_sam_format_gpu
-        rc = fn(self._h, *args, buf.ctypes.data, cap, C.byref(used))
+        order = np.zeros(max(1, reads.n), dtype=np.uint32)
+        fn, tail = lib().snapgpu_sam_format_gpu, []
+        if sorted_output:
+            fn, tail = lib().snapgpu_sam_format_gpu_sorted, [order.ctypes.data if return_order else None]
+        rc = fn(self._h, *args, buf.ctypes.data, cap, C.byref(used), *tail)
         if rc != 0 and used.value > cap:
             buf = np.empty(used.value, dtype=np.uint8)
-            rc = fn(self._h, *args, buf.ctypes.data, used.value, C.byref(used))
+            rc = fn(self._h, *args, buf.ctypes.data, used.value, C.byref(used), *tail)
         _check(rc, "sam_format_gpu")
-        return buf[:used.value].tobytes()
+        text = buf[:used.value].tobytes()
+        return (text, order[:reads.n]) if return_order else text
 
     def sam_ms(self):
         """(kernel ms, download ms) of the last device SAM call (snapgpu_sam_last_ms)."""
@@ -521,6 +530,13 @@ class BaseAligner:
         v = [C.c_double() for _ in range(3)]
         _check(lib().snapgpu_sam_pass_ms(self._h, *[C.byref(x) for x in v]), "sam_pass_ms")
         return tuple(x.value for x in v)
+
+    def sam_sort_ms(self):
+        """Kernel ms of the sort step of the last device SAM call (snapgpu_sam_sort_ms): 0 after an
+        unsorted call."""
+        v = C.c_double()
+        _check(lib().snapgpu_sam_sort_ms(self._h, C.byref(v)), "sam_sort_ms")
+        return v.value
 
     def upload(self, reads):
         return DeviceReads(self, reads)
@@ -686,9 +702,10 @@ class DeviceReads:
                                             c.nOps.ctypes.data, c.ops.ctypes.data), "cigar_download")
         return c
 
-    def run_sam(self, reads, ids=None, read_group="FASTQ"):
+    def run_sam(self, reads, ids=None, read_group="FASTQ", sorted_output=False):
         """SAM lines of the records and CIGARs run() + run_cigars() left in HBM, formatted on the
-        GPU (asynchronous).  reads: the batch this was uploaded from; ids: None for its own ids."""
+        GPU (asynchronous).  reads: the batch this was uploaded from; ids: None for its own ids;
+        sorted_output: the lines in coordinate order (`-so`), sam_order() then gives that order."""
         rg = None if read_group is None else read_group.encode()
         if ids is None:
             self._sam_keep = None
@@ -697,7 +714,15 @@ class DeviceReads:
             blob, offs, lens = _id_arrays(ids, reads.n)
             self._sam_keep = (blob, offs, lens)
             args = [blob, offs.ctypes.data, lens.ctypes.data]
-        _check(lib().snapgpu_sam_resident(self.aligner._h, self._h, reads._p, *args, rg), "sam_resident")
+        fn = lib().snapgpu_sam_resident_sorted if sorted_output else lib().snapgpu_sam_resident
+        _check(fn(self.aligner._h, self._h, reads._p, *args, rg), "sam_resident")
+
+    def sam_order(self):
+        """The output order of the last run_sam(sorted_output=True) -> uint32[n] (waits): entry j is
+        the read whose line is the j-th of sam()'s text."""
+        order = np.zeros(max(1, self.n), dtype=np.uint32)
+        _check(lib().snapgpu_sam_order_download(self.aligner._h, self._h, order.ctypes.data), "sam_order_download")
+        return order[:self.n]
 
     def sam(self, timing=None):
         """The text run_sam() wrote -> bytes (waits).  timing: a dict that receives "done", the
@@ -851,6 +876,18 @@ def sam_line_lengths(index, reads, ids, results, cigars, read_group="FASTQ", cli
     out = np.zeros(max(1, reads.n), dtype=np.uint32)
     _check(lib().snapgpu_sam_line_lengths(index._h, *args, out.ctypes.data), "sam_line_lengths")
     return out[:reads.n]
+
+
+def sam_sort_keys(index, results):
+    """The coordinate-sort key of every record (snapgpu_sam_sort_keys: the host side of the sorted
+    device formatter; needs no GPU) -> np.uint32 array.  np.argsort(keys, kind="stable") is the order
+    of the sorted device calls and of sam_sort_records."""
+    res = np.ascontiguousarray(results, dtype=RESULT_DTYPE)
+    n = len(res)
+    out = np.zeros(max(1, n), dtype=np.uint32)
+    src = res if n else np.zeros(1, dtype=RESULT_DTYPE)
+    _check(lib().snapgpu_sam_sort_keys(index._h, n, src.ctypes.data, out.ctypes.data), "sam_sort_keys")
+    return out[:n]
 
 
 def _sam_line_write(index, reads, ids, results, cigars, read_group="FASTQ", clip=None):

@@ -333,6 +333,15 @@ _PROTOS = [
                                          C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
     ("snapgpu_sam_last_ms", C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     ("snapgpu_sam_pass_ms", C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    ("snapgpu_sam_resident_sorted", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Reads), C.c_char_p, C.c_void_p,
+                                              C.c_void_p, C.c_char_p]),
+    ("snapgpu_sam_order_download", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("snapgpu_sam_format_gpu_sorted", C.c_int, [C.c_void_p, C.POINTER(Reads), C.c_char_p, C.c_void_p, C.c_void_p,
+                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p,
+                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
+                                                C.POINTER(C.c_uint64), C.c_void_p]),
+    ("snapgpu_sam_sort_keys", C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
+    ("snapgpu_sam_sort_ms", C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     ("snapgpu_sam_line_lengths", C.c_int, [C.c_void_p, C.POINTER(Reads), C.c_char_p, C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_void_p,
                                            C.c_void_p, C.c_void_p]),

@@ -15,10 +15,21 @@ The "ab" child alternates A16 and B `--reps` times after one warm-up of each; it
 D2H of the records and CIGAR rows that A needs and B does not, and snapgpu_copy_peak.  B's bytes
 must equal A's (SHA-256).  Medians and the spread go to --out, rewritten after every child.
 
+--sorted measures coordinate-sorted output (`-so`) instead, in one child that alternates two legs
+`--reps` times after one warm-up of each:
+
+  S      snapgpu_sam_resident_sorted + snapgpu_sam_download: wall time, kernel ms by pass and the
+         sort step's ms (snapgpu_sam_sort_ms);
+  B + H  the unsorted device path B as above, then snapgpu_sam_sort_records on its text (H, one host
+         thread by construction).
+
+S's bytes must equal B + H's (SHA-256).  No threshold: the report states S against B + H.
+
 Every child runs under its own time limit and the first one that fails, faults or times out ends
 the run: nothing is started on a GPU after a failure.
 
     python3 tools/sam_format_time.py --reps 5 --out profiles/r07/sam_format.json
+    python3 tools/sam_format_time.py --reps 5 --sorted --out profiles/r10/sam_sorted.json
 """
 import argparse
 import ctypes as C
@@ -75,9 +86,10 @@ def child(mode, reps, n_reads, genome_bases):
         assert rc == 0, snapgpu.last_error()
         return ms, hashlib.sha256(buf[:used.value]).hexdigest(), used.value
 
-    def device():
+    def device(sorted_output=False, keep=False):
+        fn = lib.snapgpu_sam_resident_sorted if sorted_output else lib.snapgpu_sam_resident
         t = time.perf_counter()
-        rc = lib.snapgpu_sam_resident(al._h, dev._h, reads._p, blob, offs.ctypes.data, lens.ctypes.data, b"FASTQ")
+        rc = fn(al._h, dev._h, reads._p, blob, offs.ctypes.data, lens.ctypes.data, b"FASTQ")
         assert rc == 0, snapgpu.last_error()
         lib.snapgpu_sam_download(al._h, dev._h, None, 0, C.byref(used))
         buf = np.empty(max(1, used.value), dtype=np.uint8)
@@ -86,7 +98,54 @@ def child(mode, reps, n_reads, genome_bases):
         dev.synchronize()
         ms = (time.perf_counter() - t) * 1e3
         k, d = al.sam_ms()
+        if keep:   # the text itself, for the host sorter
+            return ms, buf[:used.value], k, d, al.sam_pass_ms()
         return ms, hashlib.sha256(buf[:used.value]).hexdigest(), used.value, k, d, al.sam_pass_ms()
+
+    def host_sort(text):
+        out_buf = np.empty(max(1, len(text)), dtype=np.uint8)
+        t = time.perf_counter()
+        rc = lib.snapgpu_sam_sort_records(idx._h, text.ctypes.data_as(C.c_char_p), len(text),
+                                          out_buf.ctypes.data_as(C.c_char_p), len(text), C.byref(used))
+        ms = (time.perf_counter() - t) * 1e3
+        assert rc == 0 and used.value == len(text), snapgpu.last_error()
+        return ms, hashlib.sha256(out_buf[:len(text)]).hexdigest()
+
+    if mode == "sorted":
+        device(True)
+        host_sort(device(keep=True)[1])   # warm-up of both legs
+        S, B, H, sort_ms, kern = [], [], [], [], {"S": [], "B": []}
+        passes = {"S": [], "B": []}
+        digests = {"S": set(), "BH": set()}
+        for _ in range(reps):
+            ms, h, nbytes, k, d, ps = device(True)
+            S.append(ms)
+            sort_ms.append(al.sam_sort_ms())
+            kern["S"].append(k)
+            passes["S"].append(ps)
+            digests["S"].add(h)
+            ms, text, k, d, ps = device(keep=True)
+            assert len(text) == nbytes
+            B.append(ms)
+            kern["B"].append(k)
+            passes["B"].append(ps)
+            ms, h = host_sort(text)
+            H.append(ms)
+            digests["BH"].add(h)
+        bh = [b + h for b, h in zip(B, H)]
+        pass_stats = lambda v: {name: _stats([p[i] for p in v]) for i, name in enumerate(("length", "scan", "write"))}
+        out.update({
+            "S_wall_ms": _stats(S), "B_wall_ms": _stats(B), "H_host_sort_ms": _stats(H), "B_plus_H_ms": _stats(bh),
+            "S_sort_ms": _stats(sort_ms), "S_kernel_ms": _stats(kern["S"]), "B_kernel_ms": _stats(kern["B"]),
+            "S_pass_ms": pass_stats(passes["S"]), "B_pass_ms": pass_stats(passes["B"]),
+            "sorted_write_over_unsorted_write": round(statistics.median(p[2] for p in passes["S"]) /
+                                                      statistics.median(p[2] for p in passes["B"]), 3),
+            "text_bytes": nbytes, "sha256_S": sorted(digests["S"]), "sha256_B_plus_H": sorted(digests["BH"]),
+            "digests_equal": len(digests["S"]) == 1 and digests["S"] == digests["BH"],
+            "S_median_above_B_plus_H_median": statistics.median(S) > statistics.median(bh),
+        })
+        print("RESULT " + json.dumps(out), flush=True)
+        return
 
     host()   # warm-up
     a, b, digests = [], [], set()
@@ -131,8 +190,9 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--reads", type=int, default=C2["reads"])
     ap.add_argument("--genome-bases", type=int, default=C2["genome_bases"], help="a smaller genome for a quick check")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r07", "sam_format.json"))
-    ap.add_argument("--child", choices=("ab", "host"))
+    ap.add_argument("--out", help="default profiles/r07/sam_format.json, or profiles/r10/sam_sorted.json with --sorted")
+    ap.add_argument("--sorted", action="store_true", help="coordinate-sorted output: S against B + H (see above)")
+    ap.add_argument("--child", choices=("ab", "host", "sorted"))
     args = ap.parse_args()
     if args.reps < 3:
         ap.error("--reps must be at least 3")
@@ -140,7 +200,9 @@ def main():
         child(args.child, args.reps, args.reads, args.genome_bases)
         return 0
 
-    report = {"tool": "tools/sam_format_time.py", "reps": args.reps, "reads": args.reads, "genome_bases": args.genome_bases}
+    if not args.out:
+        args.out = os.path.join(ROOT, "profiles", *(("r10", "sam_sorted.json") if args.sorted else ("r07", "sam_format.json")))
+    report = {"tool": "tools/sam_format_time.py" + (" --sorted" if args.sorted else ""), "reps": args.reps, "reads": args.reads, "genome_bases": args.genome_bases}
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
 
     def save():
@@ -148,7 +210,8 @@ def main():
             json.dump(report, f, indent=1)
             f.write("\n")
 
-    for name, mode, threads in (("A16_and_B", "ab", 16), ("A2", "host", 2)):
+    legs = (("S_and_B_plus_H", "sorted", 16),) if args.sorted else (("A16_and_B", "ab", 16), ("A2", "host", 2))
+    for name, mode, threads in legs:
         cmd = [sys.executable, os.path.abspath(__file__), "--child", mode, "--reps", str(args.reps), "--reads",
                str(args.reads), "--genome-bases", str(args.genome_bases)]
         env = dict(os.environ, SNAPGPU_HOST_THREADS=str(threads))
@@ -169,6 +232,18 @@ def main():
         report[name] = json.loads(line[len("RESULT "):])
         save()
         print(f"[{name}] " + json.dumps(report[name]), flush=True)
+    if args.sorted:
+        r = report["S_and_B_plus_H"]
+        report["digests_equal"] = r["digests_equal"]
+        report["S_wall_median_ms"] = r["S_wall_ms"]["median"]
+        report["B_plus_H_median_ms"] = r["B_plus_H_ms"]["median"]
+        save()
+        print(f"S {r['S_wall_ms']['median']} ms (sort step {r['S_sort_ms']['median']} ms), B {r['B_wall_ms']['median']} ms + "
+              f"H {r['H_host_sort_ms']['median']} ms; digests equal: {r['digests_equal']}", flush=True)
+        if not r["digests_equal"]:
+            print("TEXT DIFFERS", flush=True)
+            return 2
+        return 0
     ab, a2 = report["A16_and_B"], report["A2"]
     report["digests_equal"] = ab["digests_equal"] and a2["digests_equal"] and ab["sha256"] == a2["sha256"]
     report["A16_median_ms"] = ab["A_ms"]["median"]
