@@ -588,6 +588,84 @@ int snapgpu_sam_line_lengths(const snapgpu_index_t *idx, const snapgpu_reads_t *
 int snapgpu_sam_header(const snapgpu_index_t *idx, int sorted, const char *commandLine, const char *version,
                        const char *rgLine, char *out, uint64_t cap, uint64_t *used);
 
+/* ------------------------------------------------------------ BAM records (reads without mate)
+ * One uncompressed BAM record per read, as BAMFormat::writeRead (Bam.cpp:596-790) writes it for a
+ * single-end genome alignment, appended in input order: the arguments of snapgpu_sam_format_clipped
+ * (NULL clip arrays: the batch's own clip state, or unclipped), the same limits (unclipped read <=
+ * 1024 bases, nOps <= SNAPGPU_CIGAR_MAX_OPS) and the same size contract as snapgpu_sam_format.
+ * Unlike the SAM line: QNAME is the whole id (not cut at the first space; a batch with an id longer
+ * than 254 bytes is refused with SNAPGPU_EINVAL -- the reference exits, Bam.cpp:723-726); SEQ and
+ * QUAL cover the whole unclipped read; the record's location decides CIGAR ops, bin and NM even for
+ * a NotFound record, while refID, pos, FLAG and MAPQ take NotFound as unmapped.
+ * NM carry (writeRead's editDistance is only assigned when it computes a CIGAR, Bam.cpp:644,
+ * 654-679, 780): nm[i] = editDistance[i] when record i gets CIGAR ops (location valid and
+ * editDistance[i] >= 0), else nm[i - 1], with nm[-1] = nmCarryIn; *nmCarryOut (may be NULL) = nm[n - 1],
+ * or nmCarryIn for n == 0 -- pass it to the next batch of the same output.
+ * Known gap: where LV fails at a valid genome substring the reference writes NM -1; editDistance -1
+ * does not tell that case from a read off the contig's end, so the rule above carries the previous
+ * value there as well. */
+int snapgpu_bam_format(const snapgpu_index_t *idx, const snapgpu_reads_t *reads, const char *ids,
+                       const uint64_t *idOffsets, const uint32_t *idLengths, const snapgpu_result_t *results,
+                       const int32_t *editDistance, const uint32_t *nOps, const uint32_t *ops, const char *readGroup,
+                       const uint32_t *frontClipped, const uint32_t *unclippedLength, int32_t nmCarryIn,
+                       int32_t *nmCarryOut, char *out, uint64_t cap, uint64_t *used);
+/* The exact byte size of every record above (block_size + 4): same inputs, same validation. */
+int snapgpu_bam_record_lengths(const snapgpu_index_t *idx, const snapgpu_reads_t *reads, const char *ids,
+                               const uint64_t *idOffsets, const uint32_t *idLengths, const snapgpu_result_t *results,
+                               const int32_t *editDistance, const uint32_t *nOps, const uint32_t *ops,
+                               const char *readGroup, const uint32_t *frontClipped, const uint32_t *unclippedLength,
+                               uint32_t *recordLengths);
+/* BAMFormat::getSortInfo (Bam.cpp:474-495) for a read without mate: the record's genome location
+ * (the offset of piece refID + pos) when it has a refID, else 0xffffffff.  Unlike the SAM key
+ * (snapgpu_sam_sort_keys) it goes by piece index, not by the first piece of that name: the two differ
+ * where two pieces share a name, or a name is empty or begins with '*'. */
+int snapgpu_bam_sort_keys(const snapgpu_index_t *idx, uint64_t n, const snapgpu_result_t *results, uint32_t *keys);
+/* BAMFormat::writeHeader (Bam.cpp:542-594): magic, the n bytes of SAM header text, one reference
+ * entry per genome piece (l_ref = piece span - 500).  Size contract as snapgpu_sam_header. */
+int snapgpu_bam_header(const snapgpu_index_t *idx, const char *samHeaderText, uint64_t n, char *out, uint64_t cap,
+                       uint64_t *used);
+/* BGZF, as the product paths' ".bam" output writes it: blocks of 0xff00 input bytes, each its own
+ * deflate stream in a gzip member with the BC extra field, then (eof != 0) the 28-byte EOF block.
+ * The blocks are compressed on the host thread pool; the bytes are the same for every thread count.
+ * Size contract as snapgpu_sam_format (n + n / 0xff00 * 128 + 256 bytes always suffice). */
+int snapgpu_bgzf_compress(const char *in, uint64_t n, int eof, char *out, uint64_t cap, uint64_t *used);
+
+/* The same records written on the GPU (bam_format.hip): a length pass (record sizes, each record's own
+ * NM or none, the sort key for sorted calls), a "last defined value" scan of the NM values over
+ * input order seeded with nmCarryIn, an exclusive scan of the sizes into 64-bit record starts, and a
+ * write pass that stages each workgroup's byte range in LDS.  Byte-identical to snapgpu_bam_format.
+ * There is no fallback to it: a failure is an error.  After the write pass a device check counts the
+ * records whose block_size is not what the scan gave them: always 0, else the download fails with
+ * SNAPGPU_EDEVICE.
+ * snapgpu_bam_resident: arguments, checks, asynchrony and ordering against the next
+ * snapgpu_align_resident as snapgpu_sam_resident; also SNAPGPU_EINVAL for an id longer than 254 bytes.
+ * The BAM state of a resident batch is its own: SAM and BAM calls on one batch do not disturb each other.
+ * _sorted: the records in the stable order of snapgpu_bam_sort_keys.  The NM carry still runs over
+ * input order (the reference's writer runs before its sort filter). */
+int snapgpu_bam_resident(snapgpu_aligner_t *a, snapgpu_device_reads_t *d, const snapgpu_reads_t *reads,
+                         const char *ids, const uint64_t *idOffsets, const uint32_t *idLengths,
+                         const char *readGroup, int32_t nmCarryIn);
+int snapgpu_bam_resident_sorted(snapgpu_aligner_t *a, snapgpu_device_reads_t *d, const snapgpu_reads_t *reads,
+                                const char *ids, const uint64_t *idOffsets, const uint32_t *idLengths,
+                                const char *readGroup, int32_t nmCarryIn);
+/* Waits; size contract as snapgpu_sam_download.  *nmCarryOut (may be NULL) = the NM of the last
+ * record in input order (nmCarryIn for an empty batch). */
+int snapgpu_bam_download(snapgpu_aligner_t *a, snapgpu_device_reads_t *d, char *out, uint64_t cap, uint64_t *used,
+                         int32_t *nmCarryOut);
+/* Waits; order[j] = the read whose record is the j-th of the sorted output.  SNAPGPU_EINVAL when the
+ * batch's last BAM call was not snapgpu_bam_resident_sorted, or there was none. */
+int snapgpu_bam_order_download(snapgpu_aligner_t *a, snapgpu_device_reads_t *d, uint32_t *order);
+/* Batch form: the arguments of snapgpu_bam_format with the aligner in place of the index, then
+ * sorted (0 / 1) and order (n entries written by a sorted call, or NULL). */
+int snapgpu_bam_format_gpu(snapgpu_aligner_t *a, const snapgpu_reads_t *reads, const char *ids,
+                           const uint64_t *idOffsets, const uint32_t *idLengths, const snapgpu_result_t *results,
+                           const int32_t *editDistance, const uint32_t *nOps, const uint32_t *ops,
+                           const char *readGroup, const uint32_t *frontClipped, const uint32_t *unclippedLength,
+                           int32_t nmCarryIn, int32_t *nmCarryOut, char *out, uint64_t cap, uint64_t *used, int sorted,
+                           uint32_t *order);
+/* kernel time (HIP events over all passes) and download time of the last device BAM call */
+int snapgpu_bam_last_ms(snapgpu_aligner_t *a, double *kernelMs, double *downloadMs);
+
 /* --------------------------------------------- RNA annotation (GTF) */
 /* GTFReader (SNAPLib/GTFReader.cpp): exon lines of a GTF/GFF3 file -> transcripts, each an
  * exon list sorted by start with an intron feature between consecutive exons (Load :1245,

@@ -20,6 +20,7 @@
 #include "cigar.h"
 #include "internal.h"
 #include "large_copy.h"
+#include "bam_format.h"
 #include "sam_format.h"
 
 using namespace sgk;
@@ -1170,6 +1171,13 @@ struct SamState {
     double downloadMs = 0;
 };
 
+// Device BAM encoder (bam_format.hip) state: the SAM formatter's buffers (its own copies: a batch's
+// SAM and BAM calls do not disturb each other) and the NM carry's.
+struct BamState : SamState {
+    Buf nm, nmTiles;
+    int32_t carryIn = 0;
+};
+
 struct snapgpu_device_reads {
     snapgpu_aligner_t *owner = nullptr;
     char *dBases = nullptr, *dQuals = nullptr;
@@ -1186,6 +1194,7 @@ struct snapgpu_device_reads {
     uint64_t bytes = 0;       // bases / quals bytes uploaded: the largest clipped end
     uint64_t extentHash = 0;  // of the offsets and lengths uploaded (snapgpu_sam_resident checks its batch)
     SamState sam;
+    BamState bam;
 };
 
 struct snapgpu_aligner {
@@ -1274,6 +1283,8 @@ struct snapgpu_aligner {
     // and the pinned staging of the text download (two chunks in flight)
     SamState samBatch;
     SamState *samLast = nullptr;
+    BamState bamBatch;
+    BamState *bamLast = nullptr;   // snapgpu_bam_last_ms
     void *samPin[2] = {};
     hipEvent_t samPinDone[2] = {};
     hipStream_t stream() const { return lane[0].stream; }
@@ -1606,6 +1617,15 @@ void samStateFree(const snapgpu_aligner_t *a, SamState &S) {
             if (e) { hipEventDestroy(e); e = nullptr; }
 }
 
+void bamStateFree(const snapgpu_aligner_t *a, BamState &S) {
+    for (auto *b : {&S.nm, &S.nmTiles}) {
+        devFree(a, b->p);
+        b->p = nullptr;
+        b->cap = 0;
+    }
+    samStateFree(a, S);
+}
+
 // Wait for an event, honouring SNAPGPU_TIMEOUT_S: on expiry the aligner is marked failed.
 int waitEvent(snapgpu_aligner_t *a, hipEvent_t ev) {
     if (a->failed) { snapgpu::setError("aligner failed earlier (device timeout): no further work accepted"); return SNAPGPU_EDEVICE; }
@@ -1848,6 +1868,7 @@ void snapgpu_aligner_free(snapgpu_aligner_t *a) {
     hostPinnedFree(a->cgPin);
     hostPinnedFree(a->cgPinOut);
     samStateFree(a, a->samBatch);
+    bamStateFree(a, a->bamBatch);
     for (int k = 0; k < 2; k++) {
         if (!a->failed) hostPinnedFree(a->samPin[k]);
         if (a->samPinDone[k]) hipEventDestroy(a->samPinDone[k]);
@@ -2063,6 +2084,8 @@ void snapgpu_device_reads_free(snapgpu_device_reads_t *d) {
     devFree(a, d->dCigEd); devFree(a, d->dCigN); devFree(a, d->dCigOps);
     if (a && a->samLast == &d->sam) const_cast<snapgpu_aligner_t *>(a)->samLast = nullptr;
     samStateFree(a, d->sam);
+    if (a && a->bamLast == &d->bam) const_cast<snapgpu_aligner_t *>(a)->bamLast = nullptr;
+    bamStateFree(a, d->bam);
     delete d;
 }
 
@@ -3370,8 +3393,37 @@ static int samLaunch(snapgpu_aligner_t *a, SamState &S, const samline::Args &A, 
     return SNAPGPU_OK;
 }
 
-// Wait for S's kernels, check them, and copy the text to the caller's (pageable) buffer in chunks
-// through two pinned staging buffers: chunk k + 1 crosses PCIe while host threads copy chunk k out.
+// `total` bytes at device address `text` to the caller's (pageable) buffer, in chunks through two
+// pinned staging buffers: chunk k + 1 crosses PCIe while host threads copy chunk k out.
+static int textDownload(snapgpu_aligner_t *a, const char *text, uint64_t total, char *out) {
+    for (int k = 0; k < 2; k++) {
+        if (!a->samPin[k]) HIPCHK(hipHostMalloc(&a->samPin[k], kSamChunk, hipHostMallocDefault));
+        if (!a->samPinDone[k]) HIPCHK(hipEventCreateWithFlags(&a->samPinDone[k], hipEventDisableTiming));
+    }
+    const uint64_t nChunks = (total + kSamChunk - 1) / kSamChunk;
+    auto issue = [&](uint64_t k) -> hipError_t {
+        const uint64_t b = k * kSamChunk, m = std::min(kSamChunk, total - b);
+        hipError_t e = hipMemcpyAsync(a->samPin[k & 1], text + b, m, hipMemcpyDeviceToHost, a->sideStream);
+        return e != hipSuccess ? e : hipEventRecord(a->samPinDone[k & 1], a->sideStream);
+    };
+    const unsigned nt = snapgpu::hostThreads(16);
+    HIPCHK(issue(0));
+    for (uint64_t k = 0; k < nChunks; k++) {
+        if (k + 1 < nChunks) HIPCHK(issue(k + 1));
+        if (int rc = waitEvent(a, a->samPinDone[k & 1])) return rc;
+        const uint64_t b = k * kSamChunk, m = std::min(kSamChunk, total - b);
+        const char *src = (const char *)a->samPin[k & 1];
+        const unsigned t = m < (1u << 20) ? 1u : nt;
+        std::vector<std::thread> th;
+        for (unsigned j = 1; j < t; j++)
+            th.emplace_back([=] { memcpy(out + b + m * j / t, src + m * j / t, m * (j + 1) / t - m * j / t); });
+        memcpy(out + b, src, m / t);
+        for (auto &x : th) x.join();
+    }
+    return SNAPGPU_OK;
+}
+
+// Wait for S's kernels, check them, and copy the text to the caller's buffer (textDownload).
 static int samDownload(snapgpu_aligner_t *a, SamState &S, char *out, uint64_t cap, uint64_t *used) {
     *used = 0;
     S.downloadMs = 0;
@@ -3391,41 +3443,85 @@ static int samDownload(snapgpu_aligner_t *a, SamState &S, char *out, uint64_t ca
     }
     *used = total;
     if (total > cap || !out) { snapgpu::setError("sam_download: output buffer too small"); return SNAPGPU_EINVAL; }
-    for (int k = 0; k < 2; k++) {
-        if (!a->samPin[k]) HIPCHK(hipHostMalloc(&a->samPin[k], kSamChunk, hipHostMallocDefault));
-        if (!a->samPinDone[k]) HIPCHK(hipEventCreateWithFlags(&a->samPinDone[k], hipEventDisableTiming));
-    }
-    const uint64_t nChunks = (total + kSamChunk - 1) / kSamChunk;
-    auto issue = [&](uint64_t k) -> hipError_t {
-        const uint64_t b = k * kSamChunk, m = std::min(kSamChunk, total - b);
-        hipError_t e = hipMemcpyAsync(a->samPin[k & 1], (const char *)S.text.p + b, m, hipMemcpyDeviceToHost, a->sideStream);
-        return e != hipSuccess ? e : hipEventRecord(a->samPinDone[k & 1], a->sideStream);
-    };
-    const unsigned nt = snapgpu::hostThreads(16);
-    HIPCHK(issue(0));
-    for (uint64_t k = 0; k < nChunks; k++) {
-        if (k + 1 < nChunks) HIPCHK(issue(k + 1));
-        if (int rc = waitEvent(a, a->samPinDone[k & 1])) return rc;
-        const uint64_t b = k * kSamChunk, m = std::min(kSamChunk, total - b);
-        const char *src = (const char *)a->samPin[k & 1];
-        const unsigned t = m < (1u << 20) ? 1u : nt;
-        std::vector<std::thread> th;
-        for (unsigned j = 1; j < t; j++)
-            th.emplace_back([=] { memcpy(out + b + m * j / t, src + m * j / t, m * (j + 1) / t - m * j / t); });
-        memcpy(out + b, src, m / t);
-        for (auto &x : th) x.join();
-    }
+    if (int rc = textDownload(a, (const char *)S.text.p, total, out)) return rc;
     S.downloadMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return SNAPGPU_OK;
 }
 
-// snapgpu_sam_resident and snapgpu_sam_resident_sorted
+// The device BAM encoder's passes over n records on the side stream, into S's buffers (samLaunch's
+// counterpart; S.textBound is samPrepare's bound on the SAM text, which exceeds the records' bytes:
+// per record the id, 1.5 bytes per base and at most 36 + 1 + 4 * 66 + 4 + 15 more, plus the read group).
+static int bamLaunch(snapgpu_aligner_t *a, BamState &S, const samline::Args &A, uint64_t n, bool sorted, int32_t nmCarryIn) {
+    for (auto &e : S.ev)
+        if (!e) HIPCHK(hipEventCreate(&e));
+    S.n = n;
+    S.ran = true;
+    S.sorted = sorted;
+    S.carryIn = nmCarryIn;
+    a->bamLast = &S;
+    if (n == 0) return SNAPGPU_OK;
+    if (n > 0xffffffffull) { snapgpu::setError("batch too large"); return SNAPGPU_EINVAL; }
+    HIPCHK(samGrow(a, S.len, n * 4));
+    HIPCHK(samGrow(a, S.nm, n * 4));
+    HIPCHK(samGrow(a, S.nmTiles, samgpu::scanTiles(n) * 4));
+    HIPCHK(samGrow(a, S.start, (n + 1) * 8));
+    HIPCHK(samGrow(a, S.sums, samgpu::scanTiles(n) * 8));
+    HIPCHK(samGrow(a, S.bad, 16));
+    HIPCHK(samGrow(a, S.text, S.textBound + 16));
+    const bamgpu::Buffers B{(uint32_t *)S.len.p, (int32_t *)S.nm.p, (int32_t *)S.nmTiles.p, (uint64_t *)S.start.p,
+                            (uint64_t *)S.sums.p, (char *)S.text.p, S.textBound, (uint32_t *)S.bad.p};
+    samgpu::SortBuffers SB{};
+    if (sorted) {
+        HIPCHK(samgpu::sortTempBytes(n, a->sideStream, &SB.tempBytes));
+        for (SamState::Buf *b : {&S.key, &S.keySorted, &S.iota, &S.order, &S.slotLen}) HIPCHK(samGrow(a, *b, n * 4));
+        HIPCHK(samGrow(a, S.sortTemp, SB.tempBytes));
+        SB.key = (uint32_t *)S.key.p; SB.keySorted = (uint32_t *)S.keySorted.p;
+        SB.iota = (uint32_t *)S.iota.p; SB.order = (uint32_t *)S.order.p;
+        SB.slotLen = (uint32_t *)S.slotLen.p;
+        SB.temp = S.sortTemp.p;
+    }
+    HIPCHK(hipEventRecord(S.ev[0], a->sideStream));
+    HIPCHK(bamgpu::launch(A, n, nmCarryIn, B, a->sideStream, sorted ? &SB : nullptr));
+    HIPCHK(hipEventRecord(S.ev[1], a->sideStream));
+    return SNAPGPU_OK;
+}
+
+// Wait for S's kernels, check them, and copy the records and the carry-out to the caller.
+static int bamDownload(snapgpu_aligner_t *a, BamState &S, char *out, uint64_t cap, uint64_t *used, int32_t *nmCarryOut) {
+    *used = 0;
+    S.downloadMs = 0;
+    if (nmCarryOut) *nmCarryOut = S.carryIn;
+    if (S.n == 0) return SNAPGPU_OK;
+    if (int rc = waitEvent(a, S.ev[1])) return rc;
+    const auto t0 = std::chrono::steady_clock::now();
+    uint64_t total = 0;
+    uint32_t bad = 0;
+    HIPCHK(hipMemcpy(&total, (const uint64_t *)S.start.p + S.n, 8, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&bad, S.bad.p, 4, hipMemcpyDeviceToHost));
+    if (bad || total > S.textBound) {
+        char msg[160];
+        snprintf(msg, sizeof msg, "bam: %u of %llu records do not carry the size the scan gave them (output %llu bytes, bound %llu)",
+                 bad, (unsigned long long)S.n, (unsigned long long)total, (unsigned long long)S.textBound);
+        snapgpu::setError(msg);
+        return SNAPGPU_EDEVICE;
+    }
+    if (nmCarryOut) HIPCHK(hipMemcpy(nmCarryOut, (const int32_t *)S.nm.p + S.n - 1, 4, hipMemcpyDeviceToHost));
+    *used = total;
+    if (total > cap || !out) { snapgpu::setError("bam_download: output buffer too small"); return SNAPGPU_EINVAL; }
+    if (int rc = textDownload(a, (const char *)S.text.p, total, out)) return rc;
+    S.downloadMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return SNAPGPU_OK;
+}
+
+// snapgpu_sam_resident and snapgpu_sam_resident_sorted; bam: snapgpu_bam_resident and
+// snapgpu_bam_resident_sorted, the same checks and ordering over the batch's BAM state
 static int samResident(snapgpu_aligner_t *a, snapgpu_device_reads_t *d, const snapgpu_reads_t *reads,
                        const char *ids, const uint64_t *idOffsets, const uint32_t *idLengths,
-                       const char *readGroup, bool sorted) {
-    if (!a || !d || !reads) { snapgpu::setError("sam_resident: null argument"); return SNAPGPU_EINVAL; }
+                       const char *readGroup, bool sorted, bool bam = false, int32_t nmCarryIn = 0) {
+    const std::string who = bam ? "bam_resident" : "sam_resident";
+    if (!a || !d || !reads) { snapgpu::setError(who + ": null argument"); return SNAPGPU_EINVAL; }
     if (a->failed) { snapgpu::setError("aligner failed earlier (device timeout)"); return SNAPGPU_EDEVICE; }
-    if (d->owner != a) { snapgpu::setError("sam_resident: the resident batch belongs to another aligner"); return SNAPGPU_EINVAL; }
+    if (d->owner != a) { snapgpu::setError(who + ": the resident batch belongs to another aligner"); return SNAPGPU_EINVAL; }
     uint64_t bytes = 0, hash = 0;
     if (reads->n == d->n)
         for (uint64_t i = 0; i < reads->n; i++) {
@@ -3433,23 +3529,25 @@ static int samResident(snapgpu_aligner_t *a, snapgpu_device_reads_t *d, const sn
             hash = extentMix(hash, reads->offsets[i], reads->lengths[i]);
         }
     if (reads->n != d->n || bytes != d->bytes || hash != d->extentHash) {
-        snapgpu::setError("sam_resident: the reads batch does not match the resident batch (n, offsets or lengths differ)");
+        snapgpu::setError(who + ": the reads batch does not match the resident batch (n, offsets or lengths differ)");
         return SNAPGPU_EINVAL;
     }
     const bool ownIds = !ids;
     if (ownIds) { ids = reads->ids; idOffsets = reads->idOffsets; idLengths = reads->idLengths; }
     if (!ids || !idOffsets || !idLengths) {
-        snapgpu::setError("sam_resident: no read ids (pass ids, or use a batch that carries them)");
+        snapgpu::setError(who + ": no read ids (pass ids, or use a batch that carries them)");
         return SNAPGPU_EINVAL;
     }
+    if (bam)
+        if (int rc = snapgpu::bamCheckIds(idLengths, reads->n)) return rc;
     const uint32_t *front = nullptr, *unclipped = nullptr;
     if (int rc = snapgpu::samCheckClips(reads, nullptr, &front, &unclipped)) return rc;
     if (!d->dCigEd) {
-        snapgpu::setError("sam_resident: no snapgpu_cigar_resident before snapgpu_sam_resident");
+        snapgpu::setError(who + ": no snapgpu_cigar_resident before snapgpu_" + who);
         return SNAPGPU_EINVAL;
     }
     HIPCHK(hipSetDevice(a->device));
-    SamState &S = d->sam;
+    SamState &S = bam ? d->bam : d->sam;
     hipStream_t st = a->sideStream;
     // snapgpu_reads_upload copied bases and qualities up to the largest clipped end: where the
     // unclipped extents (SEQ / QUAL) pass it, the formatter reads a copy that holds them all
@@ -3500,8 +3598,8 @@ static int samResident(snapgpu_aligner_t *a, snapgpu_device_reads_t *d, const sn
         HIPCHK(hipEventRecord(L.done, L.stream));
         HIPCHK(hipStreamWaitEvent(st, L.done, 0));
     }
-    if (int rc = samLaunch(a, S, A, reads->n, sorted)) return rc;
-    // the next pass set over these reads rewrites the records: it waits for the SAM kernels
+    if (int rc = bam ? bamLaunch(a, d->bam, A, reads->n, sorted, nmCarryIn) : samLaunch(a, S, A, reads->n, sorted)) return rc;
+    // the next pass set over these reads rewrites the records: it waits for the SAM / BAM kernels
     HIPCHK(hipEventRecord(a->residentSideDone, st));
     a->residentSidePending = true;
     return SNAPGPU_OK;
@@ -3552,15 +3650,18 @@ static int samFormatBatch(snapgpu_aligner_t *a, const snapgpu_reads_t *reads, co
                           const uint64_t *idOffsets, const uint32_t *idLengths, const snapgpu_result_t *results,
                           const int32_t *editDistance, const uint32_t *nOps, const uint32_t *ops,
                           const char *readGroup, const uint32_t *frontClipped, const uint32_t *unclippedLength,
-                          char *out, uint64_t cap, uint64_t *used, bool sorted, uint32_t *order) {
+                          char *out, uint64_t cap, uint64_t *used, bool sorted, uint32_t *order, bool bam = false,
+                          int32_t nmCarryIn = 0, int32_t *nmCarryOut = nullptr) {
     if (!a || !reads || !ids || !idOffsets || !idLengths || !results || !editDistance || !nOps || !ops || !used) {
-        snapgpu::setError("sam_format: null argument");
+        snapgpu::setError(bam ? "bam_format: null argument" : "sam_format: null argument");
         return SNAPGPU_EINVAL;
     }
     if (a->failed) { snapgpu::setError("aligner failed earlier (device timeout)"); return SNAPGPU_EDEVICE; }
     if (int rc = snapgpu::samCheckClips(reads, nOps, &frontClipped, &unclippedLength)) return rc;
+    if (bam)
+        if (int rc = snapgpu::bamCheckIds(idLengths, reads->n)) return rc;
     HIPCHK(hipSetDevice(a->device));
-    SamState &S = a->samBatch;
+    SamState &S = bam ? a->bamBatch : a->samBatch;
     hipStream_t st = a->sideStream;
     const uint64_t n = reads->n;
     if (S.ran && S.ev[1]) HIPCHK(hipEventSynchronize(S.ev[1]));
@@ -3590,8 +3691,8 @@ static int samFormatBatch(snapgpu_aligner_t *a, const snapgpu_reads_t *reads, co
     H.ids = ids; H.idOffsets = idOffsets; H.idLengths = idLengths;
     H.front = frontClipped; H.unclipped = unclippedLength; H.rg = readGroup;
     if (int rc = samPrepare(a, S, H, false, A)) return rc;
-    if (int rc = samLaunch(a, S, A, n, sorted)) return rc;
-    if (int rc = samDownload(a, S, out, cap, used)) return rc;
+    if (int rc = bam ? bamLaunch(a, a->bamBatch, A, n, sorted, nmCarryIn) : samLaunch(a, S, A, n, sorted)) return rc;
+    if (int rc = bam ? bamDownload(a, a->bamBatch, out, cap, used, nmCarryOut) : samDownload(a, S, out, cap, used)) return rc;
     return sorted && order ? samOrderDownload(a, S, order) : SNAPGPU_OK;
 }
 
@@ -3611,6 +3712,65 @@ int snapgpu_sam_format_gpu_sorted(snapgpu_aligner_t *a, const snapgpu_reads_t *r
                                   char *out, uint64_t cap, uint64_t *used, uint32_t *order) {
     return samFormatBatch(a, reads, ids, idOffsets, idLengths, results, editDistance, nOps, ops, readGroup, frontClipped,
                           unclippedLength, out, cap, used, true, order);
+}
+
+int snapgpu_bam_resident(snapgpu_aligner_t *a, snapgpu_device_reads_t *d, const snapgpu_reads_t *reads,
+                         const char *ids, const uint64_t *idOffsets, const uint32_t *idLengths,
+                         const char *readGroup, int32_t nmCarryIn) {
+    return samResident(a, d, reads, ids, idOffsets, idLengths, readGroup, false, true, nmCarryIn);
+}
+
+int snapgpu_bam_resident_sorted(snapgpu_aligner_t *a, snapgpu_device_reads_t *d, const snapgpu_reads_t *reads,
+                                const char *ids, const uint64_t *idOffsets, const uint32_t *idLengths,
+                                const char *readGroup, int32_t nmCarryIn) {
+    return samResident(a, d, reads, ids, idOffsets, idLengths, readGroup, true, true, nmCarryIn);
+}
+
+int snapgpu_bam_download(snapgpu_aligner_t *a, snapgpu_device_reads_t *d, char *out, uint64_t cap, uint64_t *used,
+                         int32_t *nmCarryOut) {
+    if (!a || !d || !used) { snapgpu::setError("bam_download: null argument"); return SNAPGPU_EINVAL; }
+    if (a->failed) { snapgpu::setError("aligner failed earlier (device timeout)"); return SNAPGPU_EDEVICE; }
+    if (!d->bam.ran) { snapgpu::setError("bam_download: no snapgpu_bam_resident before snapgpu_bam_download"); return SNAPGPU_EINVAL; }
+    HIPCHK(hipSetDevice(a->device));
+    return bamDownload(a, d->bam, out, cap, used, nmCarryOut);
+}
+
+int snapgpu_bam_order_download(snapgpu_aligner_t *a, snapgpu_device_reads_t *d, uint32_t *order) {
+    if (!a || !d) { snapgpu::setError("bam_order_download: null argument"); return SNAPGPU_EINVAL; }
+    if (a->failed) { snapgpu::setError("aligner failed earlier (device timeout)"); return SNAPGPU_EDEVICE; }
+    if (!d->bam.ran || !d->bam.sorted) {
+        snapgpu::setError("bam_order_download: the batch's last BAM call was not snapgpu_bam_resident_sorted (or there was none)");
+        return SNAPGPU_EINVAL;
+    }
+    if (!order && d->bam.n) { snapgpu::setError("bam_order_download: null argument"); return SNAPGPU_EINVAL; }
+    HIPCHK(hipSetDevice(a->device));
+    return samOrderDownload(a, d->bam, order);
+}
+
+int snapgpu_bam_format_gpu(snapgpu_aligner_t *a, const snapgpu_reads_t *reads, const char *ids,
+                           const uint64_t *idOffsets, const uint32_t *idLengths, const snapgpu_result_t *results,
+                           const int32_t *editDistance, const uint32_t *nOps, const uint32_t *ops,
+                           const char *readGroup, const uint32_t *frontClipped, const uint32_t *unclippedLength,
+                           int32_t nmCarryIn, int32_t *nmCarryOut, char *out, uint64_t cap, uint64_t *used, int sorted,
+                           uint32_t *order) {
+    return samFormatBatch(a, reads, ids, idOffsets, idLengths, results, editDistance, nOps, ops, readGroup, frontClipped,
+                          unclippedLength, out, cap, used, sorted != 0, order, true, nmCarryIn, nmCarryOut);
+}
+
+int snapgpu_bam_last_ms(snapgpu_aligner_t *a, double *kernelMs, double *downloadMs) {
+    if (!a || !kernelMs || !downloadMs) return SNAPGPU_EINVAL;
+    if (!a->bamLast) { snapgpu::setError("bam_last_ms: no device BAM call on this aligner"); return SNAPGPU_EINVAL; }
+    if (a->failed) { snapgpu::setError("aligner failed earlier (device timeout)"); return SNAPGPU_EDEVICE; }
+    HIPCHK(hipSetDevice(a->device));
+    BamState &S = *a->bamLast;
+    float f = 0;
+    if (S.n) {
+        HIPCHK(hipEventSynchronize(S.ev[1]));
+        HIPCHK(hipEventElapsedTime(&f, S.ev[0], S.ev[1]));
+    }
+    *kernelMs = f;
+    *downloadMs = S.downloadMs;
+    return SNAPGPU_OK;
 }
 
 int snapgpu_sam_last_ms(snapgpu_aligner_t *a, double *kernelMs, double *downloadMs) {

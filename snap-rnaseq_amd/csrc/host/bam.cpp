@@ -8,13 +8,20 @@
 // record carries no CIGAR, and its NM is the previous record's (writeRead's editDistance is only
 // set when a CIGAR is computed -- the caller passes that value in); bin = reg2bin of the record's
 // reference span, (-1, 0) for an unmapped read without mate.
+//
+// The public host encoder (snapgpu_bam_format, _record_lengths, _sort_keys, _header, snapgpu_bgzf_compress)
+// is at the end: records of reads without mate through bam_line.h, the code the device encoder
+// (bam_format.hip) compiles too.
 #include "internal.h"
+#include "bam_line.h"
 
 #include <zlib.h>
 
+#include <algorithm>
 #include <cstdio>
 #include <cstring>
 #include <string>
+#include <thread>
 
 namespace snapgpu {
 
@@ -228,38 +235,285 @@ std::string bamHeader(const Genome &g, const std::string &samText) {
 
 // BGZF: deflate blocks of at most 0xff00 input bytes, each a gzip member with the BC extra field,
 // then the empty EOF block.
+static const size_t kBgzfIn = 0xff00;
+static const unsigned char kBgzfEof[28] = {31, 139, 8, 4, 0, 0, 0, 0, 0, 255, 6, 0, 66, 67, 2, 0, 27, 0,
+                                           3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+static size_t bgzfBlockBound() { return compressBound(kBgzfIn) + 64; }
+
+// One block of m <= 0xff00 input bytes into out (bgzfBlockBound() bytes) -> its size, 0 on failure.
+static size_t bgzfBlock(const char *data, size_t m, unsigned char *out) {
+    z_stream z;
+    memset(&z, 0, sizeof(z));
+    if (deflateInit2(&z, Z_DEFAULT_COMPRESSION, Z_DEFLATED, -15, 8, Z_DEFAULT_STRATEGY) != Z_OK) return 0;
+    z.next_in = (Bytef *)data;
+    z.avail_in = (uInt)m;
+    z.next_out = out + 18;
+    z.avail_out = (uInt)(bgzfBlockBound() - 26);
+    const int r = deflate(&z, Z_FINISH);
+    const size_t clen = z.total_out;
+    deflateEnd(&z);
+    if (r != Z_STREAM_END) return 0;
+    const size_t bsize = 18 + clen + 8;
+    const unsigned char hdr[18] = {31, 139, 8, 4, 0, 0, 0, 0, 0, 255, 6, 0, 'B', 'C', 2, 0,
+                                   (unsigned char)((bsize - 1) & 0xff), (unsigned char)((bsize - 1) >> 8)};
+    memcpy(out, hdr, 18);
+    const uint32_t crc = (uint32_t)crc32(crc32(0L, Z_NULL, 0), (const Bytef *)data, (uInt)m);
+    memcpy(out + 18 + clen, &crc, 4);
+    const uint32_t isize = (uint32_t)m;
+    memcpy(out + 22 + clen, &isize, 4);
+    return bsize;
+}
+
 bool bgzfWrite(FILE *f, const char *data, size_t n, bool eof) {
-    static const size_t kIn = 0xff00;
-    std::vector<unsigned char> out(compressBound(kIn) + 64);
-    for (size_t at = 0; at < n; at += kIn) {
-        const size_t m = std::min(kIn, n - at);
-        z_stream z;
-        memset(&z, 0, sizeof(z));
-        if (deflateInit2(&z, Z_DEFAULT_COMPRESSION, Z_DEFLATED, -15, 8, Z_DEFAULT_STRATEGY) != Z_OK) return false;
-        z.next_in = (Bytef *)(data + at);
-        z.avail_in = (uInt)m;
-        z.next_out = out.data() + 18;
-        z.avail_out = (uInt)(out.size() - 26);
-        const int r = deflate(&z, Z_FINISH);
-        const size_t clen = z.total_out;
-        deflateEnd(&z);
-        if (r != Z_STREAM_END) return false;
-        const size_t bsize = 18 + clen + 8;
-        const unsigned char hdr[18] = {31, 139, 8, 4, 0, 0, 0, 0, 0, 255, 6, 0, 'B', 'C', 2, 0,
-                                       (unsigned char)((bsize - 1) & 0xff), (unsigned char)((bsize - 1) >> 8)};
-        memcpy(out.data(), hdr, 18);
-        const uint32_t crc = (uint32_t)crc32(crc32(0L, Z_NULL, 0), (const Bytef *)(data + at), (uInt)m);
-        memcpy(out.data() + 18 + clen, &crc, 4);
-        const uint32_t isize = (uint32_t)m;
-        memcpy(out.data() + 22 + clen, &isize, 4);
-        if (fwrite(out.data(), 1, bsize, f) != bsize) return false;
+    std::vector<unsigned char> out(bgzfBlockBound());
+    for (size_t at = 0; at < n; at += kBgzfIn) {
+        const size_t bsize = bgzfBlock(data + at, std::min(kBgzfIn, n - at), out.data());
+        if (!bsize || fwrite(out.data(), 1, bsize, f) != bsize) return false;
     }
-    if (eof) {
-        static const unsigned char kEof[28] = {31, 139, 8, 4, 0, 0, 0, 0, 0, 255, 6, 0, 66, 67, 2, 0, 27, 0,
-                                               3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-        if (fwrite(kEof, 1, 28, f) != 28) return false;
-    }
+    if (eof && fwrite(kBgzfEof, 1, 28, f) != 28) return false;
     return true;
 }
 
 }  // namespace snapgpu
+
+// ------------------------------------------------------------------ the public host encoder
+using namespace snapgpu;
+
+namespace {
+
+struct HostRecords {
+    samline::Args A;
+    std::vector<uint32_t> nameOff;
+    std::string names;
+};
+
+// The arguments of snapgpu_sam_format_clipped as bam_line.h takes them, checked as the SAM formatter
+// checks them, and every QNAME short enough for BAM.
+int hostRecordArgs(HostRecords &H, const snapgpu_index_t *idx, const snapgpu_reads_t *reads, const char *ids,
+                   const uint64_t *idOffsets, const uint32_t *idLengths, const snapgpu_result_t *results,
+                   const int32_t *editDistance, const uint32_t *nOps, const uint32_t *ops, const char *readGroup,
+                   const uint32_t *frontClipped, const uint32_t *unclippedLength) {
+    if (!idx || !reads || !ids || !idOffsets || !idLengths || !results || !editDistance || !nOps || !ops) {
+        setError("bam_format: null argument");
+        return SNAPGPU_EINVAL;
+    }
+    if (int rc = samCheckClips(reads, nOps, &frontClipped, &unclippedLength)) return rc;
+    if (int rc = bamCheckIds(idLengths, reads->n)) return rc;
+    const Genome &g = *idx->genome;
+    samPieceNames(g, H.nameOff, H.names);
+    H.A = samline::Args{reads->bases, reads->quals, reads->offsets, reads->lengths, frontClipped, unclippedLength,
+                        ids, idOffsets, idLengths, results, editDistance, nOps, ops, g.pieceOffsets.data(),
+                        H.nameOff.data(), H.names.data(), (int32_t)g.pieceOffsets.size(),
+                        readGroup ? (uint32_t)strlen(readGroup) : 0u, readGroup};
+    return SNAPGPU_OK;
+}
+
+// f(a, b) over the ranges of [0, n) that the host threads take (one thread below 2 * minPerThread items)
+template <class F>
+void parallelRanges(uint64_t n, uint64_t minPerThread, F f) {
+    unsigned nt = hostThreads(16);
+    if (n < minPerThread * 2) nt = 1;
+    nt = (unsigned)std::min<uint64_t>(nt, std::max<uint64_t>(1, n));
+    std::vector<std::thread> th;
+    for (unsigned t = 1; t < nt; t++) th.emplace_back([&, t] { f(n * t / nt, n * (t + 1) / nt); });
+    f(0, n / nt);
+    for (auto &x : th) x.join();
+}
+
+}  // namespace
+
+namespace snapgpu {
+
+int bamCheckIds(const uint32_t *idLengths, uint64_t n) {
+    for (uint64_t i = 0; i < n; i++)
+        if (idLengths[i] > bamline::kMaxQname) {
+            setError("bam_format: a read id is longer than 254 bytes (the BAM QNAME limit, Bam.cpp:723-726)");
+            return SNAPGPU_EINVAL;
+        }
+    return SNAPGPU_OK;
+}
+
+}  // namespace snapgpu
+
+extern "C" int snapgpu_bam_record_lengths(const snapgpu_index_t *idx, const snapgpu_reads_t *reads, const char *ids,
+                                          const uint64_t *idOffsets, const uint32_t *idLengths,
+                                          const snapgpu_result_t *results, const int32_t *editDistance,
+                                          const uint32_t *nOps, const uint32_t *ops, const char *readGroup,
+                                          const uint32_t *frontClipped, const uint32_t *unclippedLength,
+                                          uint32_t *recordLengths) {
+    HostRecords H;
+    if (int rc = hostRecordArgs(H, idx, reads, ids, idOffsets, idLengths, results, editDistance, nOps, ops, readGroup,
+                                frontClipped, unclippedLength))
+        return rc;
+    if (!recordLengths && reads->n) {
+        setError("bam_record_lengths: null argument");
+        return SNAPGPU_EINVAL;
+    }
+    const bamline::Serial g{nullptr};
+    for (uint64_t i = 0; i < reads->n; i++) recordLengths[i] = bamline::recordLength(H.A, bamline::fields(H.A, i, g));
+    return SNAPGPU_OK;
+}
+
+extern "C" int snapgpu_bam_format(const snapgpu_index_t *idx, const snapgpu_reads_t *reads, const char *ids,
+                                  const uint64_t *idOffsets, const uint32_t *idLengths, const snapgpu_result_t *results,
+                                  const int32_t *editDistance, const uint32_t *nOps, const uint32_t *ops,
+                                  const char *readGroup, const uint32_t *frontClipped, const uint32_t *unclippedLength,
+                                  int32_t nmCarryIn, int32_t *nmCarryOut, char *out, uint64_t cap, uint64_t *used) {
+    if (!used) {
+        setError("bam_format: null argument");
+        return SNAPGPU_EINVAL;
+    }
+    HostRecords H;
+    if (int rc = hostRecordArgs(H, idx, reads, ids, idOffsets, idLengths, results, editDistance, nOps, ops, readGroup,
+                                frontClipped, unclippedLength))
+        return rc;
+    const uint64_t n = reads->n;
+    // sizes and own NM values in parallel, starts and the NM carry on one thread, then every thread
+    // writes its records in place
+    std::vector<uint64_t> start(n + 1, 0);
+    std::vector<int32_t> nm(n);
+    const bamline::Serial none{nullptr};
+    parallelRanges(n, 4096, [&](uint64_t a, uint64_t b) {
+        for (uint64_t i = a; i < b; i++) {
+            const bamline::Fields F = bamline::fields(H.A, i, none);
+            start[i + 1] = bamline::recordLength(H.A, F);
+            nm[i] = F.nmOwn;
+        }
+    });
+    int32_t carry = nmCarryIn;
+    for (uint64_t i = 0; i < n; i++) {
+        start[i + 1] += start[i];
+        if (nm[i] == bamline::kNoNm) nm[i] = carry;
+        carry = nm[i];
+    }
+    if (nmCarryOut) *nmCarryOut = carry;
+    *used = start[n];
+    if (start[n] > cap || (!out && start[n])) {
+        setError("bam_format: output buffer too small");
+        return SNAPGPU_EINVAL;
+    }
+    const bamline::Serial g{out};
+    parallelRanges(n, 4096, [&](uint64_t a, uint64_t b) {
+        for (uint64_t i = a; i < b; i++) bamline::write(H.A, i, bamline::fields(H.A, i, g), nm[i], start[i], g);
+    });
+    return SNAPGPU_OK;
+}
+
+// The same records through bamAppendRecord, the product paths' encoder, on one host thread: the SamLine
+// is built as the SAM formatter builds it (formatOne, sam.cpp).  For tests that pin bam_line.h to it.
+extern "C" int snapgpu_internal_bam_append_records(const snapgpu_index_t *idx, const snapgpu_reads_t *reads,
+                                                   const char *ids, const uint64_t *idOffsets,
+                                                   const uint32_t *idLengths, const snapgpu_result_t *results,
+                                                   const int32_t *editDistance, const uint32_t *nOps,
+                                                   const uint32_t *ops, const char *readGroup,
+                                                   const uint32_t *frontClipped, const uint32_t *unclippedLength,
+                                                   int32_t nmCarryIn, int32_t *nmCarryOut, char *out, uint64_t cap,
+                                                   uint64_t *used) {
+    HostRecords H;
+    if (int rc = hostRecordArgs(H, idx, reads, ids, idOffsets, idLengths, results, editDistance, nOps, ops, readGroup,
+                                frontClipped, unclippedLength))
+        return rc;
+    std::string o;
+    int32_t nm = nmCarryIn;
+    for (uint64_t i = 0; i < reads->n; i++) {
+        SamLine L;
+        L.id = ids + idOffsets[i];
+        L.idLen = idLengths[i];
+        L.front = H.A.front ? H.A.front[i] : 0u;
+        L.clippedLen = reads->lengths[i];
+        L.fullLen = H.A.unclipped ? H.A.unclipped[i] : L.clippedLen;
+        L.bases = reads->bases + reads->offsets[i] - L.front;
+        L.quals = reads->quals + reads->offsets[i] - L.front;
+        L.result = results[i].result;
+        L.loc = results[i].location;
+        L.dir = results[i].direction;
+        L.mapq = results[i].mapq;
+        L.ed = editDistance[i];
+        L.ops = ops + i * SNAPGPU_CIGAR_MAX_OPS;
+        L.nOps = nOps[i];
+        L.rg = readGroup;
+        if (L.loc != kInvalidLocation && L.ed >= 0) nm = L.ed;
+        if (!bamAppendRecord(o, *idx->genome, L, nm)) {
+            setError("bam_append_records: record not written");
+            return SNAPGPU_EINVAL;
+        }
+    }
+    if (nmCarryOut) *nmCarryOut = nm;
+    *used = o.size();
+    if (o.size() > cap || !out) {
+        setError("bam_append_records: output buffer too small");
+        return SNAPGPU_EINVAL;
+    }
+    memcpy(out, o.data(), o.size());
+    return SNAPGPU_OK;
+}
+
+extern "C" int snapgpu_bam_sort_keys(const snapgpu_index_t *idx, uint64_t n, const snapgpu_result_t *results,
+                                     uint32_t *keys) {
+    if (!idx || !idx->genome || ((!results || !keys) && n)) {
+        setError("bam_sort_keys: null argument");
+        return SNAPGPU_EINVAL;
+    }
+    const Genome &g = *idx->genome;
+    samline::Args A{};
+    A.res = results;
+    A.pieceOffsets = g.pieceOffsets.data();
+    A.nPieces = (int32_t)g.pieceOffsets.size();
+    for (uint64_t i = 0; i < n; i++) {
+        bamline::Fields F;
+        bamline::locate(A, i, F);
+        keys[i] = bamline::sortKey(A, F);
+    }
+    return SNAPGPU_OK;
+}
+
+extern "C" int snapgpu_bam_header(const snapgpu_index_t *idx, const char *samHeaderText, uint64_t n, char *out,
+                                  uint64_t cap, uint64_t *used) {
+    if (!idx || !idx->genome || (!samHeaderText && n) || !used) {
+        setError("bam_header: null argument");
+        return SNAPGPU_EINVAL;
+    }
+    const std::string o = bamHeader(*idx->genome, std::string(samHeaderText ? samHeaderText : "", n));
+    *used = o.size();
+    if (o.size() > cap || !out) {
+        setError("bam_header: output buffer too small");
+        return SNAPGPU_EINVAL;
+    }
+    memcpy(out, o.data(), o.size());
+    return SNAPGPU_OK;
+}
+
+extern "C" int snapgpu_bgzf_compress(const char *in, uint64_t n, int eof, char *out, uint64_t cap, uint64_t *used) {
+    if ((!in && n) || !used) {
+        setError("bgzf_compress: null argument");
+        return SNAPGPU_EINVAL;
+    }
+    // every block is its own deflate stream: blocks are compressed on the host threads, each into
+    // its own slot, and concatenated in order -- the bytes do not depend on the thread count
+    const uint64_t nBlocks = (n + kBgzfIn - 1) / kBgzfIn;
+    const size_t slot = bgzfBlockBound();
+    std::vector<unsigned char> slots(nBlocks * slot);
+    std::vector<uint64_t> at(nBlocks + 1, 0);
+    parallelRanges(nBlocks, 2, [&](uint64_t a, uint64_t b) {
+        for (uint64_t k = a; k < b; k++)
+            at[k + 1] = bgzfBlock(in + k * kBgzfIn, (size_t)std::min<uint64_t>(kBgzfIn, n - k * kBgzfIn), slots.data() + k * slot);
+    });
+    for (uint64_t k = 0; k < nBlocks; k++) {
+        if (!at[k + 1]) {
+            setError("bgzf_compress: deflate failed");
+            return SNAPGPU_EIO;
+        }
+        at[k + 1] += at[k];
+    }
+    const uint64_t total = at[nBlocks] + (eof ? 28 : 0);
+    *used = total;
+    if (total > cap || (!out && total)) {
+        setError("bgzf_compress: output buffer too small");
+        return SNAPGPU_EINVAL;
+    }
+    parallelRanges(nBlocks, 2, [&](uint64_t a, uint64_t b) {
+        for (uint64_t k = a; k < b; k++) memcpy(out + at[k], slots.data() + k * slot, at[k + 1] - at[k]);
+    });
+    if (eof) memcpy(out + at[nBlocks], kBgzfEof, 28);
+    return SNAPGPU_OK;
+}

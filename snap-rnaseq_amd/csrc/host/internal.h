@@ -157,6 +157,8 @@ void samSortBases(const Genome &g, std::vector<uint32_t> &base, std::vector<uint
 bool bamAppendRecord(std::string &o, const Genome &g, const SamLine &L, int32_t nm);
 std::string bamHeader(const Genome &g, const std::string &samText);
 bool bgzfWrite(FILE *f, const char *data, size_t n, bool eof);
+// the public encoder's id check (host and device forms): SNAPGPU_EINVAL for an id past the QNAME limit
+int bamCheckIds(const uint32_t *idLengths, uint64_t n);
 
 // One pair's GTFReader::IncrementReadCount (pair form) arguments (gtf.cpp: gtfCountPairs).
 struct GtfPairQuery {

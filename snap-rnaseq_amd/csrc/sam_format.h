@@ -37,6 +37,47 @@ struct SortBuffers {
 
 inline uint64_t scanTiles(uint64_t n) { return (n + kScanTile - 1) / kScanTile; }
 
+// A 64-lane wave as sam_line.h's group: bytes go to the LDS window [w0, w1) of the output.
+struct Wave {
+    char *lds;
+    uint64_t w0, w1;
+    uint32_t lane;
+    template <class P>
+    __device__ uint32_t firstOf(uint32_t n, P p) const {
+        for (uint32_t base = 0; base < n; base += 64) {
+            const uint32_t k = base + lane;
+            const bool hit = k < n && p(k);
+            const unsigned long long m = __ballot(hit);
+            if (m) return base + (uint32_t)__ffsll(m) - 1;
+        }
+        return n;
+    }
+    template <class F>
+    __device__ uint32_t sum(uint32_t n, F f) const {
+        uint32_t s = 0;
+        for (uint32_t k = lane; k < n; k += 64) s += f(k);
+        for (int o = 32; o; o >>= 1) s += __shfl_xor(s, o);
+        return s;
+    }
+    template <class F>
+    __device__ void copy(uint64_t at, uint32_t n, F f) const {
+        if (at + n <= w0 || at >= w1) return;
+        for (uint32_t k = lane; k < n; k += 64) put(at + k, f(k));
+    }
+    __device__ void put(uint64_t at, char c) const {
+        if (at >= w0 && at < w1) lds[at - w0] = c;
+    }
+    __device__ bool lead() const { return lane == 0; }
+};
+
+// The pieces of launch() that the BAM encoder (bam_format.hip) runs as well, queued on st.
+// sortStep: order fill, the stable radix sort of (S.key, record index) into S.order, and the gather
+// S.slotLen[j] = len[S.order[j]]; S.keys is not read (the caller's length pass stored S.key).
+// scanStarts: the exclusive 64-bit scan of n lengths into start[0 .. n], start[n] = their sum
+// (sums: scanTiles(n) entries of scratch).
+hipError_t sortStep(const SortBuffers &S, const uint32_t *len, uint64_t n, hipStream_t st);
+void scanStarts(const uint32_t *len, uint64_t n, uint64_t *sums, uint64_t *start, hipStream_t st);
+
 // Bytes of temporary storage the radix sort of n (key, record) pairs on st asks for.  A size query
 // on the host: nothing is launched and nothing is waited for.
 hipError_t sortTempBytes(uint64_t n, hipStream_t st, size_t *bytes);

@@ -26,39 +26,6 @@ using samline::Fields;
 
 namespace {
 
-// A 64-lane wave as sam_line.h's group: bytes go to the LDS window [w0, w1) of the text.
-struct Wave {
-    char *lds;
-    uint64_t w0, w1;
-    uint32_t lane;
-    template <class P>
-    __device__ uint32_t firstOf(uint32_t n, P p) const {
-        for (uint32_t base = 0; base < n; base += 64) {
-            const uint32_t k = base + lane;
-            const bool hit = k < n && p(k);
-            const unsigned long long m = __ballot(hit);
-            if (m) return base + (uint32_t)__ffsll(m) - 1;
-        }
-        return n;
-    }
-    template <class F>
-    __device__ uint32_t sum(uint32_t n, F f) const {
-        uint32_t s = 0;
-        for (uint32_t k = lane; k < n; k += 64) s += f(k);
-        for (int o = 32; o; o >>= 1) s += __shfl_xor(s, o);
-        return s;
-    }
-    template <class F>
-    __device__ void copy(uint64_t at, uint32_t n, F f) const {
-        if (at + n <= w0 || at >= w1) return;
-        for (uint32_t k = lane; k < n; k += 64) put(at + k, f(k));
-    }
-    __device__ void put(uint64_t at, char c) const {
-        if (at >= w0 && at < w1) lds[at - w0] = c;
-    }
-    __device__ bool lead() const { return lane == 0; }
-};
-
 // What only the sorted instances of the length and write kernels take, as their last argument: the
 // unsorted instances get an empty one, and keep the arguments they had before there was a sorted
 // launch (and with them their registers and code).
@@ -245,10 +212,27 @@ hipError_t sortTempBytes(uint64_t n, hipStream_t st, size_t *bytes) {
     return sortPairs(nullptr, *bytes, nullptr, n, st);
 }
 
+hipError_t sortStep(const SortBuffers &S, const uint32_t *len, uint64_t n, hipStream_t st) {
+    const dim3 perItem((unsigned)((n + 255) / 256));
+    hipLaunchKernelGGL(sam_iota_kernel, perItem, dim3(256), 0, st, S.iota, n);
+    size_t bytes = S.tempBytes;
+    hipError_t e = sortPairs(S.temp, bytes, &S, n, st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(sam_gather_len_kernel, perItem, dim3(256), 0, st, len, S.order, n, S.slotLen);
+    return S.done ? hipEventRecord(S.done, st) : hipSuccess;
+}
+
+void scanStarts(const uint32_t *len, uint64_t n, uint64_t *sums, uint64_t *start, hipStream_t st) {
+    const uint64_t nTiles = scanTiles(n);
+    hipLaunchKernelGGL(sam_scan_sums_kernel, dim3((unsigned)nTiles), dim3(256), 0, st, len, n, sums);
+    hipLaunchKernelGGL(sam_scan_tiles_kernel, dim3(1), dim3(256), 0, st, sums, nTiles, start + n);
+    hipLaunchKernelGGL(sam_scan_starts_kernel, dim3((unsigned)nTiles), dim3(256), 0, st, len, n, sums, start);
+}
+
 hipError_t launch(const Args &A, uint64_t n, const Buffers &B, hipStream_t st, const SortBuffers *S) {
     hipError_t e = hipMemsetAsync(B.bad, 0, sizeof(uint32_t), st);
     if (e != hipSuccess) return e;
-    const uint64_t nTiles = scanTiles(n), nGroups = (n + kRecsPerGroup - 1) / kRecsPerGroup;
+    const uint64_t nGroups = (n + kRecsPerGroup - 1) / kRecsPerGroup;
     const uint64_t lenBlocks = (n + 3) / 4 < 65536 ? (n + 3) / 4 : 65536;
     const dim3 perItem((unsigned)((n + 255) / 256));
     if (S) hipLaunchKernelGGL(sam_length_kernel<true>, dim3((unsigned)lenBlocks), dim3(256), 0, st, A, n, B.len, B.scans,
@@ -258,16 +242,10 @@ hipError_t launch(const Args &A, uint64_t n, const Buffers &B, hipStream_t st, c
     if (B.mid[0] && (e = hipEventRecord(B.mid[0], st)) != hipSuccess) return e;
     const uint32_t *len = B.len;
     if (S) {
-        hipLaunchKernelGGL(sam_iota_kernel, perItem, dim3(256), 0, st, S->iota, n);
-        size_t bytes = S->tempBytes;
-        if ((e = sortPairs(S->temp, bytes, S, n, st)) != hipSuccess) return e;
-        hipLaunchKernelGGL(sam_gather_len_kernel, perItem, dim3(256), 0, st, B.len, S->order, n, S->slotLen);
-        if (S->done && (e = hipEventRecord(S->done, st)) != hipSuccess) return e;
+        if ((e = sortStep(*S, B.len, n, st)) != hipSuccess) return e;
         len = S->slotLen;
     }
-    hipLaunchKernelGGL(sam_scan_sums_kernel, dim3((unsigned)nTiles), dim3(256), 0, st, len, n, B.sums);
-    hipLaunchKernelGGL(sam_scan_tiles_kernel, dim3(1), dim3(256), 0, st, B.sums, nTiles, B.start + n);
-    hipLaunchKernelGGL(sam_scan_starts_kernel, dim3((unsigned)nTiles), dim3(256), 0, st, len, n, B.sums, B.start);
+    scanStarts(len, n, B.sums, B.start, st);
     if (B.mid[1] && (e = hipEventRecord(B.mid[1], st)) != hipSuccess) return e;
     if (S) hipLaunchKernelGGL(sam_write_kernel<true>, dim3((unsigned)nGroups), dim3(256), 0, st, A, n, B.start, B.scans,
                               B.text, B.textCap, SlotOrder<true>{S->order});

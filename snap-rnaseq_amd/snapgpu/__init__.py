@@ -538,6 +538,34 @@ class BaseAligner:
         _check(lib().snapgpu_sam_sort_ms(self._h, C.byref(v)), "sam_sort_ms")
         return v.value
 
+    def bam_format(self, reads, ids, results, cigars, read_group="FASTQ", clip=None, nm_carry=0, sorted_output=False,
+                   order=None):
+        """The module-level bam_format on the GPU (snapgpu_bam_format_gpu: uploads records and CIGARs,
+        runs the resident path's kernels, downloads the records) -> (bytes, NM carry-out).
+        sorted_output: the records in coordinate order (the stable order of bam_sort_keys); order: a
+        uint32[n] array that then receives that order (order[j] = the read of the j-th record)."""
+        if order is not None and not sorted_output:
+            raise ValueError("order needs sorted_output")
+        if order is not None and (order.dtype != np.uint32 or order.shape != (reads.n,) or not order.flags.c_contiguous):
+            raise ValueError("order must be a contiguous uint32 array with one entry per read")
+        args, keep, cap = _sam_inputs(reads, ids, results, cigars, read_group, clip)
+        used, carry = C.c_uint64(), C.c_int32()
+        buf = np.empty(max(1, cap), dtype=np.uint8)
+        tail = [int(sorted_output), order.ctypes.data if order is not None and reads.n else None]
+        fn = lib().snapgpu_bam_format_gpu
+        rc = fn(self._h, *args, int(nm_carry), C.byref(carry), buf.ctypes.data, cap, C.byref(used), *tail)
+        if rc != 0 and used.value > cap:
+            buf = np.empty(used.value, dtype=np.uint8)
+            rc = fn(self._h, *args, int(nm_carry), C.byref(carry), buf.ctypes.data, used.value, C.byref(used), *tail)
+        _check(rc, "bam_format_gpu")
+        return buf[:used.value].tobytes(), carry.value
+
+    def bam_ms(self):
+        """(kernel ms, download ms) of the last device BAM call (snapgpu_bam_last_ms)."""
+        k, d = C.c_double(), C.c_double()
+        _check(lib().snapgpu_bam_last_ms(self._h, C.byref(k), C.byref(d)), "bam_last_ms")
+        return k.value, d.value
+
     def upload(self, reads):
         return DeviceReads(self, reads)
 
@@ -738,6 +766,54 @@ class DeviceReads:
             timing["done"] = time.perf_counter()
         return buf[:used.value].tobytes()
 
+    def run_bam(self, reads, ids=None, read_group="FASTQ", sorted_output=False, nm_carry=0):
+        """BAM records of the records and CIGARs run() + run_cigars() left in HBM, encoded on the GPU
+        (asynchronous).  reads: the batch this was uploaded from; ids: None for its own ids;
+        sorted_output: the records in coordinate order, bam_order() then gives that order; nm_carry:
+        the NM that records without CIGAR ops repeat until the first record with ops (the previous
+        batch's bam_nm_carry())."""
+        rg = None if read_group is None else read_group.encode()
+        if ids is None:
+            self._bam_keep = None
+            args = [None, None, None]
+        else:
+            blob, offs, lens = _id_arrays(ids, reads.n)
+            self._bam_keep = (blob, offs, lens)
+            args = [blob, offs.ctypes.data, lens.ctypes.data]
+        fn = lib().snapgpu_bam_resident_sorted if sorted_output else lib().snapgpu_bam_resident
+        _check(fn(self.aligner._h, self._h, reads._p, *args, rg, int(nm_carry)), "bam_resident")
+        self._bam_carry = None
+
+    def bam_order(self):
+        """The output order of the last run_bam(sorted_output=True) -> uint32[n] (waits)."""
+        order = np.zeros(max(1, self.n), dtype=np.uint32)
+        _check(lib().snapgpu_bam_order_download(self.aligner._h, self._h, order.ctypes.data), "bam_order_download")
+        return order[:self.n]
+
+    def bam(self, timing=None):
+        """The records run_bam() wrote -> bytes (waits).  timing: as sam()."""
+        used, carry = C.c_uint64(), C.c_int32()
+        fn = lib().snapgpu_bam_download
+        rc = fn(self.aligner._h, self._h, None, 0, C.byref(used), C.byref(carry))
+        if rc != 0 and used.value == 0:
+            _check(rc, "bam_download")
+        buf = np.empty(max(1, used.value), dtype=np.uint8)
+        _check(fn(self.aligner._h, self._h, buf.ctypes.data, used.value, C.byref(used), C.byref(carry)), "bam_download")
+        if timing is not None:
+            timing["done"] = time.perf_counter()
+        self._bam_carry = carry.value
+        return buf[:used.value].tobytes()
+
+    def bam_nm_carry(self):
+        """The NM carry-out of the last run_bam() (waits): the nm_carry of the next batch."""
+        if getattr(self, "_bam_carry", None) is None:
+            used, carry = C.c_uint64(), C.c_int32()
+            rc = lib().snapgpu_bam_download(self.aligner._h, self._h, None, 0, C.byref(used), C.byref(carry))
+            if rc != 0 and used.value == 0:
+                _check(rc, "bam_download")
+            self._bam_carry = carry.value
+        return self._bam_carry
+
     def __del__(self):
         if getattr(self, "_h", None):
             lib().snapgpu_device_reads_free(self._h)
@@ -888,6 +964,84 @@ def sam_sort_keys(index, results):
     src = res if n else np.zeros(1, dtype=RESULT_DTYPE)
     _check(lib().snapgpu_sam_sort_keys(index._h, n, src.ctypes.data, out.ctypes.data), "sam_sort_keys")
     return out[:n]
+
+
+def bam_format(index, reads, ids, results, cigars, read_group="FASTQ", clip=None, nm_carry=0):
+    """Uncompressed BAM records (BAMFormat::writeRead, Bam.cpp:596-790) of single-end genome
+    alignments, in input order -> (bytes, NM carry-out).  Arguments as sam_format; nm_carry: the NM
+    that records without CIGAR ops repeat until the first record with ops (snapgpu_bam_format)."""
+    args, keep, cap = _sam_inputs(reads, ids, results, cigars, read_group, clip)
+    used, carry = C.c_uint64(), C.c_int32()
+    buf = np.empty(max(1, cap), dtype=np.uint8)
+    fn = lib().snapgpu_bam_format
+    rc = fn(index._h, *args, int(nm_carry), C.byref(carry), buf.ctypes.data, cap, C.byref(used))
+    if rc != 0 and used.value > cap:
+        buf = np.empty(used.value, dtype=np.uint8)
+        rc = fn(index._h, *args, int(nm_carry), C.byref(carry), buf.ctypes.data, used.value, C.byref(used))
+    _check(rc, "bam_format")
+    return buf[:used.value].tobytes(), carry.value
+
+
+def _bam_append_records(index, reads, ids, results, cigars, read_group="FASTQ", clip=None, nm_carry=0):
+    """bam_format's records through the product paths' own encoder (bamAppendRecord, csrc/host/bam.cpp)
+    on one host thread -> (bytes, NM carry-out) (tests)."""
+    args, keep, cap = _sam_inputs(reads, ids, results, cigars, read_group, clip)
+    used, carry = C.c_uint64(), C.c_int32()
+    buf = np.empty(max(1, cap), dtype=np.uint8)
+    fn = lib().snapgpu_internal_bam_append_records
+    fn.restype = C.c_int
+    fn.argtypes = ([C.c_void_p, C.POINTER(_ffi.Reads), C.c_char_p] + [C.c_void_p] * 6 + [C.c_char_p] + [C.c_void_p] * 2 +
+                   [C.c_int32, C.POINTER(C.c_int32), C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)])
+    rc = fn(index._h, *args, int(nm_carry), C.byref(carry), buf.ctypes.data, cap, C.byref(used))
+    if rc != 0 and used.value > cap:
+        buf = np.empty(used.value, dtype=np.uint8)
+        rc = fn(index._h, *args, int(nm_carry), C.byref(carry), buf.ctypes.data, used.value, C.byref(used))
+    _check(rc, "bam_append_records")
+    return buf[:used.value].tobytes(), carry.value
+
+
+def bam_record_lengths(index, reads, ids, results, cigars, read_group="FASTQ", clip=None):
+    """Byte size of every record bam_format writes, block_size + 4 (snapgpu_bam_record_lengths: the
+    host side of the device encoder's length pass) -> np.uint32 array."""
+    args, keep, _ = _sam_inputs(reads, ids, results, cigars, read_group, clip)
+    out = np.zeros(max(1, reads.n), dtype=np.uint32)
+    _check(lib().snapgpu_bam_record_lengths(index._h, *args, out.ctypes.data), "bam_record_lengths")
+    return out[:reads.n]
+
+
+def bam_sort_keys(index, results):
+    """The coordinate-sort key of every BAM record (snapgpu_bam_sort_keys: BAMFormat::getSortInfo, by
+    piece index) -> np.uint32 array.  np.argsort(keys, kind="stable") is the order of the sorted
+    device calls."""
+    res = np.ascontiguousarray(results, dtype=RESULT_DTYPE)
+    n = len(res)
+    out = np.zeros(max(1, n), dtype=np.uint32)
+    src = res if n else np.zeros(1, dtype=RESULT_DTYPE)
+    _check(lib().snapgpu_bam_sort_keys(index._h, n, src.ctypes.data, out.ctypes.data), "bam_sort_keys")
+    return out[:n]
+
+
+def bam_header(index, sam_header_text):
+    """The BAM header (BAMFormat::writeHeader, Bam.cpp:542-594) around a SAM header text -> bytes."""
+    text = sam_header_text.encode() if isinstance(sam_header_text, str) else bytes(sam_header_text)
+    used = C.c_uint64()
+    lib().snapgpu_bam_header(index._h, text, len(text), None, 0, C.byref(used))
+    buf = C.create_string_buffer(max(1, used.value))
+    _check(lib().snapgpu_bam_header(index._h, text, len(text), buf, used.value, C.byref(used)), "bam_header")
+    return C.string_at(buf, used.value)
+
+
+def bgzf_compress(data, eof=True):
+    """BGZF blocks of `data` (0xff00 input bytes each, compressed on the host threads), then the EOF
+    block if eof (snapgpu_bgzf_compress) -> bytes.  gzip.decompress gives `data` back."""
+    src = np.frombuffer(bytes(data), dtype=np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, dtype=np.uint8)
+    n = int(src.size)
+    cap = n + (n // 0xff00 + 1) * 128 + 256
+    buf = np.empty(cap, dtype=np.uint8)
+    used = C.c_uint64()
+    _check(lib().snapgpu_bgzf_compress(src.ctypes.data if n else None, n, int(bool(eof)), buf.ctypes.data, cap,
+                                       C.byref(used)), "bgzf_compress")
+    return buf[:used.value].tobytes()
 
 
 def _sam_line_write(index, reads, ids, results, cigars, read_group="FASTQ", clip=None):
