@@ -666,6 +666,34 @@ int snapgpu_bam_format_gpu(snapgpu_aligner_t *a, const snapgpu_reads_t *reads, c
 /* kernel time (HIP events over all passes) and download time of the last device BAM call */
 int snapgpu_bam_last_ms(snapgpu_aligner_t *a, double *kernelMs, double *downloadMs);
 
+/* BGZF on the GPU (bgzf.hip over bgzf_block.h): the same split into blocks of 0xff00 input bytes and
+ * the same member format as snapgpu_bgzf_compress, each member's deflate stream written by one
+ * workgroup: LZ77 matches (length 4 .. 258, distance 1 .. 32768, inside the block) in one
+ * dynamic-Huffman block, or a stored block where that is smaller, so a member is at most m + 31 bytes.
+ * A compress pass writes every member into its own slot, a scan places them and a gather pass packs
+ * them, so only the compressed bytes cross to the host.  The stream is a pure function of the input
+ * (bgzf_block.h); it is not the stream zlib writes.  There is no fallback to zlib: a failure is an
+ * error.  A device check counts the members that do not carry the size the scan gave them: always 0,
+ * else the download fails with SNAPGPU_EDEVICE.
+ * snapgpu_bam_bgzf_resident: asynchronous, on the stream of the BAM passes; compresses the records of
+ * the batch's last snapgpu_bam_resident / _sorted call, in that call's order (SNAPGPU_EINVAL when
+ * there was none).  A later snapgpu_bam_resident* on the batch invalidates the compressed stream.
+ * snapgpu_bam_bgzf_download: waits; size contract as snapgpu_bam_download; eof != 0 appends the
+ * 28-byte EOF block.  SNAPGPU_EINVAL without a snapgpu_bam_bgzf_resident since the batch's last
+ * snapgpu_bam_resident*.  snapgpu_bam_download of the batch still returns the records afterwards.
+ * snapgpu_bgzf_compress_gpu: the batch form for any n bytes (upload, the same kernels, download).
+ * snapgpu_bgzf_compress_model: the same stream from the host thread pool, byte for byte, for every
+ * input and thread count; needs no GPU.
+ * snapgpu_bgzf_last_ms: kernel time (HIP events over all passes) and download time of the aligner's
+ * last device BGZF call. */
+int snapgpu_bam_bgzf_resident(snapgpu_aligner_t *a, snapgpu_device_reads_t *d);
+int snapgpu_bam_bgzf_download(snapgpu_aligner_t *a, snapgpu_device_reads_t *d, int eof, char *out, uint64_t cap,
+                              uint64_t *used);
+int snapgpu_bgzf_compress_gpu(snapgpu_aligner_t *a, const char *in, uint64_t n, int eof, char *out, uint64_t cap,
+                              uint64_t *used);
+int snapgpu_bgzf_compress_model(const char *in, uint64_t n, int eof, char *out, uint64_t cap, uint64_t *used);
+int snapgpu_bgzf_last_ms(snapgpu_aligner_t *a, double *kernelMs, double *downloadMs);
+
 /* --------------------------------------------- RNA annotation (GTF) */
 /* GTFReader (SNAPLib/GTFReader.cpp): exon lines of a GTF/GFF3 file -> transcripts, each an
  * exon list sorted by start with an intron feature between consecutive exons (Load :1245,

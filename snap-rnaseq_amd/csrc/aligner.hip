@@ -21,6 +21,7 @@
 #include "internal.h"
 #include "large_copy.h"
 #include "bam_format.h"
+#include "bgzf.h"
 #include "sam_format.h"
 
 using namespace sgk;
@@ -1178,6 +1179,16 @@ struct BamState : SamState {
     int32_t carryIn = 0;
 };
 
+// Device BGZF compressor (bgzf.hip) state of one resident batch, or of the aligner's batch form:
+// grow-only device buffers (bgzfgpu::Buffers), the batch form's copy of its input.
+struct BgzfState {
+    SamState::Buf in, slots, sizes, offs, tokens, packed, res;
+    uint64_t maxBlocks = 0;   // what the last call's buffers were sized for (0: nothing to compress)
+    bool ran = false;         // the compressed stream is that of the batch's last BAM call
+    hipEvent_t ev[4] = {};    // before the compress pass, after it, after the scan, after the check
+    double downloadMs = 0;
+};
+
 struct snapgpu_device_reads {
     snapgpu_aligner_t *owner = nullptr;
     char *dBases = nullptr, *dQuals = nullptr;
@@ -1195,6 +1206,7 @@ struct snapgpu_device_reads {
     uint64_t extentHash = 0;  // of the offsets and lengths uploaded (snapgpu_sam_resident checks its batch)
     SamState sam;
     BamState bam;
+    BgzfState bgzf;
 };
 
 struct snapgpu_aligner {
@@ -1285,6 +1297,9 @@ struct snapgpu_aligner {
     SamState *samLast = nullptr;
     BamState bamBatch;
     BamState *bamLast = nullptr;   // snapgpu_bam_last_ms
+    BgzfState bgzfBatch;
+    BgzfState *bgzfLast = nullptr; // snapgpu_bgzf_last_ms
+    int bgzfGrid = 0;              // workgroups of the compress pass: one per CU
     void *samPin[2] = {};
     hipEvent_t samPinDone[2] = {};
     hipStream_t stream() const { return lane[0].stream; }
@@ -1626,6 +1641,17 @@ void bamStateFree(const snapgpu_aligner_t *a, BamState &S) {
     samStateFree(a, S);
 }
 
+void bgzfStateFree(const snapgpu_aligner_t *a, BgzfState &S) {
+    for (auto *b : {&S.in, &S.slots, &S.sizes, &S.offs, &S.tokens, &S.packed, &S.res}) {
+        devFree(a, b->p);
+        b->p = nullptr;
+        b->cap = 0;
+    }
+    if (!(a && a->failed))
+        for (auto &e : S.ev)
+            if (e) { hipEventDestroy(e); e = nullptr; }
+}
+
 // Wait for an event, honouring SNAPGPU_TIMEOUT_S: on expiry the aligner is marked failed.
 int waitEvent(snapgpu_aligner_t *a, hipEvent_t ev) {
     if (a->failed) { snapgpu::setError("aligner failed earlier (device timeout): no further work accepted"); return SNAPGPU_EDEVICE; }
@@ -1869,6 +1895,7 @@ void snapgpu_aligner_free(snapgpu_aligner_t *a) {
     hostPinnedFree(a->cgPinOut);
     samStateFree(a, a->samBatch);
     bamStateFree(a, a->bamBatch);
+    bgzfStateFree(a, a->bgzfBatch);
     for (int k = 0; k < 2; k++) {
         if (!a->failed) hostPinnedFree(a->samPin[k]);
         if (a->samPinDone[k]) hipEventDestroy(a->samPinDone[k]);
@@ -2086,6 +2113,8 @@ void snapgpu_device_reads_free(snapgpu_device_reads_t *d) {
     samStateFree(a, d->sam);
     if (a && a->bamLast == &d->bam) const_cast<snapgpu_aligner_t *>(a)->bamLast = nullptr;
     bamStateFree(a, d->bam);
+    if (a && a->bgzfLast == &d->bgzf) const_cast<snapgpu_aligner_t *>(a)->bgzfLast = nullptr;
+    bgzfStateFree(a, d->bgzf);
     delete d;
 }
 
@@ -3598,6 +3627,7 @@ static int samResident(snapgpu_aligner_t *a, snapgpu_device_reads_t *d, const sn
         HIPCHK(hipEventRecord(L.done, L.stream));
         HIPCHK(hipStreamWaitEvent(st, L.done, 0));
     }
+    if (bam) d->bgzf.ran = false;   // the records change: a compressed stream of the earlier ones is stale
     if (int rc = bam ? bamLaunch(a, d->bam, A, reads->n, sorted, nmCarryIn) : samLaunch(a, S, A, reads->n, sorted)) return rc;
     // the next pass set over these reads rewrites the records: it waits for the SAM / BAM kernels
     HIPCHK(hipEventRecord(a->residentSideDone, st));
@@ -3770,6 +3800,145 @@ int snapgpu_bam_last_ms(snapgpu_aligner_t *a, double *kernelMs, double *download
     }
     *kernelMs = f;
     *downloadMs = S.downloadMs;
+    return SNAPGPU_OK;
+}
+
+// ------------------------------------------------- BGZF on the device (bgzf.hip)
+// The compressor's passes on the side stream over the bytes at `in`: their count is *nDev (the
+// resident records' total, written by the BAM passes ahead on that stream) or n, at most capBytes.
+static int bgzfLaunch(snapgpu_aligner_t *a, BgzfState &S, const char *in, const uint64_t *nDev, uint64_t n, uint64_t capBytes) {
+    for (auto &e : S.ev)
+        if (!e) HIPCHK(hipEventCreate(&e));
+    S.ran = true;
+    S.downloadMs = 0;
+    a->bgzfLast = &S;
+    S.maxBlocks = bgzfgpu::blocksOf(nDev ? capBytes : std::min(n, capBytes));
+    if (S.maxBlocks == 0) return SNAPGPU_OK;
+    if (S.maxBlocks > 0x7fffffffull) { snapgpu::setError("bgzf: input too large"); return SNAPGPU_EINVAL; }
+    if (!a->bgzfGrid) {
+        hipDeviceProp_t prop;
+        HIPCHK(hipGetDeviceProperties(&prop, a->device));
+        a->bgzfGrid = std::max(1, prop.multiProcessorCount);
+    }
+    const uint32_t grid = (uint32_t)std::min<uint64_t>(S.maxBlocks, (uint64_t)a->bgzfGrid);
+    HIPCHK(samGrow(a, S.slots, S.maxBlocks * bgzfblock::kSlot));
+    HIPCHK(samGrow(a, S.packed, S.maxBlocks * bgzfblock::kSlot));
+    HIPCHK(samGrow(a, S.sizes, S.maxBlocks * 4));
+    HIPCHK(samGrow(a, S.offs, (S.maxBlocks + 1) * 8));
+    HIPCHK(samGrow(a, S.tokens, (uint64_t)grid * bgzfblock::kBlockIn * 4));
+    HIPCHK(samGrow(a, S.res, sizeof(bgzfgpu::Result)));
+    const bgzfgpu::Buffers B{(uint8_t *)S.slots.p, (uint32_t *)S.sizes.p, (uint64_t *)S.offs.p, (uint32_t *)S.tokens.p,
+                             (uint8_t *)S.packed.p, (bgzfgpu::Result *)S.res.p, grid};
+    HIPCHK(hipEventRecord(S.ev[0], a->sideStream));
+    HIPCHK(bgzfgpu::launch((const uint8_t *)in, nDev, n, capBytes, B, a->sideStream, S.ev[1], S.ev[2]));
+    HIPCHK(hipEventRecord(S.ev[3], a->sideStream));
+    return SNAPGPU_OK;
+}
+
+// Wait for S's kernels, check them, and copy the packed members (and the EOF block) to the caller.
+static int bgzfDownload(snapgpu_aligner_t *a, BgzfState &S, int eof, char *out, uint64_t cap, uint64_t *used) {
+    static const unsigned char kEof[28] = {31, 139, 8, 4, 0, 0, 0, 0, 0, 255, 6, 0, 66, 67, 2, 0, 27, 0,
+                                           3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    *used = 0;
+    S.downloadMs = 0;
+    uint64_t total = 0;
+    const auto t0 = std::chrono::steady_clock::now();
+    if (S.maxBlocks) {
+        if (int rc = waitEvent(a, S.ev[3])) return rc;
+        bgzfgpu::Result r{};
+        HIPCHK(hipMemcpy(&r, S.res.p, sizeof r, hipMemcpyDeviceToHost));
+        if (r.bad || r.nBlocks > S.maxBlocks || r.total > S.maxBlocks * bgzfblock::kSlot) {
+            char msg[160];
+            snprintf(msg, sizeof msg, "bgzf: %u of %u members are not what the size array says (stream %llu bytes, %llu slots)",
+                     r.bad, r.nBlocks, (unsigned long long)r.total, (unsigned long long)S.maxBlocks);
+            snapgpu::setError(msg);
+            return SNAPGPU_EDEVICE;
+        }
+        total = r.total;
+    }
+    const uint64_t need = total + (eof ? 28 : 0);
+    *used = need;
+    if (need > cap || (!out && need)) { snapgpu::setError("bgzf_download: output buffer too small"); return SNAPGPU_EINVAL; }
+    if (total)
+        if (int rc = textDownload(a, (const char *)S.packed.p, total, out)) return rc;
+    if (eof) memcpy(out + total, kEof, 28);
+    S.downloadMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return SNAPGPU_OK;
+}
+
+int snapgpu_bam_bgzf_resident(snapgpu_aligner_t *a, snapgpu_device_reads_t *d) {
+    if (!a || !d) { snapgpu::setError("bam_bgzf_resident: null argument"); return SNAPGPU_EINVAL; }
+    if (a->failed) { snapgpu::setError("aligner failed earlier (device timeout)"); return SNAPGPU_EDEVICE; }
+    if (d->owner != a) { snapgpu::setError("bam_bgzf_resident: the resident batch belongs to another aligner"); return SNAPGPU_EINVAL; }
+    if (!d->bam.ran) {
+        snapgpu::setError("bam_bgzf_resident: no snapgpu_bam_resident before snapgpu_bam_bgzf_resident");
+        return SNAPGPU_EINVAL;
+    }
+    HIPCHK(hipSetDevice(a->device));
+    // the records and their total are written by the BAM passes ahead on the side stream; the next
+    // snapgpu_bam_resident rewrites them on that stream, after these passes
+    const BamState &R = d->bam;
+    if (R.n == 0) return bgzfLaunch(a, d->bgzf, nullptr, nullptr, 0, 0);
+    return bgzfLaunch(a, d->bgzf, (const char *)R.text.p, (const uint64_t *)R.start.p + R.n, 0, R.textBound);
+}
+
+int snapgpu_bam_bgzf_download(snapgpu_aligner_t *a, snapgpu_device_reads_t *d, int eof, char *out, uint64_t cap,
+                              uint64_t *used) {
+    if (!a || !d || !used) { snapgpu::setError("bam_bgzf_download: null argument"); return SNAPGPU_EINVAL; }
+    if (a->failed) { snapgpu::setError("aligner failed earlier (device timeout)"); return SNAPGPU_EDEVICE; }
+    if (!d->bgzf.ran) {
+        snapgpu::setError("bam_bgzf_download: no snapgpu_bam_bgzf_resident since the batch's last snapgpu_bam_resident");
+        return SNAPGPU_EINVAL;
+    }
+    HIPCHK(hipSetDevice(a->device));
+    return bgzfDownload(a, d->bgzf, eof, out, cap, used);
+}
+
+int snapgpu_bgzf_compress_gpu(snapgpu_aligner_t *a, const char *in, uint64_t n, int eof, char *out, uint64_t cap,
+                              uint64_t *used) {
+    if (!a || (!in && n) || !used) { snapgpu::setError("bgzf_compress_gpu: null argument"); return SNAPGPU_EINVAL; }
+    if (a->failed) { snapgpu::setError("aligner failed earlier (device timeout)"); return SNAPGPU_EDEVICE; }
+    HIPCHK(hipSetDevice(a->device));
+    BgzfState &S = a->bgzfBatch;
+    if (S.ran && S.maxBlocks) HIPCHK(hipEventSynchronize(S.ev[3]));
+    if (n) {
+        HIPCHK(samGrow(a, S.in, n + 64));
+        HIPCHK(hipMemcpyAsync(S.in.p, in, n, hipMemcpyHostToDevice, a->sideStream));
+    }
+    if (int rc = bgzfLaunch(a, S, (const char *)S.in.p, nullptr, n, n)) return rc;
+    return bgzfDownload(a, S, eof, out, cap, used);
+}
+
+int snapgpu_bgzf_last_ms(snapgpu_aligner_t *a, double *kernelMs, double *downloadMs) {
+    if (!a || !kernelMs || !downloadMs) return SNAPGPU_EINVAL;
+    if (!a->bgzfLast) { snapgpu::setError("bgzf_last_ms: no device BGZF call on this aligner"); return SNAPGPU_EINVAL; }
+    if (a->failed) { snapgpu::setError("aligner failed earlier (device timeout)"); return SNAPGPU_EDEVICE; }
+    HIPCHK(hipSetDevice(a->device));
+    BgzfState &S = *a->bgzfLast;
+    float f = 0;
+    if (S.maxBlocks) {
+        HIPCHK(hipEventSynchronize(S.ev[3]));
+        HIPCHK(hipEventElapsedTime(&f, S.ev[0], S.ev[3]));
+    }
+    *kernelMs = f;
+    *downloadMs = S.downloadMs;
+    return SNAPGPU_OK;
+}
+
+// ms[0 .. 3): the compress pass, the scan, the gather pass with the check, of the last device BGZF
+// call (tools/bgzf_gpu_time.py)
+int snapgpu_internal_bgzf_pass_ms(snapgpu_aligner_t *a, double *ms) {
+    if (!a || !ms || !a->bgzfLast || a->failed) return SNAPGPU_EINVAL;
+    HIPCHK(hipSetDevice(a->device));
+    BgzfState &S = *a->bgzfLast;
+    for (int k = 0; k < 3; k++) {
+        float f = 0;
+        if (S.maxBlocks) {
+            HIPCHK(hipEventSynchronize(S.ev[k + 1]));
+            HIPCHK(hipEventElapsedTime(&f, S.ev[k], S.ev[k + 1]));
+        }
+        ms[k] = f;
+    }
     return SNAPGPU_OK;
 }
 

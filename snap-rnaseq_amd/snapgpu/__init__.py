@@ -566,6 +566,18 @@ class BaseAligner:
         _check(lib().snapgpu_bam_last_ms(self._h, C.byref(k), C.byref(d)), "bam_last_ms")
         return k.value, d.value
 
+    def bgzf_compress(self, data, eof=True):
+        """BGZF blocks of `data` compressed on the GPU (snapgpu_bgzf_compress_gpu: uploads the bytes,
+        runs the resident path's kernels, downloads the members), then the EOF block if eof -> bytes.
+        Byte-identical to the module-level bgzf_compress_model."""
+        return _bgzf_call(lambda *tail: lib().snapgpu_bgzf_compress_gpu(self._h, *tail), data, eof, "bgzf_compress_gpu")
+
+    def bgzf_ms(self):
+        """(kernel ms, download ms) of the last device BGZF call (snapgpu_bgzf_last_ms)."""
+        k, d = C.c_double(), C.c_double()
+        _check(lib().snapgpu_bgzf_last_ms(self._h, C.byref(k), C.byref(d)), "bgzf_last_ms")
+        return k.value, d.value
+
     def upload(self, reads):
         return DeviceReads(self, reads)
 
@@ -814,6 +826,24 @@ class DeviceReads:
             self._bam_carry = carry.value
         return self._bam_carry
 
+    def run_bgzf(self):
+        """BGZF members of the records the last run_bam() wrote, compressed on the GPU (asynchronous;
+        snapgpu_bam_bgzf_resident).  A later run_bam() invalidates them."""
+        _check(lib().snapgpu_bam_bgzf_resident(self.aligner._h, self._h), "bam_bgzf_resident")
+
+    def bgzf(self, eof=True, timing=None):
+        """The members run_bgzf() wrote, then the EOF block if eof -> bytes (waits).  timing: as sam()."""
+        used = C.c_uint64()
+        fn = lib().snapgpu_bam_bgzf_download
+        rc = fn(self.aligner._h, self._h, int(bool(eof)), None, 0, C.byref(used))
+        if rc != 0 and used.value == 0:
+            _check(rc, "bam_bgzf_download")
+        buf = np.empty(max(1, used.value), dtype=np.uint8)
+        _check(fn(self.aligner._h, self._h, int(bool(eof)), buf.ctypes.data, used.value, C.byref(used)), "bam_bgzf_download")
+        if timing is not None:
+            timing["done"] = time.perf_counter()
+        return buf[:used.value].tobytes()
+
     def __del__(self):
         if getattr(self, "_h", None):
             lib().snapgpu_device_reads_free(self._h)
@@ -1042,6 +1072,24 @@ def bgzf_compress(data, eof=True):
     _check(lib().snapgpu_bgzf_compress(src.ctypes.data if n else None, n, int(bool(eof)), buf.ctypes.data, cap,
                                        C.byref(used)), "bgzf_compress")
     return buf[:used.value].tobytes()
+
+
+def _bgzf_call(fn, data, eof, what):
+    """fn(in, n, eof, out, cap, used) of the device compressor or its host model over `data` -> bytes.
+    A member takes at most its input + 31 bytes."""
+    src = np.frombuffer(bytes(data), dtype=np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, dtype=np.uint8)
+    n = int(src.size)
+    cap = n + (n // 0xff00 + 1) * 31 + 28
+    buf = np.empty(cap, dtype=np.uint8)
+    used = C.c_uint64()
+    _check(fn(src.ctypes.data if n else None, n, int(bool(eof)), buf.ctypes.data, cap, C.byref(used)), what)
+    return buf[:used.value].tobytes()
+
+
+def bgzf_compress_model(data, eof=True):
+    """The device BGZF compressor's stream from the host threads, byte for byte (snapgpu_bgzf_compress_model:
+    the serial restatement of csrc/bgzf_block.h; needs no GPU) -> bytes.  gzip.decompress gives `data` back."""
+    return _bgzf_call(lib().snapgpu_bgzf_compress_model, data, eof, "bgzf_compress_model")
 
 
 def _sam_line_write(index, reads, ids, results, cigars, read_group="FASTQ", clip=None):

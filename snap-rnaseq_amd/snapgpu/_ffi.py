@@ -370,6 +370,14 @@ _PROTOS = [
                                          C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.c_void_p, C.c_uint64,
                                          C.POINTER(C.c_uint64), C.c_int, C.c_void_p]),
     ("snapgpu_bam_last_ms", C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    ("snapgpu_bam_bgzf_resident", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("snapgpu_bam_bgzf_download", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_uint64,
+                                            C.POINTER(C.c_uint64)]),
+    ("snapgpu_bgzf_compress_gpu", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_uint64,
+                                            C.POINTER(C.c_uint64)]),
+    ("snapgpu_bgzf_compress_model", C.c_int, [C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_uint64,
+                                              C.POINTER(C.c_uint64)]),
+    ("snapgpu_bgzf_last_ms", C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     ("snapgpu_gather_peak", C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_double)]),
     ("snapgpu_aligner_bucket_info", C.c_int, [C.c_void_p, C.POINTER(BucketInfo)]),
     ("snapgpu_aligner_lookup_seeds", C.c_int, [C.c_void_p, C.c_char_p, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p]),
