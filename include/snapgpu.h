@@ -371,6 +371,8 @@ typedef struct snapgpu_timing {
     uint64_t nSimpleReads;   /* records written by the simple pass (simple_align_kernel: reads whose
                                 seeds all point at one candidate), ahead of pass 1 */
     uint64_t nSimpleBailed;  /* reads <= 128 bases the simple pass handed on to pass 1 */
+    uint64_t nSimpleWide;    /* of nSimpleReads: records written by the pass's one-read path (the reads its
+                                four-reads-per-wave path hands on: a non-ACGT base, a score above 7, ...) */
 } snapgpu_timing_t;
 int snapgpu_last_timing(snapgpu_aligner_t *a, snapgpu_timing_t *t);
 

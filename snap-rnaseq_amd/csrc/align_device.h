@@ -65,6 +65,10 @@ struct DevTables {
     // whose bases are all ACGT: the sequence then depends on n and seedLen only (0xff: not reached)
     uint8_t seedSeq[129][16];
     uint32_t rcp16[SDIV_MAX_D + 1];   // rcp16_of(d) (small_div.h): the lps quotient's reciprocal, read when the seeds wrap
+    // The walk schedule of an all-ACGT read of length n at this aligner's maxSeeds (simple_schedule.h; set when
+    // the aligner is created, KArgs::tab only): lowestPossibleScore after step k, and nSteps | need17 << 7
+    uint8_t simpleSched[129][16];
+    uint8_t simpleSteps[129];
 };
 // The seedLen-independent tables (indel, phred, perfect, mapqT), one copy per device, set
 // once by the host: a global's address is a constant the compiler rematerializes, where a

@@ -1999,6 +1999,12 @@ snapgpu_aligner_t *snapgpu_aligner_create(int device, const snapgpu_index_t *idx
     fillTables(t, idx->seedLen);
     for (uint32_t len = 0; len <= 512; len++)   // BaseAligner.cpp:563-568, double arithmetic as there
         t.maxSeedsForLen[len] = (uint32_t)(int)(params->maxSeedCoverage * (double)len / (double)idx->seedLen);
+    for (uint32_t len = idx->seedLen; len <= 128; len++) {   // the simple pass's walk schedule (simple_schedule.h)
+        SimpleSchedule s;
+        simple_schedule(len, idx->seedLen, params->maxSeedsToUse ? params->maxSeedsToUse : t.maxSeedsForLen[len], t.wrap, s);
+        memcpy(t.simpleSched[len], s.lpsAfter, sizeof(s.lpsAfter));
+        t.simpleSteps[len] = (uint8_t)(s.nSteps | (s.need17 << 7));
+    }
     if ((e = hipMalloc(&a->dTab, sizeof(DevTables))) != hipSuccess) return fail("tables", e);
     if ((e = hipMemcpy(a->dTab, &t, sizeof(t), hipMemcpyHostToDevice)) != hipSuccess) return fail("tables", e);
     // persistent grid: waves resident on the device; element arena per wave and lane
@@ -2221,8 +2227,9 @@ static int launch_passes(snapgpu_aligner_t *a, int li, const PassIO &io, const A
         Q.counter = L.counter + 8;
         int gridS = a->gridSimple;
         if ((uint64_t)gridS > io.n) gridS = (int)io.n;
+        if ((uint64_t)gridS * SIMPLE_CHUNK > io.n) gridS = (int)((io.n + SIMPLE_CHUNK - 1) / SIMPLE_CHUNK);
         hipLaunchKernelGGL(simple_align_kernel, dim3(gridS), dim3(64), 0, L.stream, Q, io.defer2, L.counter + 9,
-                           L.counter + 12);
+                           L.counter + 12, L.counter + 13);
         HIPCHK(hipGetLastError());
         A.readList = io.defer2; A.readCount = L.counter + 9;
     }
@@ -2339,6 +2346,7 @@ static int accountEvSet(snapgpu_aligner_t *a, const EvSet &v) {
     a->timing.nForcedLimitSpans += v.hCounter[11];
     a->timing.nSimpleBailed += v.hCounter[9];
     a->timing.nSimpleReads += v.hCounter[12];
+    a->timing.nSimpleWide += v.hCounter[13];
     return SNAPGPU_OK;
 }
 

@@ -163,6 +163,7 @@ class Timing(C.Structure):
         ("nForcedLimitSpans", C.c_uint64),
         ("nSimpleReads", C.c_uint64),
         ("nSimpleBailed", C.c_uint64),
+        ("nSimpleWide", C.c_uint64),
     ]
 
 
