@@ -265,6 +265,10 @@ snapgpu_reads_t *snapgpu_reads_synthetic(const snapgpu_genome_t *g, const snapgp
 int snapgpu_reads_synthetic_pairs(const snapgpu_genome_t *g, const snapgpu_synth_reads_params_t *p, uint32_t insertMean,
                                   uint32_t insertSd, snapgpu_reads_t **reads0, snapgpu_reads_t **reads1);
 snapgpu_reads_t *snapgpu_reads_from_fastq(const char *path);
+/* The same over nBytes of FASTQ text in memory (snapgpu_reads_from_fastq maps the file and calls
+ * this).  Records are the line quadruples 4r .. 4r + 3, lines counted by '\n'; a last line without
+ * a newline counts, 1-3 trailing lines are ignored.  name only appears in error messages. */
+snapgpu_reads_t *snapgpu_reads_from_fastq_buffer(const char *text, uint64_t nBytes, const char *name);
 /* Build a batch from caller arrays (copies them). */
 snapgpu_reads_t *snapgpu_reads_from_arrays(uint64_t n, const char *bases, const char *quals,
                                            const uint64_t *offsets, const uint32_t *lengths);
@@ -337,6 +341,30 @@ void snapgpu_device_reads_free(snapgpu_device_reads_t *d);
 int  snapgpu_align_resident(snapgpu_aligner_t *a, snapgpu_device_reads_t *d);
 int  snapgpu_results_download(snapgpu_aligner_t *a, snapgpu_device_reads_t *d, snapgpu_result_t *out);
 int  snapgpu_synchronize(snapgpu_aligner_t *a);
+
+/* FASTQ parsed on the device (fastq_parse.hip): the text is uploaded through pinned staging and
+ * split, clipped (ReadClippingType clipping, 0..3) and packed in device memory.  *dOut is what
+ * snapgpu_reads_upload of the host parser's batch, clipped by snapgpu_reads_clip, would be.  With
+ * SNAPGPU_FASTQ_HOST_BATCH in flags, *readsOut is that host batch itself, downloaded (free it with
+ * snapgpu_reads_free); without, readsOut may be NULL and only offsets and lengths come back.
+ * Synchronous.  SNAPGPU_EFORMAT, with the host parser's message, for a record without '@' header;
+ * SNAPGPU_ENOMEM when the device's free memory cannot hold the call's buffers.  There is no
+ * fallback to the host parser.  snapgpu_fastq_upload_file reads the file straight into the staging. */
+#define SNAPGPU_FASTQ_HOST_BATCH 1u
+int snapgpu_fastq_upload(snapgpu_aligner_t *a, const char *text, uint64_t nBytes, const char *name,
+                         int clipping, uint32_t flags,
+                         snapgpu_device_reads_t **dOut, snapgpu_reads_t **readsOut);
+int snapgpu_fastq_upload_file(snapgpu_aligner_t *a, const char *path, int clipping, uint32_t flags,
+                              snapgpu_device_reads_t **dOut, snapgpu_reads_t **readsOut);
+/* The aligner's last snapgpu_fastq_upload*: text upload (host pass into the staging included),
+ * kernels (HIP events), downloads, in ms.  SNAPGPU_EINVAL when there was none. */
+int snapgpu_fastq_last_ms(snapgpu_aligner_t *a, double *uploadMs, double *kernelMs, double *downloadMs);
+uint32_t snapgpu_fastq_tile_bytes(void);   /* bytes of text one workgroup scans for newlines */
+/* Test accessor: a resident batch's n, bytes, longest read and extent hash; its offsets (n),
+ * lengths (n), and bases and qualities (bytes + 64 each) where the pointers are not NULL. */
+int snapgpu_device_reads_peek(snapgpu_aligner_t *a, snapgpu_device_reads_t *d, uint64_t *n, uint64_t *bytes,
+                              uint32_t *maxLen, uint64_t *extentHash, uint64_t *offsets, uint32_t *lengths,
+                              char *bases, char *quals);
 
 /* Timing of the dominant kernel (HIP events on the stream it ran on), in ms, for the last
  * snapgpu_align_resident / snapgpu_align_batch call.  snapgpu_align_batch pipelines its reads

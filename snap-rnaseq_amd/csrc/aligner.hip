@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include <chrono>
+#include <functional>
 #include <cmath>
 #include <cstring>
 #include <algorithm>
@@ -13,6 +14,10 @@
 #include <type_traits>
 #include <vector>
 
+#include <fcntl.h>
+#include <sys/stat.h>
+#include <unistd.h>
+
 #include "align_device.h"
 #include "align_score.h"
 #include "seed_lookup.h"
@@ -22,6 +27,7 @@
 #include "large_copy.h"
 #include "bam_format.h"
 #include "bgzf.h"
+#include "fastq_parse.h"
 #include "sam_format.h"
 
 using namespace sgk;
@@ -1302,6 +1308,17 @@ struct snapgpu_aligner {
     int bgzfGrid = 0;              // workgroups of the compress pass: one per CU
     void *samPin[2] = {};
     hipEvent_t samPinDone[2] = {};
+    // device FASTQ parser (snapgpu_fastq_upload): the text, newline positions and per-record arrays,
+    // grow-only; the pinned staging of the text upload (two chunks in flight); the last call's times
+    struct FastqState {
+        ExBuf text, counts, tileStart, sums, nl, rec, baseStart, idStart, sums2, tot, ids;
+        void *pin[2] = {};
+        hipEvent_t pinDone[2] = {};
+        hipEvent_t ev[9] = {};   // 0-2 count, scan; 3-6 line starts, record pass, scans; 7-8 copy pass
+        bool ran = false;
+        double uploadMs = 0, kernelMs = 0, downloadMs = 0;
+        double passMs[6] = {};   // count, scan, line starts, records, scans, copy (snapgpu_internal_fastq_pass_ms)
+    } fq;
     hipStream_t stream() const { return lane[0].stream; }
 };
 
@@ -1900,6 +1917,14 @@ void snapgpu_aligner_free(snapgpu_aligner_t *a) {
         if (!a->failed) hostPinnedFree(a->samPin[k]);
         if (a->samPinDone[k]) hipEventDestroy(a->samPinDone[k]);
     }
+    for (auto *b : {&a->fq.text, &a->fq.counts, &a->fq.tileStart, &a->fq.sums, &a->fq.nl, &a->fq.rec, &a->fq.baseStart,
+                    &a->fq.idStart, &a->fq.sums2, &a->fq.tot, &a->fq.ids})
+        devFree(a, b->p);
+    for (int k = 0; k < 2; k++) {
+        if (!a->failed) hostPinnedFree(a->fq.pin[k]);
+        if (a->fq.pinDone[k]) hipEventDestroy(a->fq.pinDone[k]);
+    }
+    for (auto &e : a->fq.ev) if (e) hipEventDestroy(e);
     snapgpu_device_reads_free(a->exReads);
     for (auto *b : {&a->exSearch, &a->exScratch, &a->exFound, &a->exHits, &a->exOff, &a->exDense}) devFree(a, b->p);
     delete a;
@@ -3930,6 +3955,370 @@ int snapgpu_bgzf_last_ms(snapgpu_aligner_t *a, double *kernelMs, double *downloa
     }
     *kernelMs = f;
     *downloadMs = S.downloadMs;
+    return SNAPGPU_OK;
+}
+
+// ------------------------------------------------- FASTQ parsed on the device (fastq_parse.hip)
+}  // extern "C"
+
+namespace {
+
+const uint64_t kFastqChunk = 16ull << 20;   // bytes per pinned staging chunk of the text upload
+
+// Bytes a grow-only buffer would newly allocate for `bytes` (ensure's policy), 0 when it fits.
+uint64_t growBytes(const snapgpu_aligner::ExBuf &b, uint64_t bytes) { return bytes <= b.cap ? 0 : bytes + bytes / 4 + 256; }
+
+hipError_t fqEnsure(snapgpu_aligner_t *a, snapgpu_aligner::ExBuf &b, uint64_t bytes) {
+    if (bytes <= b.cap) return hipSuccess;
+    devFree(a, b.p);
+    b.p = nullptr;
+    b.cap = 0;
+    const uint64_t want = growBytes(b, bytes);
+    const hipError_t e = hipMalloc(&b.p, want);
+    if (e == hipSuccess) b.cap = want;
+    return e;
+}
+
+// hipMemGetInfo before a group of allocations, as the device index builder asks: the group must fit
+// in what is free now.
+int fqFits(uint64_t need, const char *what) {
+    size_t freeB = 0, totalB = 0;
+    HIPCHK(hipMemGetInfo(&freeB, &totalB));
+    if (need > freeB) {
+        char msg[200];
+        snprintf(msg, sizeof msg, "fastq_upload: %s needs %llu bytes of device memory, %llu are free", what,
+                 (unsigned long long)need, (unsigned long long)freeB);
+        snapgpu::setError(msg);
+        return SNAPGPU_ENOMEM;
+    }
+    return SNAPGPU_OK;
+}
+
+// fill(dst, off, m): bytes [off, off + m) of the text into a staging chunk (false: setError was called)
+using FastqFill = std::function<bool(char *, uint64_t, uint64_t)>;
+
+// The text to device memory through two pinned staging chunks: chunk k + 1 is filled by the host
+// while chunk k crosses PCIe (textDownload's reverse).  *last = the text's last byte.
+int fastqTextUpload(snapgpu_aligner_t *a, uint64_t nBytes, const FastqFill &fill, char *last) {
+    auto &F = a->fq;
+    for (int k = 0; k < 2; k++) {
+        if (!F.pin[k]) HIPCHK(hipHostMalloc(&F.pin[k], kFastqChunk, hipHostMallocDefault));
+        if (!F.pinDone[k]) HIPCHK(hipEventCreateWithFlags(&F.pinDone[k], hipEventDisableTiming));
+    }
+    const uint64_t cap = fqgpu::textCapacity(nBytes);
+    HIPCHK(hipMemsetAsync((char *)F.text.p + nBytes, 0, cap - nBytes, a->copyStream));
+    const uint64_t nChunks = (nBytes + kFastqChunk - 1) / kFastqChunk;
+    for (uint64_t k = 0; k < nChunks; k++) {
+        const uint64_t b = k * kFastqChunk, m = std::min(kFastqChunk, nBytes - b);
+        char *pin = (char *)F.pin[k & 1];
+        if (k >= 2)
+            if (int rc = waitEvent(a, F.pinDone[k & 1])) return rc;
+        if (!fill(pin, b, m)) return SNAPGPU_EIO;
+        if (k + 1 == nChunks) *last = pin[m - 1];
+        HIPCHK(hipMemcpyAsync((char *)F.text.p + b, pin, m, hipMemcpyHostToDevice, a->copyStream));
+        HIPCHK(hipEventRecord(F.pinDone[k & 1], a->copyStream));
+    }
+    HIPCHK(hipStreamSynchronize(a->copyStream));
+    return SNAPGPU_OK;
+}
+
+// [0, m) split over this rank's host threads (one below 1 MB)
+template <class Fn>
+void fastqParallel(uint64_t m, Fn fn) {
+    const unsigned t = m < (1u << 20) ? 1u : snapgpu::hostThreads(16);
+    std::vector<std::thread> th;
+    for (unsigned j = 1; j < t; j++) th.emplace_back([=] { fn(m * j / t, m * (j + 1) / t); });
+    fn(0, m / t);
+    for (auto &x : th) x.join();
+}
+
+// d and r: what the call has allocated so far (the caller frees them when the call fails)
+int fastqRun(snapgpu_aligner_t *a, uint64_t nBytes, const FastqFill &fill, const char *name, int clipping, bool hostBatch,
+             snapgpu_device_reads_t *&d, snapgpu_reads_t *&r) {
+    using clk = std::chrono::steady_clock;
+    auto ms = [](clk::time_point t0) { return std::chrono::duration<double, std::milli>(clk::now() - t0).count(); };
+    auto &F = a->fq;
+    hipStream_t s = a->stream(), cs = a->copyStream;
+    for (auto &e : F.ev)
+        if (!e) HIPCHK(hipEventCreate(&e));
+    F.ran = false;
+    F.uploadMs = F.kernelMs = F.downloadMs = 0;
+    for (double &m : F.passMs) m = 0;
+    bool evUsed[3] = {false, false, false};
+    // 1. the text, its tiles' newline counts and their scan
+    const uint64_t nTiles = fqgpu::tiles(nBytes), textCap = fqgpu::textCapacity(nBytes);
+    const uint64_t needTiles[4] = {textCap, nTiles * 4 + 16, (nTiles + 1) * 8, samgpu::scanTiles(nTiles) * 8 + 16};
+    snapgpu_aligner::ExBuf *bufTiles[4] = {&F.text, &F.counts, &F.tileStart, &F.sums};
+    uint64_t need = 0;
+    for (int k = 0; k < 4; k++) need += growBytes(*bufTiles[k], needTiles[k]);
+    if (int rc = fqFits(need, "the text")) return rc;
+    for (int k = 0; k < 4; k++) HIPCHK(fqEnsure(a, *bufTiles[k], needTiles[k]));
+    const char *text = (const char *)F.text.p;
+    char last = '\n';
+    auto t0 = clk::now();
+    if (int rc = fastqTextUpload(a, nBytes, fill, &last)) return rc;
+    F.uploadMs = ms(t0);
+    uint64_t nNl = 0;
+    if (nBytes) {
+        HIPCHK(hipEventRecord(F.ev[0], s));
+        fqgpu::countNewlines(text, nBytes, (uint32_t *)F.counts.p, s);
+        HIPCHK(hipEventRecord(F.ev[1], s));
+        samgpu::scanStarts((const uint32_t *)F.counts.p, nTiles, (uint64_t *)F.sums.p, (uint64_t *)F.tileStart.p, s);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(F.ev[2], s));
+        evUsed[0] = true;
+        HIPCHK(hipMemcpyAsync(&nNl, (const uint64_t *)F.tileStart.p + nTiles, 8, hipMemcpyDeviceToHost, s));
+        if (int rc = waitLane(a, a->lane[0])) return rc;
+    }
+    // records are the line quadruples; a last line without its newline counts
+    const uint64_t nLines = nNl + (nBytes && last != '\n' ? 1 : 0), n = nLines / 4;
+    if (n > 0xffffffffull) { snapgpu::setError("fastq_upload: batch too large"); return SNAPGPU_EINVAL; }
+    // 2. newline positions, the records' lengths and clips, the scans of base and id lengths
+    uint64_t total = 0, idTotal = 0;
+    fqgpu::Records R{};
+    if (n) {
+        const uint64_t needRec[7] = {nNl * 8 + 16, n * 20 + 16, (n + 1) * 8, (n + 1) * 8, samgpu::scanTiles(n) * 8 + 16,
+                                     samgpu::scanTiles(n) * 8 + 16, sizeof(fqgpu::Totals)};
+        snapgpu_aligner::ExBuf *bufRec[7] = {&F.nl, &F.rec, &F.baseStart, &F.idStart, &F.sums, &F.sums2, &F.tot};
+        need = 0;
+        for (int k = 0; k < 7; k++) need += growBytes(*bufRec[k], needRec[k]);
+        if (int rc = fqFits(need, "the line and record arrays")) return rc;
+        for (int k = 0; k < 7; k++) HIPCHK(fqEnsure(a, *bufRec[k], needRec[k]));
+        uint32_t *rec = (uint32_t *)F.rec.p;
+        R = fqgpu::Records{rec, rec + n, rec + 2 * n, rec + 3 * n, rec + 4 * n};
+        auto *tot = (fqgpu::Totals *)F.tot.p;
+        HIPCHK(hipEventRecord(F.ev[3], s));
+        HIPCHK(hipMemsetAsync(&tot->firstBad, 0xff, 8, s));
+        HIPCHK(hipMemsetAsync(&tot->baseBytes, 0, 8, s));
+        fqgpu::lineStarts(text, nBytes, (const uint64_t *)F.tileStart.p, (uint64_t *)F.nl.p, nNl, s);
+        HIPCHK(hipEventRecord(F.ev[4], s));
+        fqgpu::records(text, nBytes, (const uint64_t *)F.nl.p, nNl, n, clipping, R, tot, s);
+        HIPCHK(hipEventRecord(F.ev[5], s));
+        samgpu::scanStarts(R.baseLen, n, (uint64_t *)F.sums.p, (uint64_t *)F.baseStart.p, s);
+        samgpu::scanStarts(R.idLen, n, (uint64_t *)F.sums2.p, (uint64_t *)F.idStart.p, s);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(F.ev[6], s));
+        evUsed[1] = true;
+        fqgpu::Totals hTot{};
+        HIPCHK(hipMemcpyAsync(&hTot, tot, sizeof hTot, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(&total, (const uint64_t *)F.baseStart.p + n, 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(&idTotal, (const uint64_t *)F.idStart.p + n, 8, hipMemcpyDeviceToHost, s));
+        if (int rc = waitLane(a, a->lane[0])) return rc;
+        if (hTot.firstBad < n) {
+            snapgpu::setError(std::string("FASTQ record without '@' header in ") + name);
+            return SNAPGPU_EFORMAT;
+        }
+        if (hTot.baseBytes != total) {
+            char msg[160];
+            snprintf(msg, sizeof msg, "fastq_upload: the record pass counted %llu base bytes, the scan placed %llu",
+                     (unsigned long long)hTot.baseBytes, (unsigned long long)total);
+            snapgpu::setError(msg);
+            return SNAPGPU_EDEVICE;
+        }
+    }
+    // 3. the resident batch (snapgpu_reads_upload's buffers) and the copy pass into it
+    const uint64_t dBytes[7] = {total + 64, total + 64, (n + 1) * 8, (n + 1) * 4, (n + 1) * sizeof(snapgpu_result_t),
+                                3 * (n + 1) * sizeof(uint32_t), (n + 8) * SEEDS_PER_READ * sizeof(SeedRec)};
+    need = growBytes(F.ids, idTotal + 16);
+    for (uint64_t b : dBytes) need += b;
+    if (int rc = fqFits(need, "the resident batch")) return rc;
+    HIPCHK(fqEnsure(a, F.ids, idTotal + 16));
+    d = new snapgpu_device_reads_t();
+    d->owner = a;
+    d->n = n;
+    d->device = a->device;
+    HIPCHK(hipMalloc(&d->dBases, dBytes[0]));
+    HIPCHK(hipMalloc(&d->dQuals, dBytes[1]));
+    HIPCHK(hipMalloc(&d->dOffsets, dBytes[2]));
+    HIPCHK(hipMalloc(&d->dLengths, dBytes[3]));
+    HIPCHK(hipMalloc(&d->dOut, dBytes[4]));
+    HIPCHK(hipMalloc(&d->dDefer, dBytes[5]));   // pass-1 / pass-2 defers, arena overflows
+    HIPCHK(hipMalloc(&d->dSeeds, dBytes[6]));
+    if (n) {
+        HIPCHK(hipEventRecord(F.ev[7], s));
+        fqgpu::pack(text, nBytes, (const uint64_t *)F.nl.p, nNl, n, R, (const uint64_t *)F.baseStart.p,
+                    (const uint64_t *)F.idStart.p, d->dBases, d->dQuals, (char *)F.ids.p, d->dOffsets, d->dLengths, s);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(F.ev[8], s));
+        evUsed[2] = true;
+        if (int rc = waitLane(a, a->lane[0])) return rc;
+    }
+    // 4. offsets and lengths always come back (the extent hash is a sequential chain); the batch on request
+    t0 = clk::now();
+    std::vector<uint64_t> tmpOff;
+    std::vector<uint32_t> tmpLen;
+    uint64_t *hOff;
+    uint32_t *hLen;
+    if (hostBatch) {
+        r = snapgpu::allocReads(n, total, false, /*zero=*/false);
+        r->ids = new char[idTotal + 1]();
+        r->idOffsets = new uint64_t[n + 1]();
+        r->idLengths = new uint32_t[n + 1]();
+        if (clipping) {
+            r->frontClipped = new uint32_t[n + 1]();
+            r->unclippedLength = new uint32_t[n + 1]();
+        }
+        r->clipping = clipping;
+        r->nUploads = 1;
+        hOff = r->offsets;
+        hLen = r->lengths;
+        if (total) {
+            HIPCHK(hipMemcpyAsync(r->bases, d->dBases, total, hipMemcpyDeviceToHost, cs));
+            HIPCHK(hipMemcpyAsync(r->quals, d->dQuals, total, hipMemcpyDeviceToHost, cs));
+        }
+        memset(r->bases + total, 0, 64);   // the batch's zero slack
+        memset(r->quals + total, 0, 64);
+        if (idTotal) HIPCHK(hipMemcpyAsync(r->ids, F.ids.p, idTotal, hipMemcpyDeviceToHost, cs));
+        if (n) {
+            HIPCHK(hipMemcpyAsync(r->idOffsets, F.idStart.p, n * 8, hipMemcpyDeviceToHost, cs));
+            HIPCHK(hipMemcpyAsync(r->idLengths, R.idLen, n * 4, hipMemcpyDeviceToHost, cs));
+            if (clipping) {
+                HIPCHK(hipMemcpyAsync(r->frontClipped, R.front, n * 4, hipMemcpyDeviceToHost, cs));
+                HIPCHK(hipMemcpyAsync(r->unclippedLength, R.baseLen, n * 4, hipMemcpyDeviceToHost, cs));
+            }
+        }
+    } else {
+        tmpOff.resize(n + 1);
+        tmpLen.resize(n + 1);
+        hOff = tmpOff.data();
+        hLen = tmpLen.data();
+    }
+    if (n) {
+        HIPCHK(hipMemcpyAsync(hOff, d->dOffsets, n * 8, hipMemcpyDeviceToHost, cs));
+        HIPCHK(hipMemcpyAsync(hLen, d->dLengths, n * 4, hipMemcpyDeviceToHost, cs));
+    }
+    HIPCHK(hipStreamSynchronize(cs));
+    uint64_t bytes = 0;
+    for (uint64_t i = 0; i < n; i++) {   // as snapgpu_reads_upload
+        const uint64_t endb = hOff[i] + hLen[i];
+        if (endb > bytes) bytes = endb;
+        if (hLen[i] > d->maxLen) d->maxLen = hLen[i];
+        d->extentHash = extentMix(d->extentHash, hOff[i], hLen[i]);
+    }
+    if (bytes > total) { snapgpu::setError("fastq_upload: a clipped read ends past the batch"); return SNAPGPU_EDEVICE; }
+    d->bytes = bytes;
+    // zero from the largest clipped end on, as an upload of the clipped batch leaves it
+    HIPCHK(hipMemsetAsync(d->dBases + bytes, 0, total + 64 - bytes, cs));
+    HIPCHK(hipMemsetAsync(d->dQuals + bytes, 0, total + 64 - bytes, cs));
+    HIPCHK(hipStreamSynchronize(cs));
+    F.downloadMs = ms(t0);
+    static const int kFirst[3] = {0, 3, 7}, kCount[3] = {2, 3, 1};   // the event groups and their intervals
+    for (int k = 0, slot = 0; k < 3; slot += kCount[k], k++)
+        if (evUsed[k])
+            for (int j = 0; j < kCount[k]; j++) {
+                float f = 0;
+                HIPCHK(hipEventElapsedTime(&f, F.ev[kFirst[k] + j], F.ev[kFirst[k] + j + 1]));
+                F.passMs[slot + j] = f;
+                F.kernelMs += f;
+            }
+    F.ran = true;
+    return SNAPGPU_OK;
+}
+
+int fastqUpload(snapgpu_aligner_t *a, uint64_t nBytes, const FastqFill &fill, const char *name, int clipping,
+                uint32_t flags, snapgpu_device_reads_t **dOut, snapgpu_reads_t **readsOut) {
+    if (dOut) *dOut = nullptr;
+    if (readsOut) *readsOut = nullptr;
+    const bool hostBatch = flags & SNAPGPU_FASTQ_HOST_BATCH;
+    if (!a || !dOut || !name || (hostBatch && !readsOut) || clipping < 0 || clipping > 3 ||
+        (flags & ~SNAPGPU_FASTQ_HOST_BATCH)) {
+        snapgpu::setError("fastq_upload: bad argument");
+        return SNAPGPU_EINVAL;
+    }
+    if (a->failed) { snapgpu::setError("aligner failed earlier (device timeout)"); return SNAPGPU_EDEVICE; }
+    HIPCHK(hipSetDevice(a->device));
+    snapgpu_device_reads_t *d = nullptr;
+    snapgpu_reads_t *r = nullptr;
+    const int rc = fastqRun(a, nBytes, fill, name, clipping, hostBatch, d, r);
+    if (rc != SNAPGPU_OK) {
+        snapgpu_device_reads_free(d);
+        snapgpu_reads_free(r);
+        return rc;
+    }
+    *dOut = d;
+    if (hostBatch) *readsOut = r;
+    return SNAPGPU_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int snapgpu_fastq_upload(snapgpu_aligner_t *a, const char *text, uint64_t nBytes, const char *name, int clipping,
+                         uint32_t flags, snapgpu_device_reads_t **dOut, snapgpu_reads_t **readsOut) {
+    if (!text && nBytes) {
+        if (dOut) *dOut = nullptr;
+        if (readsOut) *readsOut = nullptr;
+        snapgpu::setError("fastq_upload: bad argument");
+        return SNAPGPU_EINVAL;
+    }
+    const FastqFill fill = [text](char *dst, uint64_t off, uint64_t m) {
+        fastqParallel(m, [=](uint64_t b, uint64_t e) { memcpy(dst + b, text + off + b, e - b); });
+        return true;
+    };
+    return fastqUpload(a, nBytes, fill, name, clipping, flags, dOut, readsOut);
+}
+
+int snapgpu_fastq_upload_file(snapgpu_aligner_t *a, const char *path, int clipping, uint32_t flags,
+                              snapgpu_device_reads_t **dOut, snapgpu_reads_t **readsOut) {
+    if (dOut) *dOut = nullptr;
+    if (readsOut) *readsOut = nullptr;
+    if (!path) { snapgpu::setError("fastq_upload: bad argument"); return SNAPGPU_EINVAL; }
+    const int fd = open(path, O_RDONLY);
+    if (fd < 0) { snapgpu::setError(std::string("cannot open ") + path); return SNAPGPU_EIO; }
+    struct stat sb;
+    if (fstat(fd, &sb) != 0) { close(fd); snapgpu::setError(std::string("cannot stat ") + path); return SNAPGPU_EIO; }
+    // the file goes straight into the staging chunks: one host pass over its bytes
+    const FastqFill fill = [fd, path](char *dst, uint64_t off, uint64_t m) {
+        std::atomic<bool> ok{true};
+        fastqParallel(m, [&, dst, off](uint64_t b, uint64_t e) {
+            while (b < e) {
+                const ssize_t got = pread(fd, dst + b, e - b, (off_t)(off + b));
+                if (got <= 0) { ok = false; return; }
+                b += (uint64_t)got;
+            }
+        });
+        if (!ok) snapgpu::setError(std::string("cannot read ") + path);
+        return ok.load();
+    };
+    const int rc = fastqUpload(a, (uint64_t)sb.st_size, fill, path, clipping, flags, dOut, readsOut);
+    close(fd);
+    return rc;
+}
+
+int snapgpu_fastq_last_ms(snapgpu_aligner_t *a, double *uploadMs, double *kernelMs, double *downloadMs) {
+    if (!a || !uploadMs || !kernelMs || !downloadMs) return SNAPGPU_EINVAL;
+    if (!a->fq.ran) { snapgpu::setError("fastq_last_ms: no device FASTQ parse on this aligner"); return SNAPGPU_EINVAL; }
+    *uploadMs = a->fq.uploadMs;
+    *kernelMs = a->fq.kernelMs;
+    *downloadMs = a->fq.downloadMs;
+    return SNAPGPU_OK;
+}
+
+uint32_t snapgpu_fastq_tile_bytes(void) { return fqgpu::kTileBytes; }
+
+// ms[0 .. 6): newline count, its scan, line starts, record pass, the two length scans, copy pass of the
+// last device FASTQ parse (tools/fastq_parse_time.py)
+int snapgpu_internal_fastq_pass_ms(snapgpu_aligner_t *a, double *ms) {
+    if (!a || !ms || !a->fq.ran) return SNAPGPU_EINVAL;
+    for (int k = 0; k < 6; k++) ms[k] = a->fq.passMs[k];
+    return SNAPGPU_OK;
+}
+
+int snapgpu_device_reads_peek(snapgpu_aligner_t *a, snapgpu_device_reads_t *d, uint64_t *n, uint64_t *bytes,
+                              uint32_t *maxLen, uint64_t *extentHash, uint64_t *offsets, uint32_t *lengths,
+                              char *bases, char *quals) {
+    if (!a || !d || d->owner != a) { snapgpu::setError("device_reads_peek: bad argument"); return SNAPGPU_EINVAL; }
+    if (a->failed) { snapgpu::setError("aligner failed earlier (device timeout)"); return SNAPGPU_EDEVICE; }
+    HIPCHK(hipSetDevice(a->device));
+    if (n) *n = d->n;
+    if (bytes) *bytes = d->bytes;
+    if (maxLen) *maxLen = d->maxLen;
+    if (extentHash) *extentHash = d->extentHash;
+    if (offsets && d->n) HIPCHK(hipMemcpy(offsets, d->dOffsets, d->n * 8, hipMemcpyDeviceToHost));
+    if (lengths && d->n) HIPCHK(hipMemcpy(lengths, d->dLengths, d->n * 4, hipMemcpyDeviceToHost));
+    if (bases) HIPCHK(hipMemcpy(bases, d->dBases, d->bytes + 64, hipMemcpyDeviceToHost));
+    if (quals) HIPCHK(hipMemcpy(quals, d->dQuals, d->bytes + 64, hipMemcpyDeviceToHost));
     return SNAPGPU_OK;
 }
 

@@ -32,6 +32,10 @@ unsigned hostThreads(unsigned cap);
 void *hostAlloc(size_t bytes, bool *pinned, bool zero = true);
 void hostFree(void *p, bool pinned);
 
+// reads.cpp: an empty batch of n reads over totalBytes (+ 64 of slack) of bases and qualities from
+// hostAlloc; zero = false leaves those bytes, slack included, to the caller
+snapgpu_reads_t *allocReads(uint64_t n, uint64_t totalBytes, bool truth, bool zero = true);
+
 // snapgpu_reads_t::hostFlags bit 2: a view of another batch's buffers (readsView), which it does not free
 constexpr uint32_t kReadsView = 4u;
 snapgpu_reads_t *readsView(const snapgpu_reads_t *parent, uint64_t n, const uint64_t *offsets, const uint32_t *lengths);

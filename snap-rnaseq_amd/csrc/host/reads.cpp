@@ -1,5 +1,6 @@
 // reads.cpp -- read batches: wgsim-like simulator, FASTQ in/out, caller arrays.
 #include "internal.h"
+#include "fastq_record.h"
 
 #include <fcntl.h>
 #include <sys/mman.h>
@@ -15,9 +16,9 @@
 
 using namespace snapgpu;
 
-namespace {
+namespace snapgpu {
 
-snapgpu_reads_t *allocReads(uint64_t n, uint64_t totalBytes, bool truth, bool zero = true) {
+snapgpu_reads_t *allocReads(uint64_t n, uint64_t totalBytes, bool truth, bool zero) {
     auto *r = new snapgpu_reads_t();
     r->n = n;
     r->totalBytes = totalBytes;
@@ -31,6 +32,10 @@ snapgpu_reads_t *allocReads(uint64_t n, uint64_t totalBytes, bool truth, bool ze
     r->truthDirection = truth ? new uint8_t[n + 1]() : nullptr;
     return r;
 }
+
+}  // namespace snapgpu
+
+namespace {
 
 inline char complement(char c) {
     switch (c) { case 'A': return 'T'; case 'C': return 'G'; case 'G': return 'C'; case 'T': return 'A'; default: return 'N'; }
@@ -278,29 +283,17 @@ snapgpu_reads_t *readsView(const snapgpu_reads_t *parent, uint64_t n, const uint
 
 extern "C" {
 
-snapgpu_reads_t *snapgpu_reads_from_fastq(const char *path) {
+snapgpu_reads_t *snapgpu_reads_from_fastq_buffer(const char *text, uint64_t nBytes, const char *name) {
     // FASTQReader::getNextRead (FASTQ.cpp:196-253): 4-line records, id = header line without
     // '@' (trailing CR/LF removed), bases, '+' line, qualities (a quality line shorter than the
     // bases leaves NUL bytes: SAM's %.*s then ends early, as the reference's would).  A trailing
-    // partial record is ignored.  The file is mapped and parsed in parallel (this rank's host thread
-    // budget): the newline positions per byte range, then per record its lengths, prefix sums,
-    // and the copies into the batch -- 1M 100-bp reads: 306 ms with one thread and per-line strings.
-    const int fd = open(path, O_RDONLY);
-    if (fd < 0) { setError(std::string("cannot open ") + path); return nullptr; }
-    struct stat sb;
-    if (fstat(fd, &sb) != 0) { close(fd); setError(std::string("cannot stat ") + path); return nullptr; }
-    const uint64_t size = (uint64_t)sb.st_size;
-    const char *base = nullptr;
-    if (size) {
-        void *m = mmap(nullptr, size, PROT_READ, MAP_PRIVATE, fd, 0);
-        if (m == MAP_FAILED) { close(fd); setError(std::string("cannot map ") + path); return nullptr; }
-        base = (const char *)m;
-    }
-    close(fd);
-    struct Unmap {
-        const char *p; uint64_t n;
-        ~Unmap() { if (p) munmap(const_cast<char *>(p), n); }
-    } unmap{base, size};
+    // partial record is ignored.  The text is parsed in parallel (this rank's host thread
+    // budget): the newline positions per byte range, then per record its lengths (fastq_record.h),
+    // prefix sums, and the copies into the batch -- 1M 100-bp reads: 306 ms with one thread and
+    // per-line strings.
+    if ((!text && nBytes) || !name) { setError("reads_from_fastq_buffer: null argument"); return nullptr; }
+    const char *base = text;
+    const uint64_t size = nBytes;
     const unsigned nt = size < (8u << 20) ? 1u : hostThreads(16);
     auto parallel = [&](uint64_t n, auto &&fn) {
         if (nt == 1 || n < 4096) { fn(0u, (uint64_t)0, n); return; }
@@ -330,30 +323,24 @@ snapgpu_reads_t *snapgpu_reads_from_fastq(const char *path) {
     const uint64_t nLines = nl.size() + ((nl.empty() ? size : size - nl.back() - 1) > 0 ? 1 : 0);
     if (nLines > nl.size()) nl.push_back(size);   // the last line, without its newline
     const uint64_t n = nLines / 4;
-    // line i: [start, end), cut at its first NUL byte (the C-string reading of FASTQReader's lines: a
-    // reader never hands the aligner a NUL inside a read) and without its trailing CR/LF bytes
-    auto line = [&](uint64_t i, uint64_t &b, uint64_t &e) {
-        b = i ? nl[i - 1] + 1 : 0;
-        e = nl[i];
-        if (const char *z = (const char *)memchr(base + b, 0, e - b)) e = (uint64_t)(z - base);
-        while (e > b && (base[e - 1] == '\r' || base[e - 1] == '\n')) e--;
-    };
+    // record r's trimmed lines (fastq_record.h): line i is [lineStart(i), lineEnd(i))
+    const fastqrec::Serial one;
+    auto lineStart = [&](uint64_t i) { return i ? nl[i - 1] + 1 : (uint64_t)0; };
+    auto lineEnd = [&](uint64_t i) { return nl[i]; };
+    auto record = [&](uint64_t r) { return fastqrec::record(base, r, lineStart, lineEnd, one); };
     std::vector<uint32_t> blen(n + 1, 0), qlen(n + 1, 0), ilen(n + 1, 0);
     std::vector<uint64_t> badAt(nt, n);
     parallel(n, [&](unsigned t, uint64_t a, uint64_t z) {
         for (uint64_t r = a; r < z; r++) {
-            uint64_t b, e;
-            line(4 * r, b, e);
-            if (e == b || base[b] != '@') { badAt[t] = std::min(badAt[t], r); break; }
-            ilen[r] = (uint32_t)(e - b - 1);
-            line(4 * r + 1, b, e);
-            blen[r] = (uint32_t)(e - b);
-            line(4 * r + 3, b, e);
-            qlen[r] = (uint32_t)(e - b);
+            const fastqrec::Record R = record(r);
+            if (R.bad) { badAt[t] = std::min(badAt[t], r); break; }
+            ilen[r] = R.idLen;
+            blen[r] = R.baseLen;
+            qlen[r] = R.qualLen;
         }
     });
     if (*std::min_element(badAt.begin(), badAt.end()) < n) {
-        setError(std::string("FASTQ record without '@' header in ") + path);
+        setError(std::string("FASTQ record without '@' header in ") + name);
         return nullptr;
     }
     uint64_t total = 0, idTotal = 0;
@@ -372,20 +359,38 @@ snapgpu_reads_t *snapgpu_reads_from_fastq(const char *path) {
     }
     parallel(n, [&](unsigned, uint64_t a, uint64_t z) {
         for (uint64_t r = a; r < z; r++) {
-            uint64_t b, e;
-            line(4 * r, b, e);
-            memcpy(rd->ids + rd->idOffsets[r], base + b + 1, ilen[r]);
-            line(4 * r + 1, b, e);
-            memcpy(rd->bases + rd->offsets[r], base + b, blen[r]);
-            line(4 * r + 3, b, e);
-            const uint32_t nq = std::min(qlen[r], blen[r]);
-            memcpy(rd->quals + rd->offsets[r], base + b, nq);
-            if (nq < blen[r]) memset(rd->quals + rd->offsets[r] + nq, 0, blen[r] - nq);
+            const fastqrec::Record R = record(r);
+            memcpy(rd->ids + rd->idOffsets[r], base + R.idAt, R.idLen);
+            memcpy(rd->bases + rd->offsets[r], base + R.baseAt, R.baseLen);
+            const uint32_t nq = std::min(R.qualLen, R.baseLen);
+            memcpy(rd->quals + rd->offsets[r], base + R.qualAt, nq);
+            if (nq < R.baseLen) memset(rd->quals + rd->offsets[r] + nq, 0, R.baseLen - nq);
         }
     });
     memset(rd->bases + total, 0, 64);   // the batch's zero slack
     memset(rd->quals + total, 0, 64);
     return rd;
+}
+
+snapgpu_reads_t *snapgpu_reads_from_fastq(const char *path) {
+    // the file, mapped, through snapgpu_reads_from_fastq_buffer
+    const int fd = open(path, O_RDONLY);
+    if (fd < 0) { setError(std::string("cannot open ") + path); return nullptr; }
+    struct stat sb;
+    if (fstat(fd, &sb) != 0) { close(fd); setError(std::string("cannot stat ") + path); return nullptr; }
+    const uint64_t size = (uint64_t)sb.st_size;
+    const char *base = nullptr;
+    if (size) {
+        void *m = mmap(nullptr, size, PROT_READ, MAP_PRIVATE, fd, 0);
+        if (m == MAP_FAILED) { close(fd); setError(std::string("cannot map ") + path); return nullptr; }
+        base = (const char *)m;
+    }
+    close(fd);
+    struct Unmap {
+        const char *p; uint64_t n;
+        ~Unmap() { if (p) munmap(const_cast<char *>(p), n); }
+    } unmap{base, size};
+    return snapgpu_reads_from_fastq_buffer(base, size, path);
 }
 
 int snapgpu_reads_write_fastq(const snapgpu_reads_t *r, const char *path) {

@@ -7,6 +7,7 @@
 // are formatted in parallel chunks and concatenated in read order.
 #include "internal.h"
 #include "sam_line.h"
+#include "fastq_record.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -477,13 +478,8 @@ extern "C" int snapgpu_reads_clip(snapgpu_reads_t *r, int clipping, uint32_t *fr
             r->offsets[i] -= r->frontClipped[i];
             const uint32_t full = r->unclippedLength[i];
             const char *q = r->quals + r->offsets[i];
-            uint32_t len = full, front = 0;
-            if (clipping == 2 || clipping == 3)   // ClipBack / ClipFrontAndBack
-                while (len > 0 && q[len - 1] == '#') len--;
-            if (clipping == 1 || clipping == 3)   // ClipFront / ClipFrontAndBack
-                while (front < len && q[front] == '#') front++;
-            if (len - front < 50) { len = full; front = 0; }   // "just use all of it" (Read.h:393-397)
-            else len -= front;
+            uint32_t len, front;
+            fastqrec::clip([q](uint64_t k) { return q[k]; }, full, clipping, front, len, fastqrec::Serial());
             r->frontClipped[i] = front;
             r->offsets[i] += front;
             r->lengths[i] = len;

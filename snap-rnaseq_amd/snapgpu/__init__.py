@@ -7,6 +7,7 @@ host C++, alignment is HIP on gfx950.  There is no CPU fallback -- creating a
 BaseAligner without a GPU raises.
 """
 import ctypes as C
+import os
 import time
 
 import numpy as np
@@ -73,7 +74,7 @@ class SnapGpuError(RuntimeError):
 
 _PTR_CALLS = ("genome_from_fasta", "genome_synthetic", "index_build", "index_load", "index_attach", "gtf_load",
               "reads_synthetic",
-              "reads_from_fastq", "reads_from_arrays", "aligner_create", "reads_upload", "paired_aligner_create",
+              "reads_from_fastq", "reads_from_fastq_buffer", "reads_from_arrays", "aligner_create", "reads_upload", "paired_aligner_create",
               "contaminants_create")
 
 
@@ -261,6 +262,14 @@ class Reads:
     @classmethod
     def from_fastq(cls, path):
         return cls(_check(lib().snapgpu_reads_from_fastq(str(path).encode()), "reads_from_fastq"))
+
+    @classmethod
+    def from_fastq_bytes(cls, data, name="<memory>"):
+        """snapgpu_reads_from_fastq_buffer: the host parser over FASTQ text in memory (name only
+        appears in error messages)."""
+        buf = np.frombuffer(bytes(data) + b"\0", dtype=np.uint8)   # at least one byte to point at
+        return cls(_check(lib().snapgpu_reads_from_fastq_buffer(buf.ctypes.data, len(buf) - 1, str(name).encode()),
+                          "reads_from_fastq_buffer"))
 
     @classmethod
     def from_list(cls, reads):
@@ -581,6 +590,30 @@ class BaseAligner:
     def upload(self, reads):
         return DeviceReads(self, reads)
 
+    def upload_fastq(self, path_or_bytes, clipping=0, host_batch=True, name="<memory>"):
+        """FASTQ parsed on the device (snapgpu_fastq_upload / _file): the text (bytes) or the file
+        (a path) is uploaded, and split, clipped and packed in device memory -> DeviceReads, as
+        upload() of the host parser's batch clipped at `clipping` would give.  Its .reads is that
+        host batch (a Reads), or None with host_batch=False."""
+        d, r = C.c_void_p(), C.POINTER(_ffi.Reads)()
+        flags = FASTQ_HOST_BATCH if host_batch else 0
+        rp = C.byref(r) if host_batch else None
+        if isinstance(path_or_bytes, (bytes, bytearray, memoryview)):
+            buf = np.frombuffer(bytes(path_or_bytes) + b"\0", dtype=np.uint8)
+            rc = lib().snapgpu_fastq_upload(self._h, buf.ctypes.data, len(buf) - 1, str(name).encode(), int(clipping),
+                                            flags, C.byref(d), rp)
+        else:
+            rc = lib().snapgpu_fastq_upload_file(self._h, os.fspath(path_or_bytes).encode(), int(clipping), flags,
+                                                 C.byref(d), rp)
+        _check(rc, "fastq_upload")
+        return DeviceReads(self, Reads(r) if host_batch else None, handle=d.value)
+
+    def fastq_last_ms(self):
+        """(text upload ms, kernel ms, download ms) of the last upload_fastq (snapgpu_fastq_last_ms)."""
+        u, k, d = C.c_double(), C.c_double(), C.c_double()
+        _check(lib().snapgpu_fastq_last_ms(self._h, C.byref(u), C.byref(k), C.byref(d)), "fastq_last_ms")
+        return u.value, k.value, d.value
+
     def timing(self):
         t = _ffi.Timing()
         lib().snapgpu_last_timing(self._h, C.byref(t))
@@ -714,10 +747,34 @@ def characterize_seeds(aligner, reads, read_list=None, **kw):
 
 
 class DeviceReads:
-    def __init__(self, aligner, reads):
+    def __init__(self, aligner, reads, handle=None):
+        """Uploads `reads`; or, with `handle`, adopts a resident batch that already exists
+        (BaseAligner.upload_fastq: reads is then its host batch, or None)."""
         self.aligner = aligner
-        self.n = reads.n
-        self._h = _check(lib().snapgpu_reads_upload(aligner._h, reads._p), "reads_upload")
+        self.reads = reads
+        if handle is None:
+            self.n = reads.n
+            self._h = _check(lib().snapgpu_reads_upload(aligner._h, reads._p), "reads_upload")
+        else:
+            self._h = handle
+            self.n = self.peek(arrays=False)["n"]
+
+    def peek(self, arrays=True):
+        """The resident batch as the device holds it (snapgpu_device_reads_peek; for the tests) ->
+        dict of n, bytes, maxLen, extentHash and, with arrays, offsets, lengths, bases and quals
+        (bytes + 64 each)."""
+        n, nb, ml, eh = C.c_uint64(), C.c_uint64(), C.c_uint32(), C.c_uint64()
+        fn = lib().snapgpu_device_reads_peek
+        _check(fn(self.aligner._h, self._h, C.byref(n), C.byref(nb), C.byref(ml), C.byref(eh), None, None, None, None),
+               "device_reads_peek")
+        out = {"n": n.value, "bytes": nb.value, "maxLen": ml.value, "extentHash": eh.value}
+        if arrays:
+            off, ln = np.zeros(max(1, n.value), np.uint64), np.zeros(max(1, n.value), np.uint32)
+            b, q = np.zeros(nb.value + 64, np.uint8), np.zeros(nb.value + 64, np.uint8)
+            _check(fn(self.aligner._h, self._h, None, None, None, None, off.ctypes.data, ln.ctypes.data,
+                      b.ctypes.data, q.ctypes.data), "device_reads_peek")
+            out.update(offsets=off[:n.value], lengths=ln[:n.value], bases=b.tobytes(), quals=q.tobytes())
+        return out
 
     def run(self):
         """Launch the GPU passes (asynchronous)."""
@@ -849,6 +906,10 @@ class DeviceReads:
             lib().snapgpu_device_reads_free(self._h)
             self._h = None
 
+
+# the device FASTQ parser (include/snapgpu.h; csrc/fastq_parse.h: kTileBytes)
+FASTQ_HOST_BATCH = 1
+FASTQ_TILE_BYTES = 16384
 
 # the device SAM formatter's work split (csrc/sam_format.h: kRecsPerGroup, kScanTile)
 SAM_RECORDS_PER_WORKGROUP = 32

@@ -276,6 +276,7 @@ _PROTOS = [
     ("snapgpu_reads_synthetic_pairs", C.c_int, [C.c_void_p, C.POINTER(SynthReadsParams), C.c_uint32, C.c_uint32,
                                                 C.POINTER(C.POINTER(Reads)), C.POINTER(C.POINTER(Reads))]),
     ("snapgpu_reads_from_fastq", C.POINTER(Reads), [C.c_char_p]),
+    ("snapgpu_reads_from_fastq_buffer", C.POINTER(Reads), [C.c_void_p, C.c_uint64, C.c_char_p]),
     ("snapgpu_reads_from_arrays", C.POINTER(Reads), [C.c_uint64, C.c_char_p, C.c_char_p,
                                                      C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),
     ("snapgpu_reads_write_fastq", C.c_int, [C.POINTER(Reads), C.c_char_p]),
@@ -294,6 +295,16 @@ _PROTOS = [
     ("snapgpu_align_resident", C.c_int, [C.c_void_p, C.c_void_p]),
     ("snapgpu_results_download", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Result)]),
     ("snapgpu_synchronize", C.c_int, [C.c_void_p]),
+    ("snapgpu_fastq_upload", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_char_p, C.c_int, C.c_uint32,
+                                       C.POINTER(C.c_void_p), C.POINTER(C.POINTER(Reads))]),
+    ("snapgpu_fastq_upload_file", C.c_int, [C.c_void_p, C.c_char_p, C.c_int, C.c_uint32,
+                                            C.POINTER(C.c_void_p), C.POINTER(C.POINTER(Reads))]),
+    ("snapgpu_fastq_last_ms", C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                        C.POINTER(C.c_double)]),
+    ("snapgpu_fastq_tile_bytes", C.c_uint32, []),
+    ("snapgpu_device_reads_peek", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                            C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_void_p]),
     ("snapgpu_last_timing", C.c_int, [C.c_void_p, C.POINTER(Timing)]),
     ("snapgpu_aligner_get_stats", C.c_int, [C.c_void_p, C.POINTER(AlignerStats)]),
     ("snapgpu_aligner_max_k", C.c_int, [C.c_void_p]),
