@@ -370,7 +370,8 @@ int snapgpu_device_reads_peek(snapgpu_aligner_t *a, snapgpu_device_reads_t *d, u
  * snapgpu_align_resident / snapgpu_align_batch call.  snapgpu_align_batch pipelines its reads
  * in chunks over two streams: the kernel figures are then sums over its nLaunches chunks. */
 typedef struct snapgpu_timing {
-    double mainKernelMs;     /* pass 1: align_kernel<128> (reads <= 128 bases, bit-plane LV) */
+    double mainKernelMs;     /* the simple pass (front stream) + pass 1: align_kernel<128> (reads <= 128
+                                bases, bit-plane LV) on the lane; the wait between the two is left out */
     double spillKernelMs;    /* passes 2 + 3: align_kernel<256> over the reads pass 1 deferred
                                 (129..256 bases, bit-plane LV), align_kernel<512> over the rest */
     double fixupMs;          /* host MAPQ fix-ups */
@@ -382,7 +383,8 @@ typedef struct snapgpu_timing {
     uint64_t lookupOverflowReads; /* overflow-list counts it read */
     uint64_t nLaunches;      /* pass sets the figures above sum over (chunks of snapgpu_align_batch) */
     double wallMs;           /* snapgpu_align_batch: host reads in -> records out, whole call */
-    double mainKernelBusyMs; /* union of the pass-1 launch intervals (launches of the two lanes overlap) */
+    double mainKernelBusyMs; /* union of the simple-pass and pass-1 launch intervals (the two lanes' launches
+                                and the front stream's overlap) */
     double lookupKernelBusyMs;/* union of the pass-0 launch intervals */
     uint64_t nByteReads;     /* reads deferred by pass 2 to the byte-compare pass 3 (> 256 bases,
                                 or IUPAC codes in both read and genome) */
@@ -417,7 +419,9 @@ int snapgpu_aligner_get_stats(const snapgpu_aligner_t *a, snapgpu_aligner_stats_
 int snapgpu_aligner_max_k(const snapgpu_aligner_t *a);           /* getMaxK() */
 /* Whether the pass sets of the aligner's two streams may run concurrently (default 1; the
  * environment variable SNAPGPU_OVERLAP sets the initial value).  0 serialises the kernels
- * (copies and host work still overlap them): each launch's duration is then its own. */
+ * (copies and host work still overlap them): each launch's duration is then its own.  The front
+ * stage of a pass set (record pre-fill, pass 0, the simple pass) runs on a third stream ahead of the
+ * lanes; serialised, it waits for the previous set's last pass too. */
 int snapgpu_aligner_set_overlap(snapgpu_aligner_t *a, int overlap);
 /* Whether the simple pass runs ahead of pass 1 (default 1; SNAPGPU_SIMPLE_PASS sets the initial
  * value).  It never runs with stopOnFirstHit, explorePopularSeeds, maxHitsToConsider >= 0xffff, a

@@ -1105,19 +1105,25 @@ int hostMapq(double pAll, double pBest, int score, int popular) {   // mapq.h:32
 
 }  // namespace
 
-// One execution lane = one HIP stream with everything a pass set needs to run beside the
-// other lane: its own element arenas (persistent waves index them by blockIdx), work
-// counters, lookup statistics and timing events.  Lane 0 serves the resident API
-// (snapgpu_reads_upload / snapgpu_align_resident); snapgpu_align_batch alternates chunks
-// over both lanes so one chunk's copies and host tail overlap the other chunk's kernels,
-// and the second lane's kernel fills the first one's tail.
-// One chunk's input/output staging of the pipelined snapgpu_align_batch.  Two per lane: the
-// H2D of a lane's next chunk (on the aligner's copy stream) runs while the lane's current chunk
-// is still in its kernels, so the lane's next kernel can start the moment the current one ends.
+// One execution lane = one HIP stream with what the align passes of a pass set need to run
+// beside the other lane: its own element arenas (persistent waves index them by blockIdx) and
+// lookup statistics.  Lane 0 serves the resident API (snapgpu_reads_upload /
+// snapgpu_align_resident); snapgpu_align_batch alternates chunks over both lanes so one chunk's
+// copies and host tail overlap the other chunk's kernels, and the second lane's align kernel
+// fills the first one's tail.  The front stage of every pass set (counter clear, record
+// pre-fill, pass 0, order_long_kernel, the simple pass) runs on the aligner's one front stream,
+// a chunk or two ahead of the lanes; it writes only per-chunk buffers (ChunkSlot, EvSet).
+// One chunk's input/output staging of the pipelined snapgpu_align_batch and the buffers its
+// front stage writes.  Two per lane: the H2D of a lane's next chunk (on the aligner's copy stream)
+// and its front stage run while the lane's current chunk is still in its align kernels, so the
+// lane's next align kernel can start the moment the current one frees wave slots.
 struct ChunkSlot {
     char *dBases = nullptr, *dQuals = nullptr;  // device inputs
     uint64_t *dOffsets = nullptr;
     uint32_t *dLengths = nullptr;
+    uint32_t *dDefer = nullptr;                 // pass-1 / pass-2 defers, arena overflows
+    snapgpu_result_t *dOut = nullptr;
+    SeedRec *dSeeds = nullptr;
     uint64_t *hOffsets = nullptr;               // pinned staging
     uint32_t *hLengths = nullptr;
     snapgpu_result_t *hOut = nullptr;
@@ -1132,24 +1138,26 @@ struct ExecLane {
     hipStream_t stream = nullptr;
     void *arena = nullptr;                     // main passes: arenaCap elements per wave
     void *bigArena = nullptr;                  // big-arena pass: arenaElems per wave (only when arenaCap < arenaElems)
-    uint32_t *counter = nullptr;               // [0] pass-1 work, [1] pass-3 work, [2] pass-1 defers, [3] pass-2 work,
-                                               // [4] pass-2 defers, [5] long reads (pass 0), [6] arena overflows,
-                                               // [7] big-arena pass work
     unsigned long long *lookupStats = nullptr; // seed_lookup_kernel: [256][4] seeds, probes, overflow counts (per call)
     hipEvent_t done = nullptr;                 // scratch event: waitLane, cross-lane ordering
     // chunk buffers of the pipelined snapgpu_align_batch (grown on demand)
     uint64_t capReads = 0, capBytes = 0;
-    uint32_t *dDefer = nullptr;
-    snapgpu_result_t *dOut = nullptr;
-    SeedRec *dSeeds = nullptr;
     ChunkSlot slot[2];
     uint32_t nextSlot = 0;
     unsigned long long *hLookupStats = nullptr; // pinned copy of lookupStats
 };
 
-// Timing events of one pass set (one chunk) and the pinned copy of its work counters.
+// Timing events of one pass set (one chunk), its device work counters and their pinned copy.
 struct EvSet {
-    hipEvent_t e[4] = {};   // 3: before pass 0, 0: before pass 1, 1: after pass 1, 2: after pass 2
+    // front stream: 3 before pass 0, 0 after pass 0 (and order_long_kernel), 4 after the simple
+    // pass (the lane stream waits for it); lane stream: 5 before pass 1, 1 after pass 1, 2 after
+    // passes 2 and 3
+    hipEvent_t e[6] = {};
+    // [0] pass-1 work, [1] pass-3 work, [2] pass-1 defers, [3] pass-2 work, [4] pass-2 defers,
+    // [5] long reads (pass 0), [6] arena overflows, [7] big-arena pass work, [8..9] simple pass work /
+    // bails, [10..11] forced-mode statistics, [12..13] simple pass reads / wide.  One per pass set:
+    // the front stage clears it while the lanes' align kernels still use the earlier sets' counters.
+    uint32_t *dCounter = nullptr;
     uint32_t *hCounter = nullptr;
 };
 
@@ -1247,6 +1255,13 @@ struct snapgpu_aligner {
     // host thread can run them while another thread's align call keeps the lanes busy (the RNA
     // paired path's sub-batch pipeline); a caller serialises them among themselves
     hipStream_t sideStream = nullptr;
+    // the front stage of every pass set, both lanes' (launch_passes): one stream, so the front
+    // stages run in submission order -- its small kernels take the wave slots a lane's persistent
+    // kernel frees in its tail without queueing behind the other lane's passes 2 / 3 and record copy
+    // (normal priority; SNAPGPU_FRONT_PRIORITY=1: the device's highest)
+    hipStream_t frontStream = nullptr;
+    hipEvent_t frontDone = nullptr;     // scratch event: waitFront, lane -> front ordering
+    uint32_t *dSink = nullptr;          // 64 B nobody reads (snapgpu_gather_peak's result sink)
     std::chrono::steady_clock::time_point streamStart;
     uint64_t arenaElems = 0;      // worst case per read: (maxSeeds + 2) * maxHits (+ 64)
     uint64_t arenaCap = 0;        // per wave in the main passes (= arenaElems unless that cannot fit the grid)
@@ -1698,6 +1713,14 @@ int waitLane(snapgpu_aligner_t *a, ExecLane &L) {
     return waitEvent(a, L.done);
 }
 
+// Wait for everything queued on the front stream (a front stage whose lane part was never queued
+// -- a launch that failed half way -- is waited for by nothing else).
+int waitFront(snapgpu_aligner_t *a) {
+    if (a->failed) return waitEvent(a, nullptr);
+    HIPCHK(hipEventRecord(a->frontDone, a->frontStream));
+    return waitEvent(a, a->frontDone);
+}
+
 }  // namespace
 
 namespace snapgpu {
@@ -1864,10 +1887,11 @@ static int buildBuckets(snapgpu_aligner_t *a, hipStream_t s0) {
     return rc;
 }
 
+// (The caller has waited for the lane and for the front stream: nothing is in flight on them.)
 static void freeLaneChunkBuffers(snapgpu_aligner_t *a, ExecLane &L) {
-    devFree(a, L.dDefer); devFree(a, L.dOut); devFree(a, L.dSeeds);
-    L.dDefer = nullptr; L.dOut = nullptr; L.dSeeds = nullptr;
     for (ChunkSlot &S : L.slot) {
+        devFree(a, S.dDefer); devFree(a, S.dOut); devFree(a, S.dSeeds);
+        S.dDefer = nullptr; S.dOut = nullptr; S.dSeeds = nullptr;
         devFree(a, S.dBases); devFree(a, S.dQuals); devFree(a, S.dOffsets); devFree(a, S.dLengths);
         S.dBases = S.dQuals = nullptr; S.dOffsets = nullptr; S.dLengths = nullptr;
         if (!a->failed) { hostPinnedFree(S.hOffsets); hostPinnedFree(S.hLengths); hostPinnedFree(S.hOut); }
@@ -1883,13 +1907,14 @@ void snapgpu_aligner_free(snapgpu_aligner_t *a) {
         return;
     }
     hipSetDevice(a->device);
+    if (a->frontStream) hipStreamSynchronize(a->frontStream);
     for (auto &L : a->lane) if (L.stream) hipStreamSynchronize(L.stream);
     devFree(a, a->dBuckets); devFree(a, a->dOverflow); devFree(a, a->dPieces);
     devFree(a, a->dBucketBase); devFree(a, a->dBucketCount); devFree(a, a->dGenomeAlloc); devFree(a, a->dTab);
     devFree(a, a->dGPlanes); devFree(a, a->dPhase); devFree(a, a->dDiag);
     for (auto &L : a->lane) {
         freeLaneChunkBuffers(a, L);
-        devFree(a, L.arena); devFree(a, L.bigArena); devFree(a, L.counter); devFree(a, L.lookupStats);
+        devFree(a, L.arena); devFree(a, L.bigArena); devFree(a, L.lookupStats);
         hostPinnedFree(L.hLookupStats);
         if (L.done) hipEventDestroy(L.done);
         for (ChunkSlot &S : L.slot) {
@@ -1900,8 +1925,12 @@ void snapgpu_aligner_free(snapgpu_aligner_t *a) {
     }
     if (a->copyStream) { hipStreamSynchronize(a->copyStream); hipStreamDestroy(a->copyStream); }
     if (a->sideStream) { hipStreamSynchronize(a->sideStream); hipStreamDestroy(a->sideStream); }
+    if (a->frontStream) hipStreamDestroy(a->frontStream);
+    if (a->frontDone) hipEventDestroy(a->frontDone);
+    devFree(a, a->dSink);
     for (auto &v : a->evs) {
         for (auto &e : v.e) if (e) hipEventDestroy(e);
+        devFree(a, v.dCounter);
         hostPinnedFree(v.hCounter);
     }
     for (auto &e : a->cev) if (e) hipEventDestroy(e);
@@ -1964,7 +1993,6 @@ snapgpu_aligner_t *snapgpu_aligner_create(int device, const snapgpu_index_t *idx
             if ((e = hipEventCreateWithFlags(&S.h2d, hipEventDisableTiming)) != hipSuccess ||
                 (e = hipEventCreateWithFlags(&S.done, hipEventDisableTiming)) != hipSuccess)
                 return fail("event", e);
-        if ((e = hipMalloc(&L.counter, 64)) != hipSuccess) return fail("counter", e);
         if ((e = hipMalloc(&L.lookupStats, 1024 * sizeof(unsigned long long))) != hipSuccess) return fail("lookup stats", e);
         if ((e = hipHostMalloc(&L.hLookupStats, 1024 * sizeof(unsigned long long), hipHostMallocDefault)) != hipSuccess)
             return fail("pinned lookup stats", e);
@@ -1979,6 +2007,17 @@ snapgpu_aligner_t *snapgpu_aligner_create(int device, const snapgpu_index_t *idx
         const bool high = !(t && atoi(t) == 0) && hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess;
         if ((e = high ? hipStreamCreateWithPriority(&a->sideStream, hipStreamNonBlocking, greatest)
                       : hipStreamCreateWithFlags(&a->sideStream, hipStreamNonBlocking)) != hipSuccess) return fail("stream", e);
+        // The front stream at normal priority (SNAPGPU_FRONT_PRIORITY=1: the highest, =0: normal).
+        // Measured both ways: at the highest priority a pass 0 that
+        // becomes ready while an align kernel is still placing its grid holds that launch back --
+        // the align kernel then runs for two chunks' time on part of its waves -- and the C2 line
+        // loses what the front stage gained; C3 comes out 1 % behind the parent instead of 3 % ahead.
+        const char *f = getenv("SNAPGPU_FRONT_PRIORITY");
+        const bool fhigh = f && atoi(f) != 0 && hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess;
+        if ((e = fhigh ? hipStreamCreateWithPriority(&a->frontStream, hipStreamNonBlocking, greatest)
+                       : hipStreamCreateWithFlags(&a->frontStream, hipStreamNonBlocking)) != hipSuccess) return fail("stream", e);
+        if ((e = hipEventCreateWithFlags(&a->frontDone, hipEventDisableTiming)) != hipSuccess) return fail("event", e);
+        if ((e = hipMalloc(&a->dSink, 64)) != hipSuccess) return fail("sink", e);
     }
     for (auto &ev : a->cev) if ((e = hipEventCreate(&ev)) != hipSuccess) return fail("event", e);
     if ((e = hipEventCreateWithFlags(&a->residentSideDone, hipEventDisableTiming)) != hipSuccess) return fail("event", e);
@@ -2179,14 +2218,24 @@ struct PassIO {
     uint32_t maxLen;    // longest read (or a bound): no long reads, no order_long_kernel
 };
 
-// Queue pass 0 (seed lookups), pass 1 (align_kernel<128>), pass 2 (align_kernel<256> over the
-// reads pass 1 deferred: 129..256 bases, bit planes) and pass 3 (align_kernel<512> over what
-// pass 2 deferred: longer reads and IUPAC-on-both-sides reads, byte compare) on lane `li`, with
-// HIP events around them.  The deferred counts stay on the device (each pass reads its list
-// length from the counter the previous one appended with).
+// Queue one pass set.  Its front stage -- counter clear, record pre-fill, pass 0 (seed lookups),
+// order_long_kernel, the simple pass -- goes onto the front stream, behind `inputs` (the event
+// after which the reads are on the device; null: they are) and the earlier sets' front stages.
+// Lane `li` waits for it and runs pass 1 (align_kernel<128>), pass 2 (align_kernel<256> over the
+// reads pass 1 deferred: 129..256 bases, bit planes), pass 3 (align_kernel<512> over what pass 2
+// deferred: longer reads and IUPAC-on-both-sides reads, byte compare) and the big-arena pass,
+// with HIP events around them.  The front stage touches io's buffers and ev's counters only, never
+// the lane's arenas: it runs while the lane's earlier set is still in its align kernels.  The
+// deferred counts stay on the device (each pass reads its list length from the counter the
+// previous one appended with).
 static int launch_passes(snapgpu_aligner_t *a, int li, const PassIO &io, const AlignExt &x, EvSet &ev,
-                         const EvSet *prev) {
+                         const EvSet *prev, hipEvent_t inputs = nullptr, bool front = true) {
     ExecLane &L = a->lane[li];
+    uint32_t *const cnt = ev.dCounter;
+    // front = false: the front stage on the lane's own stream, ahead of the lane's part (the resident
+    // path: its pass sets are all queued at once, and the first two front stages side by side on
+    // the idle device beat one front stream -- DESIGN.md section 5, round 15)
+    const hipStream_t fs = front ? a->frontStream : L.stream;
     if (io.n == 0) return SNAPGPU_OK;
     if (io.n > 0xffffffffull) { snapgpu::setError("batch too large"); return SNAPGPU_EINVAL; }
     KArgs A;
@@ -2207,10 +2256,10 @@ static int launch_passes(snapgpu_aligner_t *a, int li, const PassIO &io, const A
     A.tab = a->dTab;
     A.bases = io.bases; A.quals = io.quals; A.offsets = io.offsets; A.lengths = io.lengths;
     A.nReads = (uint32_t)io.n; A.out = io.out;
-    A.counter = L.counter; A.arena = L.arena; A.arenaElems = a->arenaCap;
-    if (a->arenaCap < a->arenaElems) { A.ovfList = io.ovf; A.ovfCount = L.counter + 6; }
-    A.deferList = io.defer; A.deferCount = L.counter + 2; A.readList = nullptr;
-    A.forcedStats = L.counter + 10;
+    A.counter = cnt; A.arena = L.arena; A.arenaElems = a->arenaCap;
+    if (a->arenaCap < a->arenaElems) { A.ovfList = io.ovf; A.ovfCount = cnt + 6; }
+    A.deferList = io.defer; A.deferCount = cnt + 2; A.readList = nullptr;
+    A.forcedStats = cnt + 10;
     A.search = x.search; A.maxHitsToGet = x.maxHitsToGet;
     A.hitSlot = x.maxHitsToGet < 512 ? x.maxHitsToGet : 512;
     A.hitStride = multiHitStride(x.maxHitsToGet);
@@ -2218,30 +2267,32 @@ static int launch_passes(snapgpu_aligner_t *a, int li, const PassIO &io, const A
     int grid = a->grid;
     if ((uint64_t)grid > io.n) grid = (int)io.n;
     (void)hipGetLastError();   // clear any stale error of an unrelated earlier runtime call
-    if (prev && !a->overlapKernels) HIPCHK(hipStreamWaitEvent(L.stream, prev->e[2], 0));
-    HIPCHK(hipMemsetAsync(L.counter, 0, 64, L.stream));
+    // SNAPGPU_OVERLAP=0: nothing of this set starts before the previous set's last pass has ended
+    if (prev && !a->overlapKernels) HIPCHK(hipStreamWaitEvent(fs, prev->e[2], 0));
+    if (inputs) HIPCHK(hipStreamWaitEvent(fs, inputs, 0));
+    HIPCHK(hipMemsetAsync(cnt, 0, 64, fs));
     // every record pre-filled with 0xff (result 0xff is no AlignmentResult): a read that no pass
     // writes -- lost in the routing between passes -- fails the call on the host (finishChunk /
     // finishRecords) instead of coming back as a stale or zeroed NotFound-looking record
-    HIPCHK(hipMemsetAsync(io.out, 0xff, io.n * sizeof(snapgpu_result_t), L.stream));
+    HIPCHK(hipMemsetAsync(io.out, 0xff, io.n * sizeof(snapgpu_result_t), fs));
     // pass 0: the first SEEDS_PER_READ seed lookups of every read (4 reads per 64-lane block); it also puts the
     // reads longer than 128 bases straight onto pass 2's list
     A.seedRecs = nullptr;
-    A.longCount = L.counter + 5;
+    A.longCount = cnt + 5;
     // longest-first: the long reads' order list is pass 2's defer list (free until pass 2 writes it)
     A.orderTmp = a->orderLong && io.n < (1ull << 28) ? io.defer2 : nullptr;
-    HIPCHK(hipEventRecord(ev.e[3], L.stream));
+    HIPCHK(hipEventRecord(ev.e[3], fs));
     hipLaunchKernelGGL(seed_lookup_kernel, dim3((unsigned)((io.n + 4 * LOOKUP_WAVES - 1) / (4 * LOOKUP_WAVES))),
-                       dim3(64 * LOOKUP_WAVES), 0, L.stream, A, io.seeds,
-                       L.lookupStats);
+                       dim3(64 * LOOKUP_WAVES), 0, fs, A, io.seeds,
+                       L.lookupStats);   // (per lane still; the front stages run one after the other)
     HIPCHK(hipGetLastError());
     if (A.orderTmp && io.maxLen > 128) {
-        hipLaunchKernelGGL(order_long_kernel, dim3(1), dim3(256), 0, L.stream, A.orderTmp, A.longCount, A.deferList);
+        hipLaunchKernelGGL(order_long_kernel, dim3(1), dim3(256), 0, fs, A.orderTmp, A.longCount, A.deferList);
         HIPCHK(hipGetLastError());
     }
     A.orderTmp = nullptr;
     A.seedRecs = reinterpret_cast<const uint4 *>(io.seeds);
-    HIPCHK(hipEventRecord(ev.e[0], L.stream));
+    HIPCHK(hipEventRecord(ev.e[0], fs));
     const bool ext = x.search || x.maxHitsToGet;
     // the simple pass (simple_align.h) takes the single-candidate reads; pass 1 then runs over the
     // list of the reads it left.  The list is pass 2's defer list: free from order_long_kernel's end
@@ -2249,47 +2300,61 @@ static int launch_passes(snapgpu_aligner_t *a, int li, const PassIO &io, const A
     if (a->simplePass && !ext && !A.stopOnFirst && !A.explore && A.maxHits >= 1 && A.maxHits < 0xffffu && A.seedRecs &&
         !A.phaseBuf) {
         KArgs Q = A;
-        Q.counter = L.counter + 8;
+        Q.counter = cnt + 8;
         int gridS = a->gridSimple;
         if ((uint64_t)gridS > io.n) gridS = (int)io.n;
         if ((uint64_t)gridS * SIMPLE_CHUNK > io.n) gridS = (int)((io.n + SIMPLE_CHUNK - 1) / SIMPLE_CHUNK);
-        hipLaunchKernelGGL(simple_align_kernel, dim3(gridS), dim3(64), 0, L.stream, Q, io.defer2, L.counter + 9,
-                           L.counter + 12, L.counter + 13);
+        hipLaunchKernelGGL(simple_align_kernel, dim3(gridS), dim3(64), 0, fs, Q, io.defer2, cnt + 9,
+                           cnt + 12, cnt + 13);
         HIPCHK(hipGetLastError());
-        A.readList = io.defer2; A.readCount = L.counter + 9;
+        A.readList = io.defer2; A.readCount = cnt + 9;
     }
+    // end of the front stage (with the simple pass off or on the ext path: pass 0 alone); the lane
+    // goes on from here
+    HIPCHK(hipEventRecord(ev.e[4], fs));
+    HIPCHK(hipStreamWaitEvent(L.stream, ev.e[4], 0));
+    HIPCHK(hipEventRecord(ev.e[5], L.stream));
     if (ext) hipLaunchKernelGGL((align_kernel<128, true>), dim3(grid), dim3(64), 0, L.stream, A);
     else hipLaunchKernelGGL((align_kernel<128, false>), dim3(grid), dim3(64), 0, L.stream, A);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(ev.e[1], L.stream));
     A.readList = nullptr; A.readCount = nullptr;
+    // Passes 2 and 3 are launched only when a read can reach them: pass 2's list holds the reads
+    // longer than 128 bases (pass 0) and, with IUPAC codes in the genome, what pass 1 defers; pass 3's
+    // holds pass 2's reads longer than 256 bases and its IUPAC defers.  A launch over an empty list
+    // does nothing, yet waits for wave slots behind the other lane's align kernel and holds the
+    // chunk's record copy back.
+    const bool pass2 = io.maxLen > 128 || idx->hasIupac;
+    const bool pass3 = pass2 && (io.maxLen > 256 || idx->hasIupac);
     // pass 2: reads of 129..256 bases (bit planes, 256-bit masks)
     KArgs M = A;
-    M.counter = L.counter + 3;
-    M.readList = io.defer; M.readCount = L.counter + 2;
-    M.deferList = io.defer2; M.deferCount = L.counter + 4;   // (M.seedRecs: pass 0's records, long reads too)
+    M.counter = cnt + 3;
+    M.readList = io.defer; M.readCount = cnt + 2;
+    M.deferList = io.defer2; M.deferCount = cnt + 4;   // (M.seedRecs: pass 0's records, long reads too)
     int grid256 = a->grid256;
     if ((uint64_t)grid256 > io.n) grid256 = (int)io.n;
-    if (ext) hipLaunchKernelGGL((align_kernel<256, true>), dim3(grid256), dim3(64), 0, L.stream, M);
+    if (!pass2) {}
+    else if (ext) hipLaunchKernelGGL((align_kernel<256, true>), dim3(grid256), dim3(64), 0, L.stream, M);
     else hipLaunchKernelGGL((align_kernel<256, false>), dim3(grid256), dim3(64), 0, L.stream, M);
     HIPCHK(hipGetLastError());
     // pass 3: reads longer than 256 bases or needing the byte-compare LV
     KArgs B = A;
-    B.counter = L.counter + 1;
-    B.readList = io.defer2; B.readCount = L.counter + 4;
+    B.counter = cnt + 1;
+    B.readList = io.defer2; B.readCount = cnt + 4;
     B.deferList = nullptr; B.deferCount = nullptr;
     B.seedRecs = nullptr;
     int grid2 = a->grid512;
     if ((uint64_t)grid2 > io.n) grid2 = (int)io.n;
-    if (ext) hipLaunchKernelGGL((align_kernel<512, true>), dim3(grid2), dim3(64), 0, L.stream, B);
+    if (!pass3) {}
+    else if (ext) hipLaunchKernelGGL((align_kernel<512, true>), dim3(grid2), dim3(64), 0, L.stream, B);
     else hipLaunchKernelGGL((align_kernel<512, false>), dim3(grid2), dim3(64), 0, L.stream, B);
     HIPCHK(hipGetLastError());
     if (a->gridBig) {
         // big-arena pass: the reads passes 1-3 abandoned when they outgrew a capped arena, aligned
         // from scratch by the byte-compare kernel (any read length) on worst-case arenas
         KArgs V = A;
-        V.counter = L.counter + 7;
-        V.readList = io.ovf; V.readCount = L.counter + 6;
+        V.counter = cnt + 7;
+        V.readList = io.ovf; V.readCount = cnt + 6;
         V.deferList = nullptr; V.deferCount = nullptr;
         V.ovfList = nullptr; V.ovfCount = nullptr;
         V.seedRecs = nullptr;
@@ -2301,7 +2366,7 @@ static int launch_passes(snapgpu_aligner_t *a, int li, const PassIO &io, const A
         HIPCHK(hipGetLastError());
     }
     HIPCHK(hipEventRecord(ev.e[2], L.stream));
-    HIPCHK(hipMemcpyAsync(ev.hCounter, L.counter, 64, hipMemcpyDeviceToHost, L.stream));
+    HIPCHK(hipMemcpyAsync(ev.hCounter, cnt, 64, hipMemcpyDeviceToHost, L.stream));
     return SNAPGPU_OK;
 }
 
@@ -2311,6 +2376,7 @@ static EvSet *nextEvSet(snapgpu_aligner_t *a) {
         EvSet v;
         for (auto &e : v.e)
             if (hipEventCreate(&e) != hipSuccess) { snapgpu::setError("hipEventCreate"); return nullptr; }
+        if (hipMalloc(&v.dCounter, 64) != hipSuccess) { snapgpu::setError("device counter"); return nullptr; }
         if (hipHostMalloc(&v.hCounter, 64, hipHostMallocDefault) != hipSuccess) { snapgpu::setError("pinned counter"); return nullptr; }
         a->evs.push_back(v);
     }
@@ -2323,19 +2389,32 @@ static int beginCall(snapgpu_aligner_t *a) {
     a->timing = snapgpu_timing_t{};
     for (auto &L : a->lane) HIPCHK(hipMemsetAsync(L.lookupStats, 0, 1024 * sizeof(unsigned long long), L.stream));
     HIPCHK(hipMemsetAsync(a->dDiag, 0, sizeof(uint32_t) * 4, a->lane[0].stream));
-    // the other lane's first kernels must not start before the watchdog record is cleared
+    // The call's front stages reuse the event sets' counters from the first one on, and write
+    // buffers that work queued on a lane before this call may still use (a resident run not yet
+    // synchronised, uploads on lane 0): the front stream goes on behind both lanes.
+    for (auto &L : a->lane) {
+        HIPCHK(hipEventRecord(L.done, L.stream));
+        HIPCHK(hipStreamWaitEvent(a->frontStream, L.done, 0));
+    }
+    // the first front kernel and the other lane's first kernels must not start before the watchdog
+    // record is cleared
     HIPCHK(hipStreamSynchronize(a->lane[0].stream));
     return SNAPGPU_OK;
 }
 
-// Union of the [e[from], e[to]] intervals of the call's pass sets (they overlap across lanes), ms.
-static double busyUnion(snapgpu_aligner_t *a, int from, int to) {
+// Union of the [e[from], e[to]] intervals (and, with from2 >= 0, the [e[from2], e[to2]] ones) of
+// the call's pass sets (they overlap across lanes and with the front stream), ms.
+static double busyUnion(snapgpu_aligner_t *a, int from, int to, int from2 = -1, int to2 = -1) {
     std::vector<std::pair<float, float>> iv;
     const hipEvent_t ref = a->evs[0].e[3];
     for (uint64_t i = 0; i < a->nEvUsed; i++) {
         float b = 0, e = 0;
         if (hipEventElapsedTime(&b, ref, a->evs[i].e[from]) != hipSuccess ||
             hipEventElapsedTime(&e, ref, a->evs[i].e[to]) != hipSuccess) return -1;
+        iv.emplace_back(b, e);
+        if (from2 < 0) continue;
+        if (hipEventElapsedTime(&b, ref, a->evs[i].e[from2]) != hipSuccess ||
+            hipEventElapsedTime(&e, ref, a->evs[i].e[to2]) != hipSuccess) return -1;
         iv.emplace_back(b, e);
     }
     std::sort(iv.begin(), iv.end());
@@ -2350,14 +2429,18 @@ static double busyUnion(snapgpu_aligner_t *a, int from, int to) {
 
 static void accountBusy(snapgpu_aligner_t *a) {
     if (a->nEvUsed == 0) return;
-    a->timing.mainKernelBusyMs = busyUnion(a, 0, 1);
+    a->timing.mainKernelBusyMs = busyUnion(a, 0, 4, 5, 1);   // the simple pass (front stream), pass 1 (lane)
     a->timing.lookupKernelBusyMs = busyUnion(a, 3, 0);
 }
 
 // Kernel times and counters of one finished pass set into a->timing.
 static int accountEvSet(snapgpu_aligner_t *a, const EvSet &v) {
     float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, v.e[0], v.e[1]));
+    // the simple pass on the front stream and pass 1 on the lane; the wait between them (the lane's
+    // earlier set, the other lane's kernel holding the wave slots) is neither's
+    HIPCHK(hipEventElapsedTime(&ms, v.e[0], v.e[4]));
+    a->timing.mainKernelMs += ms;
+    HIPCHK(hipEventElapsedTime(&ms, v.e[5], v.e[1]));
     a->timing.mainKernelMs += ms;
     HIPCHK(hipEventElapsedTime(&ms, v.e[1], v.e[2]));
     a->timing.spillKernelMs += ms;
@@ -2389,6 +2472,7 @@ static int launch_resident(snapgpu_aligner_t *a, snapgpu_device_reads_t *d, cons
     rc = beginCall(a);
     if (rc) return rc;
     if (a->residentSidePending) {   // a CIGAR call may still read resident records on the side stream
+        HIPCHK(hipStreamWaitEvent(a->frontStream, a->residentSideDone, 0));   // (the 0xff pre-fill)
         for (auto &L : a->lane) HIPCHK(hipStreamWaitEvent(L.stream, a->residentSideDone, 0));
         a->residentSidePending = false;
     }
@@ -2402,7 +2486,8 @@ static int launch_resident(snapgpu_aligner_t *a, snapgpu_device_reads_t *d, cons
         if (!ev) return SNAPGPU_EDEVICE;
         PassIO io{d->dBases, d->dQuals, d->dOffsets + b, d->dLengths + b, m, d->dOut + b, d->dDefer + b,
                   d->dDefer + (n + 1) + b, d->dDefer + 2 * (n + 1) + b, d->dSeeds + b * SEEDS_PER_READ, d->maxLen};
-        if ((rc = launch_passes(a, (int)(c & 1), io, x, *ev, c ? &a->evs[a->nEvUsed - 2] : nullptr))) return rc;
+        if ((rc = launch_passes(a, (int)(c & 1), io, x, *ev, c ? &a->evs[a->nEvUsed - 2] : nullptr, nullptr, false)))
+            return rc;
     }
     a->lastReads = d;
     a->pendingTiming = n > 0;
@@ -2440,6 +2525,7 @@ int snapgpu_synchronize(snapgpu_aligner_t *a) {
         const int rc = waitLane(a, L);
         if (rc) return rc;
     }
+    if (const int rc = waitFront(a)) return rc;   // (every queued front stage has a lane behind it: returns at once)
     if (a->pendingTiming) {
         a->timing = snapgpu_timing_t{};
         for (uint64_t i = 0; i < a->nEvUsed; i++) {
@@ -2515,6 +2601,7 @@ static int ensureLaneCapacity(snapgpu_aligner_t *a, ExecLane &L, uint64_t reads,
     if (reads <= L.capReads && bytes <= L.capBytes) return SNAPGPU_OK;
     int rc = waitLane(a, L);
     if (rc) return rc;
+    if ((rc = waitFront(a))) return rc;   // nothing of the front stream in flight on the buffers freed here
     freeLaneChunkBuffers(a, L);
     reads = std::max<uint64_t>(reads, 1024);
     const uint64_t cb = bytes + 512;   // zero slack past the last read: over-reading loads stay inside
@@ -2530,10 +2617,12 @@ static int ensureLaneCapacity(snapgpu_aligner_t *a, ExecLane &L, uint64_t reads,
         HIPCHK(hipHostMalloc(&S.hOffsets, (reads + 1) * 8, hipHostMallocDefault));
         HIPCHK(hipHostMalloc(&S.hLengths, (reads + 1) * 4, hipHostMallocDefault));
         HIPCHK(hipHostMalloc(&S.hOut, (reads + 1) * sizeof(snapgpu_result_t), hipHostMallocDefault));
+        // per slot: the front stage of this slot's chunk writes them while the lane's other slot's
+        // chunk is still being aligned (the slot's previous chunk, four back, is finished by then)
+        HIPCHK(hipMalloc(&S.dDefer, 3 * (reads + 1) * 4));   // pass-1 / pass-2 defers, arena overflows
+        HIPCHK(hipMalloc(&S.dOut, (reads + 1) * sizeof(snapgpu_result_t)));
+        HIPCHK(hipMalloc(&S.dSeeds, (reads + 8) * SEEDS_PER_READ * sizeof(SeedRec)));
     }
-    HIPCHK(hipMalloc(&L.dDefer, 3 * (reads + 1) * 4));   // pass-1 / pass-2 defers, arena overflows
-    HIPCHK(hipMalloc(&L.dOut, (reads + 1) * sizeof(snapgpu_result_t)));
-    HIPCHK(hipMalloc(&L.dSeeds, (reads + 8) * SEEDS_PER_READ * sizeof(SeedRec)));
     L.capReads = reads;
     L.capBytes = bytes;
     return SNAPGPU_OK;
@@ -2632,6 +2721,7 @@ static void abandonChunks(snapgpu_aligner_t *a) {
         for (ChunkSlot &S : L.slot) S.pending = false;
         if (!a->failed) waitLane(a, L);
     }
+    if (!a->failed) waitFront(a);   // a front stage queued by a launch that failed before its lane part
     if (!a->failed && a->copyStream) (void)hipStreamSynchronize(a->copyStream);
     a->streamOpen = false;
 }
@@ -2701,13 +2791,13 @@ int snapgpu_align_batch_submit(snapgpu_aligner_t *a, const snapgpu_reads_t *read
         HIPBRK(hipMemcpyAsync(S.dOffsets, S.hOffsets, m * 8, hipMemcpyHostToDevice, cs));
         HIPBRK(hipMemcpyAsync(S.dLengths, S.hLengths, m * 4, hipMemcpyHostToDevice, cs));
         HIPBRK(hipEventRecord(S.h2d, cs));
-        HIPBRK(hipStreamWaitEvent(s, S.h2d, 0));
-        PassIO io{S.dBases, S.dQuals, S.dOffsets, S.dLengths, m, L.dOut, L.dDefer, L.dDefer + (L.capReads + 1),
-                  L.dDefer + 2 * (L.capReads + 1), L.dSeeds, maxLen};
+        // (the front stage waits for the inputs, the lane for the front stage)
+        PassIO io{S.dBases, S.dQuals, S.dOffsets, S.dLengths, m, S.dOut, S.dDefer, S.dDefer + (L.capReads + 1),
+                  S.dDefer + 2 * (L.capReads + 1), S.dSeeds, maxLen};
         EvSet *ev = nextEvSet(a);
         if (!ev) { rc = SNAPGPU_EDEVICE; break; }
-        if ((rc = launch_passes(a, li, io, AlignExt(), *ev, a->nEvUsed >= 2 ? &a->evs[a->nEvUsed - 2] : nullptr))) break;
-        HIPBRK(hipMemcpyAsync(S.hOut, L.dOut, m * sizeof(snapgpu_result_t), hipMemcpyDeviceToHost, s));
+        if ((rc = launch_passes(a, li, io, AlignExt(), *ev, a->nEvUsed >= 2 ? &a->evs[a->nEvUsed - 2] : nullptr, S.h2d))) break;
+        HIPBRK(hipMemcpyAsync(S.hOut, S.dOut, m * sizeof(snapgpu_result_t), hipMemcpyDeviceToHost, s));
         HIPBRK(hipEventRecord(S.done, s));
         S.pending = true;
         S.seq = a->chunkSeq++;
@@ -4581,7 +4671,7 @@ int snapgpu_gather_peak(snapgpu_aligner_t *a, uint32_t nLoads, double *ms) {
     for (int rep = 0; rep < 3; rep++) {
         HIPCHK(hipEventRecord(a->cev[0], a->stream()));
         hipLaunchKernelGGL(gather_peak_kernel, dim3(grid), dim3(256), 0, a->stream(), a->dBuckets, (uint32_t)nBk, nLoads,
-                           0x5bd1e995u * (rep + 1), a->lane[0].counter + 8);
+                           0x5bd1e995u * (rep + 1), a->dSink + 8);
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(a->cev[1], a->stream()));
         HIPCHK(hipEventSynchronize(a->cev[1]));
