@@ -356,8 +356,20 @@ int snapgpu_fastq_upload(snapgpu_aligner_t *a, const char *text, uint64_t nBytes
                          snapgpu_device_reads_t **dOut, snapgpu_reads_t **readsOut);
 int snapgpu_fastq_upload_file(snapgpu_aligner_t *a, const char *path, int clipping, uint32_t flags,
                               snapgpu_device_reads_t **dOut, snapgpu_reads_t **readsOut);
-/* The aligner's last snapgpu_fastq_upload*: text upload (host pass into the staging included),
- * kernels (HIP events), downloads, in ms.  SNAPGPU_EINVAL when there was none. */
+/* The same over a BGZF stream of the text (bgzip's .gz; see snapgpu_bgzf_inflate_gpu below): the
+ * compressed bytes are uploaded and inflated on the device straight into the parser's text buffer,
+ * and the passes above run from there.  An empty stream, or only empty members (the EOF block),
+ * is an empty batch.  SNAPGPU_EFORMAT for a stream that is not BGZF (plain gzip included) or has a
+ * member the inflater refuses; the call frees what it allocated.  The _file form reads the
+ * compressed file into host memory first. */
+int snapgpu_fastq_upload_bgzf(snapgpu_aligner_t *a, const char *data, uint64_t nBytes, const char *name,
+                              int clipping, uint32_t flags,
+                              snapgpu_device_reads_t **dOut, snapgpu_reads_t **readsOut);
+int snapgpu_fastq_upload_bgzf_file(snapgpu_aligner_t *a, const char *path, int clipping, uint32_t flags,
+                                   snapgpu_device_reads_t **dOut, snapgpu_reads_t **readsOut);
+/* The aligner's last snapgpu_fastq_upload*: text upload (host pass into the staging included; the
+ * compressed stream's for the BGZF forms), kernels (HIP events; the inflate kernel included),
+ * downloads, in ms.  SNAPGPU_EINVAL when there was none. */
 int snapgpu_fastq_last_ms(snapgpu_aligner_t *a, double *uploadMs, double *kernelMs, double *downloadMs);
 uint32_t snapgpu_fastq_tile_bytes(void);   /* bytes of text one workgroup scans for newlines */
 /* Test accessor: a resident batch's n, bytes, longest read and extent hash; its offsets (n),
@@ -727,6 +739,31 @@ int snapgpu_bgzf_compress_gpu(snapgpu_aligner_t *a, const char *in, uint64_t n, 
                               uint64_t *used);
 int snapgpu_bgzf_compress_model(const char *in, uint64_t n, int eof, char *out, uint64_t cap, uint64_t *used);
 int snapgpu_bgzf_last_ms(snapgpu_aligner_t *a, double *kernelMs, double *downloadMs);
+
+/* BGZF inflated (host/inflate.cpp, inflate.hip over inflate_block.h): a stream of BGZF members, as
+ * bgzip, samtools and the compressors above write them, back to its bytes.  Every form first walks
+ * the members (magic, CM 8, FLG 4, a BC subfield anywhere in the extra field, BSIZE inside the
+ * stream, ISIZE <= 65,536, nothing after the last member); what fails there, a plain gzip file
+ * included, is SNAPGPU_EFORMAT with the member's index and byte offset.  A member is accepted
+ * exactly when zlib's raw inflater accepts its deflate stream with ISIZE bytes out and the trailer's
+ * CRC32; otherwise SNAPGPU_EFORMAT names the lowest refused member (and, for the model and the
+ * device, the status of inflate_block.h).  Size contract as snapgpu_bgzf_compress*: *used = bytes
+ * needed, SNAPGPU_EINVAL when cap is too small.
+ * snapgpu_bgzf_inflate_size: the walk alone.
+ * snapgpu_bgzf_inflate: zlib, members spread over the host threads.
+ * snapgpu_bgzf_inflate_model: inflate_block.h on the host threads, the code the kernel compiles;
+ * needs no GPU and no zlib.
+ * snapgpu_bgzf_inflate_gpu: upload, one wave per member, download.  No fallback to the host;
+ * SNAPGPU_ENOMEM when the device's free memory cannot hold the stream and its output.
+ * snapgpu_bgzf_inflate_last_ms: upload (staging pass included), kernel (HIP events) and download of
+ * the aligner's last device inflate, the one inside snapgpu_fastq_upload_bgzf* included.
+ * snapgpu_bgzf_inflate_waves: waves the inflate kernel launches on this aligner's device (> 0). */
+int snapgpu_bgzf_inflate_size(const char *in, uint64_t n, uint64_t *outBytes, uint64_t *nMembers);
+int snapgpu_bgzf_inflate(const char *in, uint64_t n, char *out, uint64_t cap, uint64_t *used);
+int snapgpu_bgzf_inflate_model(const char *in, uint64_t n, char *out, uint64_t cap, uint64_t *used);
+int snapgpu_bgzf_inflate_gpu(snapgpu_aligner_t *a, const char *in, uint64_t n, char *out, uint64_t cap, uint64_t *used);
+int snapgpu_bgzf_inflate_last_ms(snapgpu_aligner_t *a, double *uploadMs, double *kernelMs, double *downloadMs);
+int snapgpu_bgzf_inflate_waves(snapgpu_aligner_t *a);
 
 /* --------------------------------------------- RNA annotation (GTF) */
 /* GTFReader (SNAPLib/GTFReader.cpp): exon lines of a GTF/GFF3 file -> transcripts, each an

@@ -28,6 +28,7 @@
 #include "bam_format.h"
 #include "bgzf.h"
 #include "fastq_parse.h"
+#include "inflate.h"
 #include "sam_format.h"
 
 using namespace sgk;
@@ -1333,7 +1334,18 @@ struct snapgpu_aligner {
         bool ran = false;
         double uploadMs = 0, kernelMs = 0, downloadMs = 0;
         double passMs[6] = {};   // count, scan, line starts, records, scans, copy (snapgpu_internal_fastq_pass_ms)
+        double arriveKernelMs = 0;   // kernels that brought the text (the BGZF form's inflate kernel)
     } fq;
+    // device BGZF inflater (inflate.hip): the compressed stream, its member table, the members'
+    // statuses with the lowest refused index after them, and the batch form's output, grow-only;
+    // the last call's times (snapgpu_bgzf_inflate_last_ms)
+    struct InflateState {
+        ExBuf in, members, status, out;
+        hipEvent_t ev[2] = {};
+        int waves = 0;           // waves of the inflate kernel: inflategpu::kWavesPerCu per CU
+        bool ran = false;
+        double uploadMs = 0, kernelMs = 0, downloadMs = 0;
+    } inf;
     hipStream_t stream() const { return lane[0].stream; }
 };
 
@@ -1954,6 +1966,8 @@ void snapgpu_aligner_free(snapgpu_aligner_t *a) {
         if (a->fq.pinDone[k]) hipEventDestroy(a->fq.pinDone[k]);
     }
     for (auto &e : a->fq.ev) if (e) hipEventDestroy(e);
+    for (auto *b : {&a->inf.in, &a->inf.members, &a->inf.status, &a->inf.out}) devFree(a, b->p);
+    for (auto &e : a->inf.ev) if (e) hipEventDestroy(e);
     snapgpu_device_reads_free(a->exReads);
     for (auto *b : {&a->exSearch, &a->exScratch, &a->exFound, &a->exHits, &a->exOff, &a->exDense}) devFree(a, b->p);
     delete a;
@@ -4087,16 +4101,16 @@ int fqFits(uint64_t need, const char *what) {
 // fill(dst, off, m): bytes [off, off + m) of the text into a staging chunk (false: setError was called)
 using FastqFill = std::function<bool(char *, uint64_t, uint64_t)>;
 
-// The text to device memory through two pinned staging chunks: chunk k + 1 is filled by the host
-// while chunk k crosses PCIe (textDownload's reverse).  *last = the text's last byte.
-int fastqTextUpload(snapgpu_aligner_t *a, uint64_t nBytes, const FastqFill &fill, char *last) {
+// nBytes of text (or of a compressed stream) to dst[0 .. cap) in device memory, zeros after them,
+// through two pinned staging chunks: chunk k + 1 is filled by the host while chunk k crosses PCIe
+// (textDownload's reverse).  *last = the last byte.
+int fastqTextUpload(snapgpu_aligner_t *a, char *dst, uint64_t cap, uint64_t nBytes, const FastqFill &fill, char *last) {
     auto &F = a->fq;
     for (int k = 0; k < 2; k++) {
         if (!F.pin[k]) HIPCHK(hipHostMalloc(&F.pin[k], kFastqChunk, hipHostMallocDefault));
         if (!F.pinDone[k]) HIPCHK(hipEventCreateWithFlags(&F.pinDone[k], hipEventDisableTiming));
     }
-    const uint64_t cap = fqgpu::textCapacity(nBytes);
-    HIPCHK(hipMemsetAsync((char *)F.text.p + nBytes, 0, cap - nBytes, a->copyStream));
+    HIPCHK(hipMemsetAsync(dst + nBytes, 0, cap - nBytes, a->copyStream));
     const uint64_t nChunks = (nBytes + kFastqChunk - 1) / kFastqChunk;
     for (uint64_t k = 0; k < nChunks; k++) {
         const uint64_t b = k * kFastqChunk, m = std::min(kFastqChunk, nBytes - b);
@@ -4105,7 +4119,7 @@ int fastqTextUpload(snapgpu_aligner_t *a, uint64_t nBytes, const FastqFill &fill
             if (int rc = waitEvent(a, F.pinDone[k & 1])) return rc;
         if (!fill(pin, b, m)) return SNAPGPU_EIO;
         if (k + 1 == nChunks) *last = pin[m - 1];
-        HIPCHK(hipMemcpyAsync((char *)F.text.p + b, pin, m, hipMemcpyHostToDevice, a->copyStream));
+        HIPCHK(hipMemcpyAsync(dst + b, pin, m, hipMemcpyHostToDevice, a->copyStream));
         HIPCHK(hipEventRecord(F.pinDone[k & 1], a->copyStream));
     }
     HIPCHK(hipStreamSynchronize(a->copyStream));
@@ -4122,9 +4136,88 @@ void fastqParallel(uint64_t m, Fn fn) {
     for (auto &x : th) x.join();
 }
 
+// ---- BGZF inflated on the device (inflate.hip)
+using inflateblock::Member;
+
+int inflateWaves(snapgpu_aligner_t *a) {
+    if (!a->inf.waves) {
+        hipDeviceProp_t prop;
+        HIPCHK(hipGetDeviceProperties(&prop, a->device));
+        a->inf.waves = std::max(1, prop.multiProcessorCount) * (int)inflategpu::kWavesPerCu;
+    }
+    return SNAPGPU_OK;
+}
+
+// what the inflater's own buffers would newly allocate for a stream of n bytes in nMembers members
+uint64_t inflateGrowBytes(const snapgpu_aligner_t *a, uint64_t n, uint64_t nMembers) {
+    return growBytes(a->inf.in, n + inflategpu::kInSlack) + growBytes(a->inf.members, nMembers * sizeof(Member) + 16) +
+           growBytes(a->inf.status, (nMembers + 1) * 4 + 16);
+}
+
+// The stream to device memory through the text upload's staging chunks, its member table beside
+// it, the kernel over all members into dst (device memory with room for every member's output),
+// and the verdict: SNAPGPU_EFORMAT with the lowest refused member.  The caller has checked
+// inflateGrowBytes and dst against the device's free memory.  Waits.
+int inflateOnDevice(snapgpu_aligner_t *a, const char *what, const char *in, uint64_t n, const std::vector<Member> &members,
+                    char *dst) {
+    using clk = std::chrono::steady_clock;
+    auto &I = a->inf;
+    I.ran = false;
+    I.uploadMs = I.kernelMs = I.downloadMs = 0;
+    const uint64_t nm = members.size();
+    if (nm >= inflategpu::kNoBad) { snapgpu::setError(std::string(what) + ": too many members"); return SNAPGPU_EINVAL; }
+    if (int rc = inflateWaves(a)) return rc;
+    for (auto &e : I.ev)
+        if (!e) HIPCHK(hipEventCreate(&e));
+    HIPCHK(fqEnsure(a, I.in, n + inflategpu::kInSlack));
+    HIPCHK(fqEnsure(a, I.members, nm * sizeof(Member) + 16));
+    HIPCHK(fqEnsure(a, I.status, (nm + 1) * 4 + 16));
+    auto t0 = clk::now();
+    const FastqFill fill = [in](char *pin, uint64_t off, uint64_t m) {
+        fastqParallel(m, [=](uint64_t b, uint64_t e) { memcpy(pin + b, in + off + b, e - b); });
+        return true;
+    };
+    char last = 0;
+    if (int rc = fastqTextUpload(a, (char *)I.in.p, n + inflategpu::kInSlack, n, fill, &last)) return rc;
+    if (nm) HIPCHK(hipMemcpyAsync(I.members.p, members.data(), nm * sizeof(Member), hipMemcpyHostToDevice, a->copyStream));
+    HIPCHK(hipStreamSynchronize(a->copyStream));
+    I.uploadMs = std::chrono::duration<double, std::milli>(clk::now() - t0).count();
+    hipStream_t s = a->stream();
+    uint32_t *status = (uint32_t *)I.status.p, *firstBad = status + nm;
+    HIPCHK(hipEventRecord(I.ev[0], s));
+    HIPCHK(inflategpu::launch((const uint8_t *)I.in.p, (const Member *)I.members.p, (uint32_t)nm, (uint8_t *)dst, status,
+                              firstBad, (uint32_t)I.waves, s));
+    HIPCHK(hipEventRecord(I.ev[1], s));
+    uint32_t bad = inflategpu::kNoBad;
+    HIPCHK(hipMemcpyAsync(&bad, firstBad, 4, hipMemcpyDeviceToHost, s));
+    if (int rc = waitLane(a, a->lane[0])) return rc;
+    float f = 0;
+    HIPCHK(hipEventElapsedTime(&f, I.ev[0], I.ev[1]));
+    I.kernelMs = f;
+    I.ran = true;
+    if (bad != inflategpu::kNoBad) {
+        if (bad >= nm) { snapgpu::setError(std::string(what) + ": the kernel names a member the stream does not have"); return SNAPGPU_EDEVICE; }
+        uint32_t st = 0;
+        HIPCHK(hipMemcpy(&st, status + bad, 4, hipMemcpyDeviceToHost));
+        return snapgpu::bgzfRefused(what, bad, members[bad].inStart, st);
+    }
+    return SNAPGPU_OK;
+}
+
+// How the text reaches the parser's device buffer, which fastqRun sizes: the plain form uploads it
+// (fastqTextUpload), the BGZF form uploads the compressed stream and inflates it there.
+struct FastqArrival {
+    uint64_t nBytes = 0;      // the text's bytes
+    uint64_t extraNeed = 0;   // device bytes the arrival itself newly allocates (fastqRun's memory check counts them)
+    // the text into text[0 .. nBytes), zeros from there to cap; *last = its last byte (nBytes > 0);
+    // *kernelMs = what its own kernels took
+    std::function<int(char *text, uint64_t cap, char *last, double *kernelMs)> arrive;
+};
+
 // d and r: what the call has allocated so far (the caller frees them when the call fails)
-int fastqRun(snapgpu_aligner_t *a, uint64_t nBytes, const FastqFill &fill, const char *name, int clipping, bool hostBatch,
+int fastqRun(snapgpu_aligner_t *a, const FastqArrival &arrival, const char *name, int clipping, bool hostBatch,
              snapgpu_device_reads_t *&d, snapgpu_reads_t *&r) {
+    const uint64_t nBytes = arrival.nBytes;
     using clk = std::chrono::steady_clock;
     auto ms = [](clk::time_point t0) { return std::chrono::duration<double, std::milli>(clk::now() - t0).count(); };
     auto &F = a->fq;
@@ -4132,22 +4225,22 @@ int fastqRun(snapgpu_aligner_t *a, uint64_t nBytes, const FastqFill &fill, const
     for (auto &e : F.ev)
         if (!e) HIPCHK(hipEventCreate(&e));
     F.ran = false;
-    F.uploadMs = F.kernelMs = F.downloadMs = 0;
+    F.uploadMs = F.kernelMs = F.downloadMs = F.arriveKernelMs = 0;
     for (double &m : F.passMs) m = 0;
     bool evUsed[3] = {false, false, false};
     // 1. the text, its tiles' newline counts and their scan
     const uint64_t nTiles = fqgpu::tiles(nBytes), textCap = fqgpu::textCapacity(nBytes);
     const uint64_t needTiles[4] = {textCap, nTiles * 4 + 16, (nTiles + 1) * 8, samgpu::scanTiles(nTiles) * 8 + 16};
     snapgpu_aligner::ExBuf *bufTiles[4] = {&F.text, &F.counts, &F.tileStart, &F.sums};
-    uint64_t need = 0;
+    uint64_t need = arrival.extraNeed;
     for (int k = 0; k < 4; k++) need += growBytes(*bufTiles[k], needTiles[k]);
     if (int rc = fqFits(need, "the text")) return rc;
     for (int k = 0; k < 4; k++) HIPCHK(fqEnsure(a, *bufTiles[k], needTiles[k]));
     const char *text = (const char *)F.text.p;
     char last = '\n';
     auto t0 = clk::now();
-    if (int rc = fastqTextUpload(a, nBytes, fill, &last)) return rc;
-    F.uploadMs = ms(t0);
+    if (int rc = arrival.arrive((char *)F.text.p, textCap, &last, &F.arriveKernelMs)) return rc;
+    F.uploadMs = ms(t0) - F.arriveKernelMs;
     uint64_t nNl = 0;
     if (nBytes) {
         HIPCHK(hipEventRecord(F.ev[0], s));
@@ -4301,11 +4394,40 @@ int fastqRun(snapgpu_aligner_t *a, uint64_t nBytes, const FastqFill &fill, const
                 F.passMs[slot + j] = f;
                 F.kernelMs += f;
             }
+    F.kernelMs += F.arriveKernelMs;
     F.ran = true;
     return SNAPGPU_OK;
 }
 
-int fastqUpload(snapgpu_aligner_t *a, uint64_t nBytes, const FastqFill &fill, const char *name, int clipping,
+// the plain form's arrival: the text itself through the staging chunks
+FastqArrival fastqPlainArrival(snapgpu_aligner_t *a, uint64_t nBytes, const FastqFill &fill) {
+    FastqArrival A;
+    A.nBytes = nBytes;
+    A.arrive = [a, nBytes, &fill](char *text, uint64_t cap, char *last, double *) -> int {
+        return fastqTextUpload(a, text, cap, nBytes, fill, last);
+    };
+    return A;
+}
+
+// The BGZF form's arrival: the compressed stream goes up and bgzf_inflate_kernel writes the text
+// where the parser reads it; its last byte comes back.
+FastqArrival fastqBgzfArrival(snapgpu_aligner_t *a, const char *in, uint64_t n, const std::vector<Member> &members,
+                              uint64_t textBytes) {
+    FastqArrival A;
+    A.nBytes = textBytes;
+    A.extraNeed = inflateGrowBytes(a, n, members.size());
+    A.arrive = [a, in, n, &members, textBytes](char *text, uint64_t cap, char *last, double *kernelMs) -> int {
+        HIPCHK(hipMemsetAsync(text + textBytes, 0, cap - textBytes, a->stream()));
+        const int rc = inflateOnDevice(a, "fastq_upload_bgzf", in, n, members, text);
+        *kernelMs = a->inf.kernelMs;
+        if (rc) return rc;
+        if (textBytes) HIPCHK(hipMemcpy(last, text + textBytes - 1, 1, hipMemcpyDeviceToHost));
+        return (int)SNAPGPU_OK;
+    };
+    return A;
+}
+
+int fastqUpload(snapgpu_aligner_t *a, const FastqArrival &arrival, const char *name, int clipping,
                 uint32_t flags, snapgpu_device_reads_t **dOut, snapgpu_reads_t **readsOut) {
     if (dOut) *dOut = nullptr;
     if (readsOut) *readsOut = nullptr;
@@ -4319,7 +4441,7 @@ int fastqUpload(snapgpu_aligner_t *a, uint64_t nBytes, const FastqFill &fill, co
     HIPCHK(hipSetDevice(a->device));
     snapgpu_device_reads_t *d = nullptr;
     snapgpu_reads_t *r = nullptr;
-    const int rc = fastqRun(a, nBytes, fill, name, clipping, hostBatch, d, r);
+    const int rc = fastqRun(a, arrival, name, clipping, hostBatch, d, r);
     if (rc != SNAPGPU_OK) {
         snapgpu_device_reads_free(d);
         snapgpu_reads_free(r);
@@ -4346,7 +4468,7 @@ int snapgpu_fastq_upload(snapgpu_aligner_t *a, const char *text, uint64_t nBytes
         fastqParallel(m, [=](uint64_t b, uint64_t e) { memcpy(dst + b, text + off + b, e - b); });
         return true;
     };
-    return fastqUpload(a, nBytes, fill, name, clipping, flags, dOut, readsOut);
+    return fastqUpload(a, fastqPlainArrival(a, nBytes, fill), name, clipping, flags, dOut, readsOut);
 }
 
 int snapgpu_fastq_upload_file(snapgpu_aligner_t *a, const char *path, int clipping, uint32_t flags,
@@ -4371,9 +4493,86 @@ int snapgpu_fastq_upload_file(snapgpu_aligner_t *a, const char *path, int clippi
         if (!ok) snapgpu::setError(std::string("cannot read ") + path);
         return ok.load();
     };
-    const int rc = fastqUpload(a, (uint64_t)sb.st_size, fill, path, clipping, flags, dOut, readsOut);
+    const int rc = fastqUpload(a, fastqPlainArrival(a, (uint64_t)sb.st_size, fill), path, clipping, flags, dOut, readsOut);
     close(fd);
     return rc;
+}
+
+int snapgpu_fastq_upload_bgzf(snapgpu_aligner_t *a, const char *data, uint64_t nBytes, const char *name, int clipping,
+                              uint32_t flags, snapgpu_device_reads_t **dOut, snapgpu_reads_t **readsOut) {
+    if (dOut) *dOut = nullptr;
+    if (readsOut) *readsOut = nullptr;
+    if (!a || (!data && nBytes) || !name) {
+        snapgpu::setError("fastq_upload_bgzf: bad argument");
+        return SNAPGPU_EINVAL;
+    }
+    std::vector<Member> members;
+    uint64_t textBytes = 0;
+    if (int rc = snapgpu::bgzfWalk("fastq_upload_bgzf", data, nBytes, members, &textBytes)) return rc;
+    return fastqUpload(a, fastqBgzfArrival(a, data, nBytes, members, textBytes), name, clipping, flags, dOut, readsOut);
+}
+
+int snapgpu_fastq_upload_bgzf_file(snapgpu_aligner_t *a, const char *path, int clipping, uint32_t flags,
+                                   snapgpu_device_reads_t **dOut, snapgpu_reads_t **readsOut) {
+    if (dOut) *dOut = nullptr;
+    if (readsOut) *readsOut = nullptr;
+    if (!path) { snapgpu::setError("fastq_upload_bgzf: bad argument"); return SNAPGPU_EINVAL; }
+    const int fd = open(path, O_RDONLY);
+    if (fd < 0) { snapgpu::setError(std::string("cannot open ") + path); return SNAPGPU_EIO; }
+    struct stat sb;
+    if (fstat(fd, &sb) != 0) { close(fd); snapgpu::setError(std::string("cannot stat ") + path); return SNAPGPU_EIO; }
+    // the member walk hops through the whole stream, so the compressed file is read first
+    const uint64_t size = (uint64_t)sb.st_size;
+    std::unique_ptr<char[]> data(new char[size ? size : 1]);
+    std::atomic<bool> ok{true};
+    char *dst = data.get();
+    fastqParallel(size, [&ok, fd, dst](uint64_t b, uint64_t e) {
+        while (b < e) {
+            const ssize_t got = pread(fd, dst + b, e - b, (off_t)b);
+            if (got <= 0) { ok = false; return; }
+            b += (uint64_t)got;
+        }
+    });
+    close(fd);
+    if (!ok) { snapgpu::setError(std::string("cannot read ") + path); return SNAPGPU_EIO; }
+    return snapgpu_fastq_upload_bgzf(a, data.get(), size, path, clipping, flags, dOut, readsOut);
+}
+
+int snapgpu_bgzf_inflate_gpu(snapgpu_aligner_t *a, const char *in, uint64_t n, char *out, uint64_t cap, uint64_t *used) {
+    if (!a || (!in && n) || !used) { snapgpu::setError("bgzf_inflate_gpu: null argument"); return SNAPGPU_EINVAL; }
+    *used = 0;
+    if (a->failed) { snapgpu::setError("aligner failed earlier (device timeout)"); return SNAPGPU_EDEVICE; }
+    std::vector<Member> members;
+    uint64_t total = 0;
+    if (int rc = snapgpu::bgzfWalk("bgzf_inflate_gpu", in, n, members, &total)) return rc;
+    *used = total;
+    if (total > cap || (!out && total)) { snapgpu::setError("bgzf_inflate_gpu: output buffer too small"); return SNAPGPU_EINVAL; }
+    HIPCHK(hipSetDevice(a->device));
+    auto &I = a->inf;
+    if (int rc = fqFits(inflateGrowBytes(a, n, members.size()) + growBytes(I.out, total + 64), "the stream and its output")) return rc;
+    HIPCHK(fqEnsure(a, I.out, total + 64));
+    if (int rc = inflateOnDevice(a, "bgzf_inflate_gpu", in, n, members, (char *)I.out.p)) return rc;
+    const auto t0 = std::chrono::steady_clock::now();
+    if (total)
+        if (int rc = textDownload(a, (const char *)I.out.p, total, out)) return rc;
+    I.downloadMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return SNAPGPU_OK;
+}
+
+int snapgpu_bgzf_inflate_last_ms(snapgpu_aligner_t *a, double *uploadMs, double *kernelMs, double *downloadMs) {
+    if (!a || !uploadMs || !kernelMs || !downloadMs) return SNAPGPU_EINVAL;
+    if (!a->inf.ran) { snapgpu::setError("bgzf_inflate_last_ms: no device inflate on this aligner"); return SNAPGPU_EINVAL; }
+    *uploadMs = a->inf.uploadMs;
+    *kernelMs = a->inf.kernelMs;
+    *downloadMs = a->inf.downloadMs;
+    return SNAPGPU_OK;
+}
+
+int snapgpu_bgzf_inflate_waves(snapgpu_aligner_t *a) {
+    if (!a) { snapgpu::setError("bgzf_inflate_waves: null argument"); return SNAPGPU_EINVAL; }
+    if (a->failed) { snapgpu::setError("aligner failed earlier (device timeout)"); return SNAPGPU_EDEVICE; }
+    if (int rc = inflateWaves(a)) return rc;
+    return a->inf.waves;
 }
 
 int snapgpu_fastq_last_ms(snapgpu_aligner_t *a, double *uploadMs, double *kernelMs, double *downloadMs) {

@@ -7,6 +7,10 @@
 #include <string>
 #include <vector>
 
+namespace inflateblock {
+struct Member;   // inflate_block.h
+}
+
 namespace snapgpu {
 
 // Guard bytes of 'n' before base 0 and after the last base.  The reference keeps
@@ -163,6 +167,12 @@ std::string bamHeader(const Genome &g, const std::string &samText);
 bool bgzfWrite(FILE *f, const char *data, size_t n, bool eof);
 // the public encoder's id check (host and device forms): SNAPGPU_EINVAL for an id past the QNAME limit
 int bamCheckIds(const uint32_t *idLengths, uint64_t n);
+
+// inflate.cpp: the member walk of a BGZF stream (header checks, BSIZE hops, ISIZE <= 65,536) -> the
+// members and the bytes they inflate to, or SNAPGPU_EFORMAT naming the member's index and byte
+// offset; and the error of a member whose deflate stream a decoder refused (inflate_block.h's Status)
+int bgzfWalk(const char *what, const char *in, uint64_t n, std::vector<inflateblock::Member> &members, uint64_t *outBytes);
+int bgzfRefused(const char *what, uint64_t index, uint64_t at, uint32_t status);
 
 // One pair's GTFReader::IncrementReadCount (pair form) arguments (gtf.cpp: gtfCountPairs).
 struct GtfPairQuery {

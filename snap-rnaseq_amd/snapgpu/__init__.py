@@ -587,25 +587,47 @@ class BaseAligner:
         _check(lib().snapgpu_bgzf_last_ms(self._h, C.byref(k), C.byref(d)), "bgzf_last_ms")
         return k.value, d.value
 
+    def bgzf_inflate(self, data):
+        """The bytes of the BGZF stream `data`, inflated on the GPU (snapgpu_bgzf_inflate_gpu: uploads the
+        stream, one wave per member, downloads the bytes).  Byte-identical to the module-level
+        bgzf_inflate and bgzf_inflate_model; refuses what they refuse."""
+        return _inflate_call(lambda *tail: lib().snapgpu_bgzf_inflate_gpu(self._h, *tail), data, "bgzf_inflate_gpu")
+
+    def bgzf_inflate_ms(self):
+        """(upload ms, kernel ms, download ms) of the last device inflate, upload_fastq(bgzf=True)'s
+        included (snapgpu_bgzf_inflate_last_ms)."""
+        u, k, d = C.c_double(), C.c_double(), C.c_double()
+        _check(lib().snapgpu_bgzf_inflate_last_ms(self._h, C.byref(u), C.byref(k), C.byref(d)), "bgzf_inflate_last_ms")
+        return u.value, k.value, d.value
+
+    def bgzf_inflate_waves(self):
+        """Waves the inflate kernel launches on this aligner's device (snapgpu_bgzf_inflate_waves)."""
+        n = lib().snapgpu_bgzf_inflate_waves(self._h)
+        if n <= 0:
+            raise SnapGpuError(f"bgzf_inflate_waves failed ({n}): {last_error()}")
+        return n
+
     def upload(self, reads):
         return DeviceReads(self, reads)
 
-    def upload_fastq(self, path_or_bytes, clipping=0, host_batch=True, name="<memory>"):
+    def upload_fastq(self, path_or_bytes, clipping=0, host_batch=True, name="<memory>", bgzf=False):
         """FASTQ parsed on the device (snapgpu_fastq_upload / _file): the text (bytes) or the file
         (a path) is uploaded, and split, clipped and packed in device memory -> DeviceReads, as
         upload() of the host parser's batch clipped at `clipping` would give.  Its .reads is that
-        host batch (a Reads), or None with host_batch=False."""
+        host batch (a Reads), or None with host_batch=False.  bgzf=True: the bytes or the file are a
+        BGZF stream of the text (bgzip's .gz), inflated on the device (snapgpu_fastq_upload_bgzf /
+        _file)."""
         d, r = C.c_void_p(), C.POINTER(_ffi.Reads)()
         flags = FASTQ_HOST_BATCH if host_batch else 0
         rp = C.byref(r) if host_batch else None
+        from_bytes, from_file = ((lib().snapgpu_fastq_upload_bgzf, lib().snapgpu_fastq_upload_bgzf_file) if bgzf else
+                                 (lib().snapgpu_fastq_upload, lib().snapgpu_fastq_upload_file))
         if isinstance(path_or_bytes, (bytes, bytearray, memoryview)):
             buf = np.frombuffer(bytes(path_or_bytes) + b"\0", dtype=np.uint8)
-            rc = lib().snapgpu_fastq_upload(self._h, buf.ctypes.data, len(buf) - 1, str(name).encode(), int(clipping),
-                                            flags, C.byref(d), rp)
+            rc = from_bytes(self._h, buf.ctypes.data, len(buf) - 1, str(name).encode(), int(clipping), flags, C.byref(d), rp)
         else:
-            rc = lib().snapgpu_fastq_upload_file(self._h, os.fspath(path_or_bytes).encode(), int(clipping), flags,
-                                                 C.byref(d), rp)
-        _check(rc, "fastq_upload")
+            rc = from_file(self._h, os.fspath(path_or_bytes).encode(), int(clipping), flags, C.byref(d), rp)
+        _check(rc, "fastq_upload_bgzf" if bgzf else "fastq_upload")
         return DeviceReads(self, Reads(r) if host_batch else None, handle=d.value)
 
     def fastq_last_ms(self):
@@ -1151,6 +1173,40 @@ def bgzf_compress_model(data, eof=True):
     """The device BGZF compressor's stream from the host threads, byte for byte (snapgpu_bgzf_compress_model:
     the serial restatement of csrc/bgzf_block.h; needs no GPU) -> bytes.  gzip.decompress gives `data` back."""
     return _bgzf_call(lib().snapgpu_bgzf_compress_model, data, eof, "bgzf_compress_model")
+
+
+def bgzf_inflate_size(data):
+    """(bytes the BGZF stream `data` inflates to, its members): the member walk alone
+    (snapgpu_bgzf_inflate_size).  Raises for a stream that is not BGZF."""
+    src = np.frombuffer(bytes(data), dtype=np.uint8)
+    out, members = C.c_uint64(), C.c_uint64()
+    _check(lib().snapgpu_bgzf_inflate_size(src.ctypes.data if src.size else None, int(src.size), C.byref(out),
+                                           C.byref(members)), "bgzf_inflate_size")
+    return out.value, members.value
+
+
+def _inflate_call(fn, data, what):
+    """fn(in, n, out, cap, used) of an inflater over the BGZF stream `data` -> bytes: a first call for
+    the size (the size contract of include/snapgpu.h), a second into a buffer of it."""
+    src = np.frombuffer(bytes(data), dtype=np.uint8)
+    n = int(src.size)
+    size, _ = bgzf_inflate_size(data)
+    buf = np.empty(max(1, size), dtype=np.uint8)
+    used = C.c_uint64()
+    _check(fn(src.ctypes.data if n else None, n, buf.ctypes.data, size, C.byref(used)), what)
+    return buf[:used.value].tobytes()
+
+
+def bgzf_inflate(data):
+    """The bytes of the BGZF stream `data`, inflated by zlib on the host threads (snapgpu_bgzf_inflate:
+    bgzf_compress's counterpart).  gzip.decompress gives the same bytes."""
+    return _inflate_call(lib().snapgpu_bgzf_inflate, data, "bgzf_inflate")
+
+
+def bgzf_inflate_model(data):
+    """The same through csrc/inflate_block.h on the host threads, the decoder the device kernel
+    compiles (snapgpu_bgzf_inflate_model; needs no GPU and no zlib)."""
+    return _inflate_call(lib().snapgpu_bgzf_inflate_model, data, "bgzf_inflate_model")
 
 
 def _sam_line_write(index, reads, ids, results, cigars, read_group="FASTQ", clip=None):

@@ -299,6 +299,10 @@ _PROTOS = [
                                        C.POINTER(C.c_void_p), C.POINTER(C.POINTER(Reads))]),
     ("snapgpu_fastq_upload_file", C.c_int, [C.c_void_p, C.c_char_p, C.c_int, C.c_uint32,
                                             C.POINTER(C.c_void_p), C.POINTER(C.POINTER(Reads))]),
+    ("snapgpu_fastq_upload_bgzf", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_char_p, C.c_int, C.c_uint32,
+                                            C.POINTER(C.c_void_p), C.POINTER(C.POINTER(Reads))]),
+    ("snapgpu_fastq_upload_bgzf_file", C.c_int, [C.c_void_p, C.c_char_p, C.c_int, C.c_uint32,
+                                                 C.POINTER(C.c_void_p), C.POINTER(C.POINTER(Reads))]),
     ("snapgpu_fastq_last_ms", C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                         C.POINTER(C.c_double)]),
     ("snapgpu_fastq_tile_bytes", C.c_uint32, []),
@@ -390,6 +394,14 @@ _PROTOS = [
     ("snapgpu_bgzf_compress_model", C.c_int, [C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_uint64,
                                               C.POINTER(C.c_uint64)]),
     ("snapgpu_bgzf_last_ms", C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    ("snapgpu_bgzf_inflate_size", C.c_int, [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    ("snapgpu_bgzf_inflate", C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
+    ("snapgpu_bgzf_inflate_model", C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
+    ("snapgpu_bgzf_inflate_gpu", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
+                                           C.POINTER(C.c_uint64)]),
+    ("snapgpu_bgzf_inflate_last_ms", C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                               C.POINTER(C.c_double)]),
+    ("snapgpu_bgzf_inflate_waves", C.c_int, [C.c_void_p]),
     ("snapgpu_gather_peak", C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_double)]),
     ("snapgpu_aligner_bucket_info", C.c_int, [C.c_void_p, C.POINTER(BucketInfo)]),
     ("snapgpu_aligner_lookup_seeds", C.c_int, [C.c_void_p, C.c_char_p, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p]),
