@@ -444,6 +444,22 @@ int snapgpu_aligner_set_simple_pass(snapgpu_aligner_t *a, int on);
  * SNAPGPU_EDEVICE.  Each aligner has its own watchdog record: a trip in one aligner neither
  * fails nor stops another aligner on the same device. */
 int snapgpu_aligner_debug_trip(snapgpu_aligner_t *a, uint32_t read_index);
+/* Test accessor (no reference equivalent): the persistent kernels' grids and what they were sized
+ * from.  A grid is the compute units times the workgroups per CU that are resident at once: the
+ * lesser of the runtime's occupancy answer and ldsPerCU / (the kernel's static LDS rounded up to
+ * ldsUnit); grid256 and grid512 are capped at grid128 (they reuse its arenas).  shortRows: pass 1 runs
+ * the 128-base align kernel with 16 Landau-Vishkin rows in LDS (maxK + extraSearchDepth <= 16), lds128
+ * being that kernel's static LDS.  The environment variable SNAPGPU_WAVES_PER_CU caps every perCU. */
+typedef struct snapgpu_grids {
+    uint32_t computeUnits, shortRows;
+    uint32_t perCU128, grid128;
+    uint32_t perCU256, grid256;
+    uint32_t perCU512, grid512;
+    uint32_t perCUSimple, gridSimple;
+    uint32_t perCUCigar, gridCigar;
+    uint32_t lds128, ldsUnit, ldsPerCU, reserved;
+} snapgpu_grids_t;
+int snapgpu_aligner_debug_grids(snapgpu_aligner_t *a, snapgpu_grids_t *g);
 /* SHA-256 of the sources this library was built from (snapgpu/_srcsha.py: csrc, this header, the
  * Makefile); the Python loader refuses a library whose identity differs from the sources beside it. */
 const char *snapgpu_source_sha256(void);
@@ -954,6 +970,12 @@ int snapgpu_paired_intersect_batch(snapgpu_paired_aligner_t *pa, const snapgpu_r
                                    const snapgpu_reads_t *reads1, snapgpu_pair_result_t *out);
 /* The single-end BaseAligner the chimeric fallback uses (maxHits, maxK, seeds of the params). */
 snapgpu_aligner_t *snapgpu_paired_aligner_single(snapgpu_paired_aligner_t *pa);
+/* Test accessor (as snapgpu_aligner_debug_grids): out[0] compute units; the resident workgroups per CU
+ * and the grid of the pair kernel for reads up to 128 bases (out[1], out[2]), up to 256 bases (out[3],
+ * out[4]: capped at out[2], whose pools it uses) and up to 512 bases (out[5], out[6]); out[7] the grid
+ * of the pass over the reference's whole pools (at most out[6], halved until its pools fit 8 GB).
+ * SNAPGPU_PAIRED_GRID caps every grid. */
+int snapgpu_paired_aligner_debug_grids(const snapgpu_paired_aligner_t *pa, uint32_t out[8]);
 
 /* ------------------------------------------- RNA seed census
  * BaseAligner::CharacterizeSeeds (BaseAligner.cpp:206-508) on the GPU: the seeds of AlignRead's

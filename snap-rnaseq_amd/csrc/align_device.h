@@ -370,8 +370,15 @@ __device__ __forceinline__ int cand_e1(uint32_t cw) { return (int)((cw >> 10) & 
 __device__ __forceinline__ int cand_e2(uint32_t cw) { return (int)((cw >> 13) & 7u); }
 static_assert(EB <= 8 && ELEM <= 64, "cand_* encoding: 3-bit slot, 6-bit bit");
 
-template <int MAXLEN>
+// LV rows of a bit-plane kernel: FULL_ROWS serve any score limit the aligner accepts; an aligner whose
+// limit (maxK + extraSearchDepth) is at most SHORT_ROWS runs align_kernel<128> on SHORT_ROWS rows, which
+// with the byte-path members gone brings Lds<128> from 8,096 B to 7,552 B (the static_assert below).
+constexpr int FULL_ROWS = MAX_K - 1;
+constexpr int SHORT_ROWS = 16;
+
+template <int MAXLEN, int ROWS = FULL_ROWS>
 struct Lds {
+    static_assert(ROWS == FULL_ROWS || ROWS == SHORT_ROWS, "LV row capacity");
     static constexpr uint32_t ORD = ordcap(MAXLEN);
     static constexpr int NB = MAXLEN / 64;          // 64-position blocks
     static constexpr bool BYTE_PATH = MAXLEN > 256; // byte-compare LV (align_device.h) vs bit planes
@@ -379,16 +386,17 @@ struct Lds {
     // The bit-plane kernels keep only the forward read: the reverse complement's planes are built
     // from it, its qualities read backwards.  The byte path keeps both, with 64 bytes of slack.
     static constexpr int RL = BYTE_PATH ? MAXLEN + 64 : MAXLEN;
-    static constexpr int RCL = BYTE_PATH ? MAXLEN + 64 : 1;
+    static constexpr int RCL = BYTE_PATH ? MAXLEN + 64 : 0;
     // element hash-chain heads: u16 on the bit-plane kernels (arenas capped below 0xffff elements,
     // snapgpu_aligner_create), u32 on the byte path (the big-arena pass's worst-case arenas)
     using HeadT = typename std::conditional<BYTE_PATH, uint32_t, uint16_t>::type;
     static constexpr HeadT HEAD_NONE = (HeadT)~(HeadT)0;
     char fwd[RL];                                   // read[FORWARD], zero slack
+    // (the byte-path members are zero-length arrays in the bit-plane kernels, as grp is on the byte path)
     char rc[RCL];                                   // read[RC] (byte path)
     char fwdQ[RL];
     char rcQ[RCL];
-    uint32_t win[BYTE_PATH ? (MAXLEN + 192) / 4 : 1];   // genome window [g-64, g+n+64+64)
+    uint32_t win[BYTE_PATH ? (MAXLEN + 192) / 4 : 0];   // genome window [g-64, g+n+64+64)
     HeadT head[NBUCKET];                            // element hash chains
     // hit insertion and scoring never overlap in time: their scratch shares LDS (the
     // insertion table is cleared again after every score call that used it)
@@ -399,10 +407,11 @@ struct Lds {
             uint32_t scrLoc[WAVE];                  // batch scratch: hit location per lane
         } ins;
         struct {
-            // LV rows 1..MAX_K-1 (L + 2 per row, lane; actions recomputed; row 0 is never stored:
+            // LV rows 1..ROWS (L + 2 per row, lane; actions recomputed; row 0 is never stored:
             // lv_rows() maps row e to rows8[e - 1]); between passes, the staged selection keys of
-            // the forced-mode ranking
-            alignas(16) uint8_t rows8[BYTE_PATH ? 1 : MAX_K - 1][WAVE];
+            // the forced-mode ranking (SKCAP dwords) or forced_sort's histogram (256 dwords).  The
+            // last row also carries score_batched's lvIdx.
+            alignas(16) uint8_t rows8[BYTE_PATH ? 1 : ROWS][WAVE];
             uint16_t order[ordcap(MAXLEN)];         // forced-mode pop order
         } sc;
     } u;
@@ -415,28 +424,34 @@ struct Lds {
     uint32_t ekey[MIRCAP];                          // element key / hash-chain link of elements < MIRCAP
     uint16_t enext[MIRCAP];                         //   (0xffff = end of chain)
     uint64_t seedUsed[NB + 1];                      // BaseAligner::seedUsed bit vector
-    int16_t btAct[BYTE_PATH ? MAX_K + 1 : 1];       // LV backtrace scratch (byte path)
-    int16_t btMatched[BYTE_PATH ? MAX_K + 1 : 1];
-    uint16_t rows[BYTE_PATH ? MAX_K : 1][WAVE];     // byte-path LV rows: (L+2) | action<<12
+    int16_t btAct[BYTE_PATH ? MAX_K + 1 : 0];       // LV backtrace scratch (byte path)
+    int16_t btMatched[BYTE_PATH ? MAX_K + 1 : 0];
+    uint16_t rows[BYTE_PATH ? MAX_K : 0][WAVE];     // byte-path LV rows: (L+2) | action<<12
     GroupLdsT<NW> grp[BYTE_PATH ? 0 : 1];           // scorer of align_kernel<128> / <256>
     // the read's first ELCAP candidate elements (Elem64) live here, not in the HBM arena
     alignas(16) uint32_t eloc[BYTE_PATH ? 1 : ELCAP][16];
 };
-// LV row e (1 <= e < MAX_K) of the bit-plane scorer at rows8[e - 1]
-template <int MAXLEN>
-__device__ __forceinline__ uint8_t (*lv_rows(Lds<MAXLEN> &S))[WAVE] {
+// A CU allocates LDS in units of 1,280 B (tools/gpu/lds_residency.hip, profiles/r17): 20 one-wave
+// workgroups (5 per SIMD at 96 VGPRs) are resident together only at 6 units each, 163,840 / 20 = 8,192 B
+// being 6.4.  At 7 units (7,681..8,960 B) 18 fit and a tenth of the persistent grid waits for the first
+// waves to leave.
+static_assert(sizeof(Lds<128, SHORT_ROWS>) <= 7680, "Lds<128> of the short-row kernel: 6 LDS allocation units, 20 waves per CU");
+static_assert(SHORT_ROWS * WAVE >= 256 * 4 && SHORT_ROWS * WAVE >= SKCAP * 4, "forced_sort's histogram and the staged keys lie in the LV rows");
+// LV row e (1 <= e <= ROWS) of the bit-plane scorer at rows8[e - 1]
+template <int MAXLEN, int ROWS>
+__device__ __forceinline__ uint8_t (*lv_rows(Lds<MAXLEN, ROWS> &S))[WAVE] {
     return reinterpret_cast<uint8_t (*)[WAVE]>(&S.u.sc.rows8[0][0] - WAVE);
 }
 // head of element hash chain h (NONE when empty)
-template <int MAXLEN>
-__device__ __forceinline__ uint32_t head_get(const Lds<MAXLEN> &S, uint32_t h) {
+template <int MAXLEN, int ROWS>
+__device__ __forceinline__ uint32_t head_get(const Lds<MAXLEN, ROWS> &S, uint32_t h) {
     const auto v = S.head[h];
     return v == Lds<MAXLEN>::HEAD_NONE ? NONE : (uint32_t)v;
 }
 // head[h] = e, returning the previous head (NONE when empty); leaders of one insertion step may
 // share a bucket, so the exchange is atomic (a CAS on the dword holding a u16 head)
-template <int MAXLEN>
-__device__ __forceinline__ uint32_t head_exchange(Lds<MAXLEN> &S, uint32_t h, uint32_t e) {
+template <int MAXLEN, int ROWS>
+__device__ __forceinline__ uint32_t head_exchange(Lds<MAXLEN, ROWS> &S, uint32_t h, uint32_t e) {
     if constexpr (Lds<MAXLEN>::BYTE_PATH) {
         return atomicExch(&S.head[h], e);
     } else {
@@ -642,8 +657,8 @@ __device__ __forceinline__ LvOut lv_wave(const Bitmap<NB> &F, int p0, int patter
 
 // Stage genome bytes [g - 64, g + n + 128) into LDS window (4-byte aligned start).
 // Returns w0 such that win[w0 + p] == genome[g + p].
-template <int MAXLEN>
-__device__ __forceinline__ int stage_window(Lds<MAXLEN> &S, const char *genome, uint32_t g, int n) {
+template <int MAXLEN, int ROWS>
+__device__ __forceinline__ int stage_window(Lds<MAXLEN, ROWS> &S, const char *genome, uint32_t g, int n) {
     const int lane = lane_id();
     int64_t start = (int64_t)g - 64;
     int64_t astart = start & ~(int64_t)3;
@@ -873,8 +888,8 @@ __device__ __forceinline__ uint32_t elem_hash(uint32_t key) { return (key * 2654
 
 // find element with `key`; NONE if absent.  Elements < MIRCAP keep (key, next) in LDS
 // (next always points to an older, smaller index), so most walks never touch HBM.
-template <int MAXLEN>
-__device__ __forceinline__ uint32_t chain_find(const KArgs &A, const Lds<MAXLEN> &S, const ElemOf<MAXLEN> *ar, uint32_t key,
+template <int MAXLEN, int ROWS>
+__device__ __forceinline__ uint32_t chain_find(const KArgs &A, const Lds<MAXLEN, ROWS> &S, const ElemOf<MAXLEN> *ar, uint32_t key,
                                                uint32_t cap) {
     uint32_t e = head_get(S, elem_hash(key));
     for (uint32_t steps = 0; e != NONE; steps++) {
@@ -896,23 +911,23 @@ __device__ __forceinline__ uint32_t chain_find(const KArgs &A, const Lds<MAXLEN>
 // on C2 and 5% on C3 in round 3: profiles/r03/ab/compact_sk_ab.txt.)
 // (The asm after the HBM load keeps the two loads apart: merged into one load of a selected
 // pointer they became a flat load, which waits on both the LDS and the vector-memory counters.)
-template <int MAXLEN>
-__device__ __forceinline__ uint32_t sk_get(const KArgs &, const Lds<MAXLEN> &S, const ElemOf<MAXLEN> *ar, uint32_t e) {
+template <int MAXLEN, int ROWS>
+__device__ __forceinline__ uint32_t sk_get(const KArgs &, const Lds<MAXLEN, ROWS> &S, const ElemOf<MAXLEN> *ar, uint32_t e) {
     uint32_t v;
     if (e < SKCAP) v = S.sk[e];
     else { v = ar[e].sortkey; __asm__ volatile("" :: "v"(v)); }
     return v;
 }
-template <int MAXLEN>
-__device__ __forceinline__ void sk_set(const KArgs &, Lds<MAXLEN> &S, ElemOf<MAXLEN> *ar, uint32_t e, uint32_t v) {
+template <int MAXLEN, int ROWS>
+__device__ __forceinline__ void sk_set(const KArgs &, Lds<MAXLEN, ROWS> &S, ElemOf<MAXLEN> *ar, uint32_t e, uint32_t v) {
     if (e < SKCAP) S.sk[e] = v;
     else ar[e].sortkey = v;
 }
 
 // recompute of `owner`'s selection maximum (elements e == owner mod 64), the whole wave
 // scanning that lane's elements 64 at a time
-template <int MAXLEN>
-__device__ __forceinline__ void recompute_lane_max(const KArgs &A, Lds<MAXLEN> &S, const ElemOf<MAXLEN> *ar, int owner) {
+template <int MAXLEN, int ROWS>
+__device__ __forceinline__ void recompute_lane_max(const KArgs &A, Lds<MAXLEN, ROWS> &S, const ElemOf<MAXLEN> *ar, int owner) {
     const int lane = lane_id();
     uint64_t best = 0;
     const uint32_t nElems = S.nElems;

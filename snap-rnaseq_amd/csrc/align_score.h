@@ -349,8 +349,8 @@ struct PassLane {
 };
 
 // One speculative pass over up to G = 64/GS candidates of the list: group gi takes cand[lvIdx[gi]].
-template <int GS, int MAXLEN>
-__device__ __forceinline__ void lv_pass(const KArgs &A, Lds<MAXLEN> &S, const Elem64 *ar, const uint16_t *lvIdx, int m, int k,
+template <int GS, int MAXLEN, int ROWS>
+__device__ __forceinline__ void lv_pass(const KArgs &A, Lds<MAXLEN, ROWS> &S, const Elem64 *ar, const uint16_t *lvIdx, int m, int k,
                                         uint32_t n, PassLane &P, int &e1, int &e2) {
     constexpr int NW = Lds<MAXLEN>::NW;
     GroupLdsT<NW> &G = S.grp[0];
@@ -453,8 +453,8 @@ __device__ __forceinline__ bool cand_needs_lv(uint32_t cw, int k) {
     return a <= k && b <= k - a;
 }
 
-template <int GS, bool EXT, int MAXLEN>
-__device__ __forceinline__ bool pass_apply(const KArgs &A, Lds<MAXLEN> &S, Elem64 *ar, ReadState &st, uint32_t i0,
+template <int GS, bool EXT, int MAXLEN, int ROWS>
+__device__ __forceinline__ bool pass_apply(const KArgs &A, Lds<MAXLEN, ROWS> &S, Elem64 *ar, ReadState &st, uint32_t i0,
                                            uint32_t iEnd, const uint16_t *lvIdx, int m, int k, uint32_t n, uint32_t nb,
                                            uint32_t &lastSlot, bool &lastSkip, int *result) {
     auto &G = S.grp[0];
@@ -669,8 +669,8 @@ __device__ __forceinline__ bool pass_apply(const KArgs &A, Lds<MAXLEN> &S, Elem6
 // in the free tail of the wave's element arena, with an LDS histogram (the idle LV rows).  The
 // pops then read it from the top.  O(n) per pass where the windowed ranks cost O(n^2) per
 // 256-element window.  Returns false (rank path) when the arena tail cannot hold two buffers.
-template <int MAXLEN>
-__device__ __forceinline__ bool forced_sort(const KArgs &A, Lds<MAXLEN> &S, Elem64 *ar, uint32_t nE,
+template <int MAXLEN, int ROWS>
+__device__ __forceinline__ bool forced_sort(const KArgs &A, Lds<MAXLEN, ROWS> &S, Elem64 *ar, uint32_t nE,
                                             const uint64_t *&sorted, uint32_t &nLinked) {
     // the free slots between the elements and the spill blocks at the arena's top
     if (((uint64_t)A.arenaElems - S.nSpill - nE) * sizeof(Elem64) < 16ull * nE + 64) return false;
@@ -837,8 +837,8 @@ _Pragma("unroll") \
 // pair (lv_pair_dist, limits <= 5: 32 positions).  Distances above the limit are encoded 7; at limit 7 a
 // 7 is also an exact distance, which cand_needs_lv still sends through lv_group (7 <= k), so the
 // encoding stays sound: a candidate it lets fail without LV has e1 > k or e2 > k - e1.
-template <int MAXLEN, bool QUAD>
-__device__ __forceinline__ uint32_t forced_filter(const KArgs &A, Lds<MAXLEN> &S, const Elem64 *ar, const ReadState &st,
+template <int MAXLEN, bool QUAD, int ROWS>
+__device__ __forceinline__ uint32_t forced_filter(const KArgs &A, Lds<MAXLEN, ROWS> &S, const Elem64 *ar, const ReadState &st,
                                                   uint32_t n, const uint64_t *fSorted, uint32_t fAvail,
                                                   const uint16_t *order, uint32_t ordBase, uint32_t pos0, uint32_t cnt,
                                                   int k) {
@@ -898,8 +898,8 @@ __device__ __forceinline__ uint32_t forced_filter(const KArgs &A, Lds<MAXLEN> &S
 // Returns true when the read's result is final.  The scorer's LV rows overlay the insertion table
 // (Lds::u), so a call that scored a batch and hands the read back to the seed loop clears the table
 // again; a call that finds no linked element -- most non-forced calls -- has written none of it.
-template <bool EXT, int MAXLEN>
-__device__ __forceinline__ bool score_batched(const KArgs &A, Lds<MAXLEN> &S, Elem64 *ar, ReadState &st, bool force,
+template <bool EXT, int MAXLEN, int ROWS>
+__device__ __forceinline__ bool score_batched(const KArgs &A, Lds<MAXLEN, ROWS> &S, Elem64 *ar, ReadState &st, bool force,
                                            uint32_t n, int *result, uint32_t *flags) {
     const int lane = lane_id();
     auto &G = S.grp[0];
@@ -1136,9 +1136,11 @@ __device__ __forceinline__ bool score_batched(const KArgs &A, Lds<MAXLEN> &S, El
         PH_T(A, tpl);
         uint32_t lastSlot = NONE;   // element of the last candidate reached, and its lps decision
         bool lastSkip = false;
-        // the LV list of a pass (positions into cand, list order) in an LV row the scorer never
-        // reaches at the limits that fill it (k <= 15 uses rows 1..15)
-        uint16_t *lvIdx = reinterpret_cast<uint16_t *>(&S.u.sc.rows8[MAX_K - 2][0]);
+        // the LV list of a pass (positions into cand, list order) at the start of the last LV row, which
+        // the scorer never reaches at the limits that fill it: k <= 15 uses rows 1..15 (ROWS >= 16), and
+        // from k = 16 on a pass has one group, whose entry (lanes 0 and 1 of the row) is outside the band
+        // of row SHORT_ROWS (lanes 15..47)
+        uint16_t *lvIdx = reinterpret_cast<uint16_t *>(&S.u.sc.rows8[ROWS - 1][0]);
         for (uint32_t i0 = 0; i0 < nc;) {
             if (overdue(A, st, 2)) return true;
             const int k = st.scoreLimit < (uint32_t)(MAX_K - 1) ? (int)st.scoreLimit : MAX_K - 1;

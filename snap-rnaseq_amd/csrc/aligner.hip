@@ -24,6 +24,7 @@
 #include "simple_align.h"
 #include "cigar.h"
 #include "internal.h"
+#include "resident_grid.h"
 #include "large_copy.h"
 #include "bam_format.h"
 #include "bgzf.h"
@@ -41,8 +42,8 @@ namespace sgk {
 // ------------------------------------------------------------------ score()
 // BaseAligner::score, BaseAligner.cpp:977-1399.  Returns true iff a final
 // result was produced (written into st / *result).
-template <int MAXLEN, bool EXT>
-__device__ __forceinline__ bool score_wave(const KArgs &A, Lds<MAXLEN> &S, Elem512 *ar, ReadState &st, bool force,
+template <int MAXLEN, bool EXT, int ROWS>
+__device__ __forceinline__ bool score_wave(const KArgs &A, Lds<MAXLEN, ROWS> &S, Elem512 *ar, ReadState &st, bool force,
                                            uint32_t n, const uint32_t (&rbF)[MAXLEN / 64],
                                            const uint32_t (&rbR)[MAXLEN / 64], int *result, uint32_t *flags) {
     constexpr int NB = MAXLEN / 64;
@@ -219,8 +220,8 @@ __device__ __forceinline__ bool score_wave(const KArgs &A, Lds<MAXLEN> &S, Elem5
 // [0, lim0) then the reverse-complement hits [lim0, lim0 + lim1), the order and
 // timestamps of applying the directions one after the other (their elements never
 // coincide: the direction is part of the element key).
-template <int MAXLEN, bool EXT>
-__device__ __forceinline__ void insert_hits(const KArgs &A, Lds<MAXLEN> &S, ElemOf<MAXLEN> *ar, ReadState &st,
+template <int MAXLEN, bool EXT, int ROWS>
+__device__ __forceinline__ void insert_hits(const KArgs &A, Lds<MAXLEN, ROWS> &S, ElemOf<MAXLEN> *ar, ReadState &st,
                                             uint32_t lim0, uint32_t lim1, uint32_t off0, uint32_t off1,
                                             const uint32_t *list0, const uint32_t *list1, uint32_t single0,
                                             uint32_t single1, uint32_t numWeightLists, uint32_t minLoc,
@@ -427,8 +428,8 @@ __device__ __forceinline__ void defer_read(const KArgs &A, uint32_t r) {
 
 // ------------------------------------------------------------- AlignRead
 // EXT: windowed search / multi-hit export compiled in (snapgpu_align_batch_ex)
-template <int MAXLEN, bool EXT>
-__device__ __forceinline__ void align_one(const KArgs &A, Lds<MAXLEN> &S, ElemOf<MAXLEN> *ar, uint32_t r) {
+template <int MAXLEN, bool EXT, int ROWS>
+__device__ __forceinline__ void align_one(const KArgs &A, Lds<MAXLEN, ROWS> &S, ElemOf<MAXLEN> *ar, uint32_t r) {
     constexpr int NB = MAXLEN / 64;
     const int lane = lane_id();
     PH_T(A, tsetup);
@@ -763,13 +764,15 @@ __device__ __forceinline__ void align_one(const KArgs &A, Lds<MAXLEN> &S, ElemOf
 #endif
 }
 
-template <int MAXLEN, bool EXT>
+template <int MAXLEN, bool EXT, int ROWS = FULL_ROWS>
 // amdgpu_waves_per_eu: <128> at 5 waves/SIMD (<= 96 VGPRs: the forced-mode prefilter's peak costs
 // ~10 VGPRs of spills around it, 2.5 % faster than 4 waves without them,
 // profiles/r05/ab/prefilter_pairs_r05l.txt), <256> at 4, <512> at 3 (<= 168 VGPRs: a few cold
 // spills are cheaper than dropping to 2 waves/SIMD).
+// ROWS: the LV row capacity (align_device.h); SHORT_ROWS only for aligners whose score limit never
+// passes it (snapgpu_aligner_create), where <128>'s LDS then lets all 20 waves of a CU be resident.
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MAXLEN <= 128 ? 5 : (MAXLEN <= 256 ? 4 : 3)))) void align_kernel(KArgs A) {
-    __shared__ Lds<MAXLEN> S;
+    __shared__ Lds<MAXLEN, ROWS> S;
     ElemOf<MAXLEN> *ar = reinterpret_cast<ElemOf<MAXLEN> *>(A.arena) + (uint64_t)blockIdx.x * A.arenaElems;
     const int lane = lane_id();
     uint32_t total = A.readList ? uni(*A.readCount) : A.nReads;
@@ -1267,6 +1270,9 @@ struct snapgpu_aligner {
     uint64_t arenaElems = 0;      // worst case per read: (maxSeeds + 2) * maxHits (+ 64)
     uint64_t arenaCap = 0;        // per wave in the main passes (= arenaElems unless that cannot fit the grid)
     int grid = 0, grid256 = 0, grid512 = 0, gridBig = 0;
+    // resident workgroups per CU of each persistent kernel (resident_grid.h) behind those grids
+    int perCU128 = 0, perCU256 = 0, perCU512 = 0, perCUSimple = 0, perCUCigar = 0;
+    bool shortRows = false;       // pass 1 runs align_kernel<128, EXT, SHORT_ROWS>: maxK + extraSearchDepth <= SHORT_ROWS
     // snapgpu_align_batch chunk (SNAPGPU_CHUNK_READS): a streaming caller's 1M-read batches go
     // as one chunk each, alternating lanes (fewest persistent-kernel tails; A/B in
     // profiles/r02/ab/chunk_size_slots.txt); resident runs keep 2^18-read chunks over both lanes
@@ -2088,18 +2094,16 @@ snapgpu_aligner_t *snapgpu_aligner_create(int device, const snapgpu_index_t *idx
     // persistent grid: waves resident on the device; element arena per wave and lane
     hipDeviceProp_t prop;
     hipGetDeviceProperties(&prop, device);
-    int perCU = 0;
-    hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, (const void *)align_kernel<128, false>, 64, 0);
-    if (perCU <= 0) perCU = 8;
-    // occupancy test hook: fewer resident waves per CU than the kernel's resources allow
-    // (the same code, LDS caps and registers; only the persistent grid shrinks)
-    if (const char *t = getenv("SNAPGPU_WAVES_PER_CU"); t && atoi(t) > 0) perCU = std::min(perCU, atoi(t));
-    a->grid = prop.multiProcessorCount * perCU;
-    {
-        int perCUs = 0;
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCUs, (const void *)simple_align_kernel, 64, 0);
-        a->gridSimple = prop.multiProcessorCount * (perCUs > 0 ? perCUs : 8);
-    }
+    // The score limit never passes maxK + extraSearchDepth: at SHORT_ROWS or below, pass 1 runs the
+    // short-row kernel, whose LDS lets 20 waves per CU be resident (18 on the full rows; resident_grid.h).
+    // The grids are what is resident (SNAPGPU_WAVES_PER_CU, a test hook, caps them: the same code, LDS
+    // caps and registers; only the persistent grids shrink).
+    a->shortRows = params->maxK + params->extraSearchDepth <= (uint32_t)SHORT_ROWS;
+    a->perCU128 = a->shortRows ? resident_blocks_per_cu((const void *)align_kernel<128, false, SHORT_ROWS>, 64, prop, 8)
+                               : resident_blocks_per_cu((const void *)align_kernel<128, false>, 64, prop, 8);
+    a->grid = prop.multiProcessorCount * a->perCU128;
+    a->perCUSimple = resident_blocks_per_cu((const void *)simple_align_kernel, 64, prop, 8);
+    a->gridSimple = prop.multiProcessorCount * a->perCUSimple;
     uint32_t maxSeeds = params->maxSeedsToUse ? params->maxSeedsToUse
                                               : (uint32_t)(params->maxSeedCoverage * params->maxReadSize / idx->seedLen);
     a->arenaElems = (uint64_t)(maxSeeds + 2) * params->maxHitsToConsider + 64;
@@ -2124,15 +2128,12 @@ snapgpu_aligner_t *snapgpu_aligner_create(int device, const snapgpu_index_t *idx
             (e = hipMalloc(&L.bigArena, (uint64_t)a->gridBig * a->arenaElems * sizeof(Elem512))) != hipSuccess)
             return fail("big arena", e);
     }
-    int perCU256 = 0;   // passes 2 and 3 (deferred reads) reuse the arenas of the first a->grid blocks
-    hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU256, (const void *)align_kernel<256, false>, 64, 0);
-    if (perCU256 <= 0) perCU256 = 4;
-    a->grid256 = prop.multiProcessorCount * perCU256;
+    // passes 2 and 3 (deferred reads) reuse the arenas of the first a->grid blocks
+    a->perCU256 = resident_blocks_per_cu((const void *)align_kernel<256, false>, 64, prop, 4);
+    a->grid256 = prop.multiProcessorCount * a->perCU256;
     if (a->grid256 > a->grid) a->grid256 = a->grid;
-    int perCU512 = 0;
-    hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU512, (const void *)align_kernel<512, false>, 64, 0);
-    if (perCU512 <= 0) perCU512 = 4;
-    a->grid512 = prop.multiProcessorCount * perCU512;
+    a->perCU512 = resident_blocks_per_cu((const void *)align_kernel<512, false>, 64, prop, 4);
+    a->grid512 = prop.multiProcessorCount * a->perCU512;
     if (a->grid512 > a->grid) a->grid512 = a->grid;
     if (const char *t = getenv("SNAPGPU_PHASES"); t && atoi(t)) {
         const size_t pb = (size_t)a->grid * PH_SLOTS * sizeof(unsigned long long);
@@ -2328,7 +2329,10 @@ static int launch_passes(snapgpu_aligner_t *a, int li, const PassIO &io, const A
     HIPCHK(hipEventRecord(ev.e[4], fs));
     HIPCHK(hipStreamWaitEvent(L.stream, ev.e[4], 0));
     HIPCHK(hipEventRecord(ev.e[5], L.stream));
-    if (ext) hipLaunchKernelGGL((align_kernel<128, true>), dim3(grid), dim3(64), 0, L.stream, A);
+    if (a->shortRows) {
+        if (ext) hipLaunchKernelGGL((align_kernel<128, true, SHORT_ROWS>), dim3(grid), dim3(64), 0, L.stream, A);
+        else hipLaunchKernelGGL((align_kernel<128, false, SHORT_ROWS>), dim3(grid), dim3(64), 0, L.stream, A);
+    } else if (ext) hipLaunchKernelGGL((align_kernel<128, true>), dim3(grid), dim3(64), 0, L.stream, A);
     else hipLaunchKernelGGL((align_kernel<128, false>), dim3(grid), dim3(64), 0, L.stream, A);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(ev.e[1], L.stream));
@@ -3357,14 +3361,42 @@ static CigarArgs cigar_args(snapgpu_aligner_t *a, snapgpu_device_reads_t *d, int
 }
 
 // cigar_kernel over n reads on the aligner's side stream (timing events around it)
-static int cigar_kernel_launch(snapgpu_aligner_t *a, const CigarArgs &C, uint64_t n) {
+// cigar_kernel's persistent grid, sized on first use
+static int cigar_grid(snapgpu_aligner_t *a) {
     if (!a->cigarGrid) {
         hipDeviceProp_t prop;
         HIPCHK(hipGetDeviceProperties(&prop, a->device));
-        int perCU = 0;
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, (const void *)cigar_kernel, 64, 0);
-        a->cigarGrid = prop.multiProcessorCount * (perCU > 0 ? perCU : 8);
+        a->perCUCigar = resident_blocks_per_cu((const void *)cigar_kernel, 64, prop, 8);
+        a->cigarGrid = prop.multiProcessorCount * a->perCUCigar;
     }
+    return SNAPGPU_OK;
+}
+
+int snapgpu_aligner_debug_grids(snapgpu_aligner_t *a, snapgpu_grids_t *g) {
+    if (!a || !g) { snapgpu::setError("debug_grids: null"); return SNAPGPU_EINVAL; }
+    HIPCHK(hipSetDevice(a->device));
+    if (int rc = cigar_grid(a)) return rc;
+    hipDeviceProp_t prop;
+    HIPCHK(hipGetDeviceProperties(&prop, a->device));
+    g->computeUnits = (uint32_t)prop.multiProcessorCount;
+    g->shortRows = a->shortRows ? 1u : 0u;
+    g->perCU128 = (uint32_t)a->perCU128; g->grid128 = (uint32_t)a->grid;
+    g->perCU256 = (uint32_t)a->perCU256; g->grid256 = (uint32_t)a->grid256;
+    g->perCU512 = (uint32_t)a->perCU512; g->grid512 = (uint32_t)a->grid512;
+    g->perCUSimple = (uint32_t)a->perCUSimple; g->gridSimple = (uint32_t)a->gridSimple;
+    g->perCUCigar = (uint32_t)a->perCUCigar; g->gridCigar = (uint32_t)a->cigarGrid;
+    hipFuncAttributes fa;
+    HIPCHK(a->shortRows ? hipFuncGetAttributes(&fa, (const void *)align_kernel<128, false, SHORT_ROWS>)
+                        : hipFuncGetAttributes(&fa, (const void *)align_kernel<128, false>));
+    g->lds128 = (uint32_t)fa.sharedSizeBytes;
+    g->ldsUnit = (uint32_t)LDS_ALLOC_UNIT;
+    g->ldsPerCU = (uint32_t)prop.maxSharedMemoryPerMultiProcessor;
+    g->reserved = 0;
+    return SNAPGPU_OK;
+}
+
+static int cigar_kernel_launch(snapgpu_aligner_t *a, const CigarArgs &C, uint64_t n) {
+    if (int rc = cigar_grid(a)) return rc;
     int grid = a->cigarGrid;
     if ((uint64_t)grid > n) grid = (int)n;
     if (grid == 0) return SNAPGPU_OK;

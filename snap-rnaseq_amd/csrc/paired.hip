@@ -35,6 +35,7 @@
 #include "bucket_table.h"
 #include "order_long.h"
 #include "internal.h"
+#include "resident_grid.h"
 
 int snapgpu_internal_index_args(const snapgpu_aligner_t *a, sgk::KArgs *A, int *device);
 void snapgpu_internal_fill_tables(sgk::DevTables *t, uint32_t seedLen);
@@ -931,6 +932,7 @@ struct snapgpu_paired_aligner {
     hipStream_t stream = nullptr;
     PassPool pass[3];                      // [0] passes 1 and 1b, [1] pass 3 (the reference's pools), [2] pass 2
     int grid256 = 0;                       // pass 1b (<256>) grid: at most pass[0].grid (its pools)
+    int computeUnits = 0, perCU[3] = {};   // resident workgroups per CU of paired_kernel<128> / <256> / <512>: the grids' source
     uint32_t refPool = 0, maxSeedsCmd = 0;
     uint32_t *dCounter = nullptr;          // [0] pass 1 queue, [1] pass 3 queue, [2] pass-1 defer count,
                                            // [3] pass 2 queue, [4] pass-2 defer count, [5] pass 1b queue,
@@ -1178,20 +1180,17 @@ snapgpu_paired_aligner_t *snapgpu_paired_aligner_create(int device, const snapgp
     pa->refPool = (uint32_t)std::min<uint64_t>(pool, p.maxCandidatePoolSize);
     hipDeviceProp_t prop;
     if ((e = hipGetDeviceProperties(&prop, device)) != hipSuccess) return fail("props", e);
-    int perCU = 0;
-    hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, (const void *)paired_kernel<128>, 64, 0);
-    if (perCU <= 0) perCU = 4;
+    // persistent grids: the workgroups resident per CU (resident_grid.h)
+    const int perCU = sgk::resident_blocks_per_cu((const void *)paired_kernel<128>, 64, prop, 4);
     uint32_t c1 = std::min<uint32_t>(pa->refPool, 4096);
     if (const char *t = getenv("SNAPGPU_PAIRED_POOL1"); t && atoi(t) > 1) c1 = std::min<uint32_t>(pa->refPool, (uint32_t)atoi(t));
     if (allocPass(pa->pass[0], prop.multiProcessorCount * perCU, c1, std::max<uint32_t>(1, std::min(pa->refPool / 2, c1 / 2)), c1))
         { snapgpu_paired_aligner_free(pa); return nullptr; }
-    int perCU256 = 0;
-    hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU256, (const void *)paired_kernel<256>, 64, 0);
-    if (perCU256 <= 0) perCU256 = 2;
+    const int perCU256 = sgk::resident_blocks_per_cu((const void *)paired_kernel<256>, 64, prop, 2);
     pa->grid256 = std::min(prop.multiProcessorCount * perCU256, pa->pass[0].grid);
-    int perCU2 = 0;
-    hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU2, (const void *)paired_kernel<512>, 64, 0);
-    if (perCU2 <= 0) perCU2 = 2;
+    const int perCU2 = sgk::resident_blocks_per_cu((const void *)paired_kernel<512>, 64, prop, 2);
+    pa->computeUnits = prop.multiProcessorCount;
+    pa->perCU[0] = perCU; pa->perCU[1] = perCU256; pa->perCU[2] = perCU2;
     // pass 2 pools hold the reference's whole pool; as many waves as fit in 8 GB
     const uint64_t stride2 = (uint64_t)pa->refPool * sizeof(Cand) + (uint64_t)pa->refPool * sizeof(Mate) +
                              (uint64_t)pa->refPool * sizeof(Anchor) + 256;
@@ -1211,6 +1210,16 @@ snapgpu_paired_aligner_t *snapgpu_paired_aligner_create(int device, const snapgp
         pa->grid256 = std::min(pa->grid256, g);
     }
     return pa;
+}
+
+int snapgpu_paired_aligner_debug_grids(const snapgpu_paired_aligner_t *pa, uint32_t out[8]) {
+    if (!pa || !out) { snapgpu::setError("paired debug_grids: null"); return SNAPGPU_EINVAL; }
+    out[0] = (uint32_t)pa->computeUnits;
+    out[1] = (uint32_t)pa->perCU[0]; out[2] = (uint32_t)pa->pass[0].grid;
+    out[3] = (uint32_t)pa->perCU[1]; out[4] = (uint32_t)pa->grid256;
+    out[5] = (uint32_t)pa->perCU[2]; out[6] = (uint32_t)pa->pass[2].grid;
+    out[7] = (uint32_t)pa->pass[1].grid;
+    return SNAPGPU_OK;
 }
 
 void snapgpu_paired_aligner_free(snapgpu_paired_aligner_t *pa) {

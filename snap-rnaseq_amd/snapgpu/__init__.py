@@ -493,6 +493,12 @@ class BaseAligner:
         """Test hook: trip this aligner's device watchdog when read `read_index` of a batch starts."""
         _check(lib().snapgpu_aligner_debug_trip(self._h, int(read_index)), "debug_trip")
 
+    def debug_grids(self):
+        """Test accessor: the persistent kernels' grids and what they were sized from (snapgpu_grids_t)."""
+        g = _ffi.Grids()
+        _check(lib().snapgpu_aligner_debug_grids(self._h, C.byref(g)), "debug_grids")
+        return {f: getattr(g, f) for f, _ in g._fields_}
+
     def copy_peak_ms(self, nbytes):
         """Diagnostic: best-of-3 time (ms) of a streaming copy of nbytes (read nbytes + write nbytes)."""
         ms = C.c_double()
@@ -723,6 +729,13 @@ class PairedAligner:
 
     def intersect(self, reads0, reads1):
         return self._run(lib().snapgpu_paired_intersect_batch, reads0, reads1, "paired_intersect_batch")
+
+    def debug_grids(self):
+        """Test accessor (snapgpu_paired_aligner_debug_grids): the pair kernels' grids and their source."""
+        out = (C.c_uint32 * 8)()
+        _check(lib().snapgpu_paired_aligner_debug_grids(self._h, out), "paired debug_grids")
+        names = ("computeUnits", "perCU128", "grid128", "perCU256", "grid256", "perCU512", "grid512", "gridPools")
+        return dict(zip(names, (int(v) for v in out)))
 
     def __del__(self):
         if getattr(self, "_h", None):

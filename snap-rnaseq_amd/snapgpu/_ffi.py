@@ -234,6 +234,12 @@ class AlignerStats(C.Structure):
 
 assert C.sizeof(Result) == 64, C.sizeof(Result)
 
+class Grids(C.Structure):   # snapgpu_grids_t
+    _fields_ = [(f, C.c_uint32) for f in (
+        "computeUnits", "shortRows", "perCU128", "grid128", "perCU256", "grid256", "perCU512", "grid512",
+        "perCUSimple", "gridSimple", "perCUCigar", "gridCigar", "lds128", "ldsUnit", "ldsPerCU", "reserved")]
+
+
 class BucketInfo(C.Structure):   # snapgpu_bucket_info_t
     _fields_ = [("nSlots", C.c_uint64), ("nKeys", C.c_uint64), ("nBuckets", C.c_uint64),
                 ("nOverflowBuckets", C.c_uint64), ("maxDisplacement", C.c_uint64), ("bytes", C.c_uint64),
@@ -315,6 +321,7 @@ _PROTOS = [
     ("snapgpu_aligner_set_overlap", C.c_int, [C.c_void_p, C.c_int]),
     ("snapgpu_aligner_set_simple_pass", C.c_int, [C.c_void_p, C.c_int]),
     ("snapgpu_aligner_debug_trip", C.c_int, [C.c_void_p, C.c_uint32]),
+    ("snapgpu_aligner_debug_grids", C.c_int, [C.c_void_p, C.POINTER(Grids)]),
     ("snapgpu_source_sha256", C.c_char_p, []),
     ("snapgpu_phase_cycles", C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_uint32, C.c_int]),
     ("snapgpu_aligner_name", C.c_char_p, [C.c_void_p]),
@@ -429,6 +436,7 @@ _PROTOS += [
     ("snapgpu_paired_params_default", None, [C.POINTER(PairedParams)]),
     ("snapgpu_paired_aligner_create", C.c_void_p, [C.c_int, C.c_void_p, C.POINTER(PairedParams)]),
     ("snapgpu_paired_aligner_free", None, [C.c_void_p]),
+    ("snapgpu_paired_aligner_debug_grids", C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
     ("snapgpu_paired_align_batch", C.c_int, [C.c_void_p, C.POINTER(Reads), C.POINTER(Reads), C.c_void_p]),
     ("snapgpu_paired_intersect_batch", C.c_int, [C.c_void_p, C.POINTER(Reads), C.POINTER(Reads), C.c_void_p]),
     ("snapgpu_paired_aligner_single", C.c_void_p, [C.c_void_p]),

@@ -20,9 +20,10 @@ import shutil
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-KERNELS = {"align": "align_kernel<128, false>", "simple": "simple_align_kernel", "lookup": "seed_lookup_kernel", "copy": "copy_peak_kernel",
+# (the align kernels by name prefix: they carry their LV row capacity as a third template argument since round 17)
+KERNELS = {"align": "align_kernel<128, false", "simple": "simple_align_kernel", "lookup": "seed_lookup_kernel", "copy": "copy_peak_kernel",
            "paired": "paired_kernel<128>",
-           "gather": "gather_peak_kernel", "cigar": "cigar_kernel", "align512": "align_kernel<512, false>"}
+           "gather": "gather_peak_kernel", "cigar": "cigar_kernel", "align512": "align_kernel<512, false"}
 
 
 def kname(name):
@@ -135,7 +136,7 @@ def main(src, dst):
         per_read = {x: c[x] / reads_per_launch for x in c}
         a["per_read"] = per_read
         traffic = {"lib_sha256": out["lib_sha256"], "kernel_source_sha256": out["kernel_source_sha256"],
-                   "kernel": KERNELS["align"] + (" + " + KERNELS["simple"] if s else ""), "reads_per_dispatch": reads_per_launch,
+                   "kernel": KERNELS["align"] + ">" + (" + " + KERNELS["simple"] if s else ""), "reads_per_dispatch": reads_per_launch,
                    "hbm_bytes_per_read": (hb.get("fetch", 0) + hb.get("write", 0)) / reads_per_launch,
                    "fetch_bytes_per_read": hb.get("fetch", 0) / reads_per_launch,
                    "write_bytes_per_read": hb.get("write", 0) / reads_per_launch,

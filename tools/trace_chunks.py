@@ -7,8 +7,9 @@ started inside c's run) and where pass 0 / the simple pass of c+1 end relative t
 import csv
 import sys
 
-KERNELS = {"seed_lookup_kernel": "p0", "simple_align_kernel": "simple", "align_kernel<128, false>": "k128",
-           "align_kernel<256, false>": "k256"}
+# (name prefixes: the align kernels carry their LV row capacity as a third template argument since round 17)
+KERNELS = {"seed_lookup_kernel": "p0", "simple_align_kernel": "simple", "align_kernel<128, false": "k128",
+           "align_kernel<256, false": "k256"}
 rows = {v: [] for v in KERNELS.values()}
 queues = {}
 for r in csv.DictReader(open(sys.argv[1])):
