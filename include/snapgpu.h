@@ -377,6 +377,21 @@ uint32_t snapgpu_fastq_tile_bytes(void);   /* bytes of text one workgroup scans 
 int snapgpu_device_reads_peek(snapgpu_aligner_t *a, snapgpu_device_reads_t *d, uint64_t *n, uint64_t *bytes,
                               uint32_t *maxLen, uint64_t *extentHash, uint64_t *offsets, uint32_t *lengths,
                               char *bases, char *quals);
+/* A batch made by snapgpu_fastq_upload* also keeps, in device memory of its own, what the SAM / BAM
+ * calls below otherwise take from the host batch: the packed ids with their offsets and lengths, the
+ * front clips and unclipped lengths, the bases and qualities past the largest clipped end, and the
+ * longest unclipped read and longest id.  Those calls then accept reads == NULL (see
+ * snapgpu_sam_resident), with or without SNAPGPU_FASTQ_HOST_BATCH.  A batch from snapgpu_reads_upload
+ * keeps none of this.
+ * snapgpu_device_reads_ids_download copies the ids back (waits; off the critical path of a caller
+ * that formats on the device): the packed blob under the size contract of snapgpu_sam_download
+ * (*used = its bytes, SNAPGPU_EINVAL if cap is too small), and, where the pointers are not NULL,
+ * n entries each of idOffsets, idLengths, frontClipped and unclippedLength -- the fields of that name
+ * of the host batch.  The two clip arrays are left untouched for a batch uploaded with clipping 0.
+ * SNAPGPU_EINVAL for a batch without resident ids. */
+int snapgpu_device_reads_ids_download(snapgpu_aligner_t *a, snapgpu_device_reads_t *d, char *ids, uint64_t cap,
+                                      uint64_t *used, uint64_t *idOffsets, uint32_t *idLengths,
+                                      uint32_t *frontClipped, uint32_t *unclippedLength);
 
 /* Timing of the dominant kernel (HIP events on the stream it ran on), in ms, for the last
  * snapgpu_align_resident / snapgpu_align_batch call.  snapgpu_align_batch pipelines its reads
@@ -581,7 +596,16 @@ int snapgpu_sam_format_clipped(const snapgpu_index_t *idx, const snapgpu_reads_t
  * state is used.  ids/idOffsets/idLengths NULL => reads->ids...; asynchronous on the side stream
  * (the next snapgpu_align_resident waits for it before it rewrites the records).  SNAPGPU_EINVAL:
  * no snapgpu_cigar_resident before, a reads batch that does not match d, an unclipped read longer
- * than 1024 bases, no ids at all. */
+ * than 1024 bases, no ids at all.
+ * reads == NULL: the batch's own resident ids and clip state, which only snapgpu_fastq_upload* leaves
+ * (SNAPGPU_EINVAL for a batch from snapgpu_reads_upload).  Nothing per read is then uploaded: the
+ * kernels read the ids, clip arrays and unclipped bases / qualities the parser left in device memory,
+ * the text bound comes from the batch's totals, and the 1024-base limit is checked against the
+ * longest unclipped read found at upload time.  There is no extent check (nothing to compare).  The
+ * text is byte-identical to the call with the host batch.  Caller ids (ids, idOffsets and idLengths
+ * all non-NULL) are still taken, and uploaded, with reads == NULL.  Calls with and without reads may
+ * alternate on one batch.  The same holds for snapgpu_sam_resident_sorted and snapgpu_bam_resident /
+ * _sorted (whose 254-byte id limit is checked against the longest id found at upload time). */
 int snapgpu_sam_resident(snapgpu_aligner_t *a, snapgpu_device_reads_t *d, const snapgpu_reads_t *reads,
                          const char *ids, const uint64_t *idOffsets, const uint32_t *idLengths,
                          const char *readGroup);

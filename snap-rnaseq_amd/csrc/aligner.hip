@@ -1183,6 +1183,7 @@ struct SamState {
     bool idsCached = false;   // aux holds the batch's own ids (reads->ids), with this read group:
     std::string cachedRg;
     bool cachedHasRg = false;
+    bool cachedDevForm = false;   // ... laid out for a call without a host batch (reads == NULL): no ids, no clip arrays
     uint64_t n = 0, textBound = 0;
     bool ran = false;
     // before the length pass, after the check; after the length pass, after the scan; after the sort step
@@ -1222,6 +1223,17 @@ struct snapgpu_device_reads {
     int device = 0;
     uint64_t bytes = 0;       // bases / quals bytes uploaded: the largest clipped end
     uint64_t extentHash = 0;  // of the offsets and lengths uploaded (snapgpu_sam_resident checks its batch)
+    // What the device FASTQ parser leaves for the SAM / BAM calls without a host batch (reads == NULL);
+    // a batch from snapgpu_reads_upload has none of it.
+    bool hasIds = false;
+    int clipping = 0;             // 0: no clip arrays (front / unclipped below are not used)
+    char *dIds = nullptr;         // the packed ids, idTotal + 16 bytes
+    char *dMeta = nullptr;        // one allocation: idStart, idLen, front, baseLen (16-byte aligned each)
+    const uint64_t *dIdStart = nullptr;
+    const uint32_t *dIdLen = nullptr, *dFront = nullptr, *dUnclipped = nullptr;
+    char *dTail = nullptr;        // bases, then qualities, of [bytes, total): what the zeroing from `bytes` on took
+    uint64_t total = 0, idTotal = 0;        // bytes of all unclipped reads, of all ids
+    uint32_t maxUnclipped = 0, maxIdLen = 0;
     SamState sam;
     BamState bam;
     BgzfState bgzf;
@@ -1333,7 +1345,7 @@ struct snapgpu_aligner {
     // device FASTQ parser (snapgpu_fastq_upload): the text, newline positions and per-record arrays,
     // grow-only; the pinned staging of the text upload (two chunks in flight); the last call's times
     struct FastqState {
-        ExBuf text, counts, tileStart, sums, nl, rec, baseStart, idStart, sums2, tot, ids;
+        ExBuf text, counts, tileStart, sums, nl, rec, baseStart, idStart, sums2, tot;
         void *pin[2] = {};
         hipEvent_t pinDone[2] = {};
         hipEvent_t ev[9] = {};   // 0-2 count, scan; 3-6 line starts, record pass, scans; 7-8 copy pass
@@ -1965,7 +1977,7 @@ void snapgpu_aligner_free(snapgpu_aligner_t *a) {
         if (a->samPinDone[k]) hipEventDestroy(a->samPinDone[k]);
     }
     for (auto *b : {&a->fq.text, &a->fq.counts, &a->fq.tileStart, &a->fq.sums, &a->fq.nl, &a->fq.rec, &a->fq.baseStart,
-                    &a->fq.idStart, &a->fq.sums2, &a->fq.tot, &a->fq.ids})
+                    &a->fq.idStart, &a->fq.sums2, &a->fq.tot})
         devFree(a, b->p);
     for (int k = 0; k < 2; k++) {
         if (!a->failed) hostPinnedFree(a->fq.pin[k]);
@@ -2194,6 +2206,7 @@ void snapgpu_device_reads_free(snapgpu_device_reads_t *d) {
     devFree(a, d->dBases); devFree(a, d->dQuals); devFree(a, d->dOffsets); devFree(a, d->dLengths);
     devFree(a, d->dOut); devFree(a, d->dDefer); devFree(a, d->dSeeds);
     devFree(a, d->dCigEd); devFree(a, d->dCigN); devFree(a, d->dCigOps);
+    devFree(a, d->dIds); devFree(a, d->dMeta); devFree(a, d->dTail);
     if (a && a->samLast == &d->sam) const_cast<snapgpu_aligner_t *>(a)->samLast = nullptr;
     samStateFree(a, d->sam);
     if (a && a->bamLast == &d->bam) const_cast<snapgpu_aligner_t *>(a)->bamLast = nullptr;
@@ -3482,6 +3495,14 @@ struct SamHostIn {
     const uint32_t *idLengths = nullptr;
     const uint32_t *front = nullptr, *unclipped = nullptr;
     const char *rg = nullptr;
+    // the device form (a resident batch's own state, no host batch): what is set here is already in
+    // device memory and is pointed at, not uploaded
+    const char *dIds = nullptr;            // with dIdOffsets / dIdLengths, when ids is null
+    const uint64_t *dIdOffsets = nullptr;
+    const uint32_t *dIdLengths = nullptr;
+    const uint32_t *dFront = nullptr, *dUnclipped = nullptr;
+    bool device = false;                   // lengths is null: the bound comes from the totals below
+    uint64_t idTotal = 0, baseTotal = 0;   // bytes of all ids (the caller's, if it passed ids), of all unclipped reads
 };
 
 // Upload H's arrays, the piece names and the read group into S.aux (unless S still holds them:
@@ -3502,14 +3523,20 @@ static int samPrepare(snapgpu_aligner_t *a, SamState &S, const SamHostIn &H, boo
     // per line: flags, POS, MAPQ, tabs, mate fields, tags and NM (< 64), RNAME, two soft clips and
     // SNAPGPU_CIGAR_MAX_OPS ops of at most 11 bytes each
     const uint64_t perLine = 64 + maxName + (H.rg ? 6 + rgLen : 0) + 22 + 11ull * SNAPGPU_CIGAR_MAX_OPS;
-    for (uint64_t i = 0; i < n; i++) {
-        idBytes = std::max<uint64_t>(idBytes, H.idOffsets[i] + H.idLengths[i]);
-        const uint32_t len = H.unclipped ? H.unclipped[i] : H.lengths[i];
-        bound += H.idLengths[i] + 2ull * std::min(len, samline::kMaxSeq) + perLine;
+    if (H.ids)
+        for (uint64_t i = 0; i < n; i++) idBytes = std::max<uint64_t>(idBytes, H.idOffsets[i] + H.idLengths[i]);
+    if (H.device) {
+        bound = H.idTotal + 2 * H.baseTotal + n * perLine;
+    } else {
+        for (uint64_t i = 0; i < n; i++) {
+            const uint32_t len = H.unclipped ? H.unclipped[i] : H.lengths[i];
+            bound += H.idLengths[i] + 2ull * std::min(len, samline::kMaxSeq) + perLine;
+        }
     }
     S.textBound = bound;
     auto al16 = [](uint64_t x) { return (x + 15) & ~15ull; };
-    const uint64_t oIdOff = 0, oIdLen = al16(oIdOff + n * 8), oFront = al16(oIdLen + n * 4),
+    const uint64_t nIds = H.ids ? n : 0;   // the id arrays ride in aux only when they come from the host
+    const uint64_t oIdOff = 0, oIdLen = al16(oIdOff + nIds * 8), oFront = al16(oIdLen + nIds * 4),
                    oFull = al16(oFront + (H.unclipped ? n * 4 : 0)), oOff = al16(oFull + (H.unclipped ? n * 4 : 0)),
                    oLen = al16(oOff + (H.offsets ? n * 8 : 0)), oNameOff = al16(oLen + (H.offsets ? n * 4 : 0)),
                    oNames = al16(oNameOff + nameOff.size() * 4), oSortBase = al16(oNames + names.size()),
@@ -3521,8 +3548,7 @@ static int samPrepare(snapgpu_aligner_t *a, SamState &S, const SamHostIn &H, boo
         S.hAux.assign(bytes, 0);
         char *h = S.hAux.data();
         if (n) {
-            memcpy(h + oIdOff, H.idOffsets, n * 8);
-            memcpy(h + oIdLen, H.idLengths, n * 4);
+            if (nIds) { memcpy(h + oIdOff, H.idOffsets, n * 8); memcpy(h + oIdLen, H.idLengths, n * 4); }
             if (H.unclipped) { memcpy(h + oFront, H.front, n * 4); memcpy(h + oFull, H.unclipped, n * 4); }
             if (H.offsets) { memcpy(h + oOff, H.offsets, n * 8); memcpy(h + oLen, H.lengths, n * 4); }
         }
@@ -3538,10 +3564,10 @@ static int samPrepare(snapgpu_aligner_t *a, SamState &S, const SamHostIn &H, boo
         HIPCHK(hipStreamSynchronize(a->copyStream));
     }
     const char *d = (const char *)S.aux.p;
-    A.idOffsets = (const uint64_t *)(d + oIdOff);
-    A.idLengths = (const uint32_t *)(d + oIdLen);
-    A.front = H.unclipped ? (const uint32_t *)(d + oFront) : nullptr;
-    A.unclipped = H.unclipped ? (const uint32_t *)(d + oFull) : nullptr;
+    A.idOffsets = H.ids ? (const uint64_t *)(d + oIdOff) : H.dIdOffsets;
+    A.idLengths = H.ids ? (const uint32_t *)(d + oIdLen) : H.dIdLengths;
+    A.front = H.unclipped ? (const uint32_t *)(d + oFront) : H.dFront;
+    A.unclipped = H.unclipped ? (const uint32_t *)(d + oFull) : H.dUnclipped;
     if (H.offsets) { A.offsets = (const uint64_t *)(d + oOff); A.lengths = (const uint32_t *)(d + oLen); }
     A.pieceOffsets = a->dPieces;
     A.pieceNameOff = (const uint32_t *)(d + oNameOff);
@@ -3550,7 +3576,7 @@ static int samPrepare(snapgpu_aligner_t *a, SamState &S, const SamHostIn &H, boo
     A.nPieces = (int32_t)g.pieceOffsets.size();
     A.rg = H.rg ? d + oRg : nullptr;
     A.rgLen = rgLen;
-    A.ids = d + oIds;
+    A.ids = H.ids ? d + oIds : H.dIds;
     return SNAPGPU_OK;
 }
 
@@ -3717,29 +3743,51 @@ static int samResident(snapgpu_aligner_t *a, snapgpu_device_reads_t *d, const sn
                        const char *ids, const uint64_t *idOffsets, const uint32_t *idLengths,
                        const char *readGroup, bool sorted, bool bam = false, int32_t nmCarryIn = 0) {
     const std::string who = bam ? "bam_resident" : "sam_resident";
-    if (!a || !d || !reads) { snapgpu::setError(who + ": null argument"); return SNAPGPU_EINVAL; }
+    if (!a || !d) { snapgpu::setError(who + ": null argument"); return SNAPGPU_EINVAL; }
     if (a->failed) { snapgpu::setError("aligner failed earlier (device timeout)"); return SNAPGPU_EDEVICE; }
     if (d->owner != a) { snapgpu::setError(who + ": the resident batch belongs to another aligner"); return SNAPGPU_EINVAL; }
-    uint64_t bytes = 0, hash = 0;
-    if (reads->n == d->n)
-        for (uint64_t i = 0; i < reads->n; i++) {
-            bytes = std::max<uint64_t>(bytes, reads->offsets[i] + reads->lengths[i]);
-            hash = extentMix(hash, reads->offsets[i], reads->lengths[i]);
-        }
-    if (reads->n != d->n || bytes != d->bytes || hash != d->extentHash) {
-        snapgpu::setError(who + ": the reads batch does not match the resident batch (n, offsets or lengths differ)");
+    // reads == NULL: the batch's own resident ids and clip state (the device FASTQ parser's), nothing
+    // to compare the extents with
+    const bool devForm = !reads;
+    const uint64_t n = d->n;
+    if (devForm && !d->hasIds) {
+        snapgpu::setError(who + ": reads is NULL and the resident batch holds no ids or clip state of its own "
+                                "(only snapgpu_fastq_upload leaves them; pass the batch it was uploaded from)");
         return SNAPGPU_EINVAL;
     }
+    if (!devForm) {
+        uint64_t bytes = 0, hash = 0;
+        if (reads->n == d->n)
+            for (uint64_t i = 0; i < reads->n; i++) {
+                bytes = std::max<uint64_t>(bytes, reads->offsets[i] + reads->lengths[i]);
+                hash = extentMix(hash, reads->offsets[i], reads->lengths[i]);
+            }
+        if (reads->n != d->n || bytes != d->bytes || hash != d->extentHash) {
+            snapgpu::setError(who + ": the reads batch does not match the resident batch (n, offsets or lengths differ)");
+            return SNAPGPU_EINVAL;
+        }
+    }
     const bool ownIds = !ids;
-    if (ownIds) { ids = reads->ids; idOffsets = reads->idOffsets; idLengths = reads->idLengths; }
-    if (!ids || !idOffsets || !idLengths) {
+    if (ownIds && !devForm) { ids = reads->ids; idOffsets = reads->idOffsets; idLengths = reads->idLengths; }
+    if (!(ownIds && devForm) && (!ids || !idOffsets || !idLengths)) {
         snapgpu::setError(who + ": no read ids (pass ids, or use a batch that carries them)");
         return SNAPGPU_EINVAL;
     }
-    if (bam)
-        if (int rc = snapgpu::bamCheckIds(idLengths, reads->n)) return rc;
     const uint32_t *front = nullptr, *unclipped = nullptr;
-    if (int rc = snapgpu::samCheckClips(reads, nullptr, &front, &unclipped)) return rc;
+    if (devForm) {
+        // the host loops' verdicts from the maxima the upload fetched, with their messages
+        const uint32_t one[1] = {ownIds ? d->maxIdLen : 0u};
+        if (bam)
+            if (int rc = ownIds ? snapgpu::bamCheckIds(one, 1) : snapgpu::bamCheckIds(idLengths, n)) return rc;
+        if (d->maxUnclipped > 1024) {
+            snapgpu::setError("sam_format: nOps > SNAPGPU_CIGAR_MAX_OPS, read longer than 1024 bases or bad clip arrays");
+            return SNAPGPU_EINVAL;
+        }
+    } else {
+        if (bam)
+            if (int rc = snapgpu::bamCheckIds(idLengths, n)) return rc;
+        if (int rc = snapgpu::samCheckClips(reads, nullptr, &front, &unclipped)) return rc;
+    }
     if (!d->dCigEd) {
         snapgpu::setError(who + ": no snapgpu_cigar_resident before snapgpu_" + who);
         return SNAPGPU_EINVAL;
@@ -3750,21 +3798,27 @@ static int samResident(snapgpu_aligner_t *a, snapgpu_device_reads_t *d, const sn
     // snapgpu_reads_upload copied bases and qualities up to the largest clipped end: where the
     // unclipped extents (SEQ / QUAL) pass it, the formatter reads a copy that holds them all
     uint64_t need = d->bytes;
+    if (devForm && d->dTail) need = d->total;   // the last read's unclipped end
     if (unclipped)
         for (uint64_t i = 0; i < reads->n; i++)
             need = std::max<uint64_t>(need, reads->offsets[i] - front[i] + unclipped[i]);
     if (need > d->bytes && S.fullBytes != need) {
         if (S.ran && S.ev[1]) HIPCHK(hipEventSynchronize(S.ev[1]));
         const uint64_t tail = need - d->bytes;
-        S.hAux.assign(2 * tail, 0);
-        memcpy(S.hAux.data(), reads->bases + d->bytes, tail);
-        memcpy(S.hAux.data() + tail, reads->quals + d->bytes, tail);
+        if (!devForm) {
+            S.hAux.assign(2 * tail, 0);
+            memcpy(S.hAux.data(), reads->bases + d->bytes, tail);
+            memcpy(S.hAux.data() + tail, reads->quals + d->bytes, tail);
+        }
         for (int q = 0; q < 2; q++) {
             SamState::Buf &b = q ? S.quals : S.bases;
             HIPCHK(samGrow(a, b, need + 64));
             HIPCHK(hipMemsetAsync((char *)b.p + need, 0, 64, a->copyStream));
             HIPCHK(hipMemcpyAsync(b.p, q ? d->dQuals : d->dBases, d->bytes, hipMemcpyDeviceToDevice, a->copyStream));
-            HIPCHK(hipMemcpyAsync((char *)b.p + d->bytes, S.hAux.data() + q * tail, tail, hipMemcpyHostToDevice, a->copyStream));
+            if (devForm)   // the resident tail: no host bytes
+                HIPCHK(hipMemcpyAsync((char *)b.p + d->bytes, d->dTail + q * tail, tail, hipMemcpyDeviceToDevice, a->copyStream));
+            else
+                HIPCHK(hipMemcpyAsync((char *)b.p + d->bytes, S.hAux.data() + q * tail, tail, hipMemcpyHostToDevice, a->copyStream));
         }
         HIPCHK(hipStreamSynchronize(a->copyStream));
         S.fullBytes = need;
@@ -3781,14 +3835,32 @@ static int samResident(snapgpu_aligner_t *a, snapgpu_device_reads_t *d, const sn
     A.nOps = d->dCigN;
     A.ops = d->dCigOps;
     SamHostIn H;
-    H.n = reads->n; H.lengths = reads->lengths;   // offsets and lengths are resident: the lengths only bound the text
+    H.n = n;
     H.ids = ids; H.idOffsets = idOffsets; H.idLengths = idLengths;
-    H.front = front; H.unclipped = unclipped; H.rg = readGroup;
-    // the batch's own ids do not change: their upload is kept for the next call with the same read group
-    const bool skip = ownIds && S.idsCached && S.cachedHasRg == (readGroup != nullptr) &&
+    H.rg = readGroup;
+    if (devForm) {
+        // aux carries only the piece names, the sort bases and the read group (and a caller's ids)
+        H.device = true;
+        H.baseTotal = d->total;
+        H.idTotal = d->idTotal;
+        if (ownIds) {
+            H.dIds = d->dIds; H.dIdOffsets = d->dIdStart; H.dIdLengths = d->dIdLen;
+        } else {
+            H.idTotal = 0;
+            for (uint64_t i = 0; i < n; i++) H.idTotal += idLengths[i];
+        }
+        if (d->clipping) { H.dFront = d->dFront; H.dUnclipped = d->dUnclipped; }
+    } else {
+        H.lengths = reads->lengths;   // offsets and lengths are resident: the lengths only bound the text
+        H.front = front; H.unclipped = unclipped;
+    }
+    // the batch's own ids do not change: their upload (or, in the device form, the upload without them)
+    // is kept for the next call of the same form with the same read group
+    const bool skip = ownIds && S.idsCached && S.cachedDevForm == devForm && S.cachedHasRg == (readGroup != nullptr) &&
                       (!readGroup || S.cachedRg == readGroup);
     if (int rc = samPrepare(a, S, H, skip, A)) return rc;
     S.idsCached = ownIds;
+    S.cachedDevForm = devForm;
     S.cachedHasRg = readGroup != nullptr;
     S.cachedRg = readGroup ? readGroup : "";
     // the records may come from pass sets on both lanes; the CIGAR kernel is ahead on this stream
@@ -3797,7 +3869,7 @@ static int samResident(snapgpu_aligner_t *a, snapgpu_device_reads_t *d, const sn
         HIPCHK(hipStreamWaitEvent(st, L.done, 0));
     }
     if (bam) d->bgzf.ran = false;   // the records change: a compressed stream of the earlier ones is stale
-    if (int rc = bam ? bamLaunch(a, d->bam, A, reads->n, sorted, nmCarryIn) : samLaunch(a, S, A, reads->n, sorted)) return rc;
+    if (int rc = bam ? bamLaunch(a, d->bam, A, n, sorted, nmCarryIn) : samLaunch(a, S, A, n, sorted)) return rc;
     // the next pass set over these reads rewrites the records: it waits for the SAM / BAM kernels
     HIPCHK(hipEventRecord(a->residentSideDone, st));
     a->residentSidePending = true;
@@ -4291,6 +4363,7 @@ int fastqRun(snapgpu_aligner_t *a, const FastqArrival &arrival, const char *name
     // 2. newline positions, the records' lengths and clips, the scans of base and id lengths
     uint64_t total = 0, idTotal = 0;
     fqgpu::Records R{};
+    fqgpu::Totals hTot{};
     if (n) {
         const uint64_t needRec[7] = {nNl * 8 + 16, n * 20 + 16, (n + 1) * 8, (n + 1) * 8, samgpu::scanTiles(n) * 8 + 16,
                                      samgpu::scanTiles(n) * 8 + 16, sizeof(fqgpu::Totals)};
@@ -4304,17 +4377,17 @@ int fastqRun(snapgpu_aligner_t *a, const FastqArrival &arrival, const char *name
         auto *tot = (fqgpu::Totals *)F.tot.p;
         HIPCHK(hipEventRecord(F.ev[3], s));
         HIPCHK(hipMemsetAsync(&tot->firstBad, 0xff, 8, s));
-        HIPCHK(hipMemsetAsync(&tot->baseBytes, 0, 8, s));
+        HIPCHK(hipMemsetAsync(&tot->baseBytes, 0, 16, s));   // and the two maxima behind it
         fqgpu::lineStarts(text, nBytes, (const uint64_t *)F.tileStart.p, (uint64_t *)F.nl.p, nNl, s);
         HIPCHK(hipEventRecord(F.ev[4], s));
         fqgpu::records(text, nBytes, (const uint64_t *)F.nl.p, nNl, n, clipping, R, tot, s);
         HIPCHK(hipEventRecord(F.ev[5], s));
         samgpu::scanStarts(R.baseLen, n, (uint64_t *)F.sums.p, (uint64_t *)F.baseStart.p, s);
         samgpu::scanStarts(R.idLen, n, (uint64_t *)F.sums2.p, (uint64_t *)F.idStart.p, s);
+        fqgpu::limits(R.baseLen, R.idLen, n, tot, s);
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(F.ev[6], s));
         evUsed[1] = true;
-        fqgpu::Totals hTot{};
         HIPCHK(hipMemcpyAsync(&hTot, tot, sizeof hTot, hipMemcpyDeviceToHost, s));
         HIPCHK(hipMemcpyAsync(&total, (const uint64_t *)F.baseStart.p + n, 8, hipMemcpyDeviceToHost, s));
         HIPCHK(hipMemcpyAsync(&idTotal, (const uint64_t *)F.idStart.p + n, 8, hipMemcpyDeviceToHost, s));
@@ -4334,14 +4407,31 @@ int fastqRun(snapgpu_aligner_t *a, const FastqArrival &arrival, const char *name
     // 3. the resident batch (snapgpu_reads_upload's buffers) and the copy pass into it
     const uint64_t dBytes[7] = {total + 64, total + 64, (n + 1) * 8, (n + 1) * 4, (n + 1) * sizeof(snapgpu_result_t),
                                 3 * (n + 1) * sizeof(uint32_t), (n + 8) * SEEDS_PER_READ * sizeof(SeedRec)};
-    need = growBytes(F.ids, idTotal + 16);
+    // what the SAM / BAM calls take from the batch itself: the packed ids, the four per-record arrays
+    // in one allocation, and (at most the last read's unclipped bases and qualities) the tail
+    auto al16 = [](uint64_t x) { return (x + 15) & ~15ull; };
+    const uint64_t oIdLen = al16(n * 8), oFront = al16(oIdLen + n * 4), oFull = al16(oFront + n * 4),
+                   metaBytes = al16(oFull + n * 4) + 16;
+    need = idTotal + 16 + metaBytes + 2ull * hTot.maxBaseLen;
     for (uint64_t b : dBytes) need += b;
     if (int rc = fqFits(need, "the resident batch")) return rc;
-    HIPCHK(fqEnsure(a, F.ids, idTotal + 16));
     d = new snapgpu_device_reads_t();
     d->owner = a;
     d->n = n;
     d->device = a->device;
+    d->hasIds = true;
+    d->clipping = clipping;
+    d->total = total;
+    d->idTotal = idTotal;
+    d->maxUnclipped = hTot.maxBaseLen;
+    d->maxIdLen = hTot.maxIdLen;
+    HIPCHK(hipMalloc(&d->dIds, idTotal + 16));
+    HIPCHK(hipMalloc(&d->dMeta, metaBytes));
+    d->dIdStart = (const uint64_t *)d->dMeta;
+    d->dIdLen = (const uint32_t *)(d->dMeta + oIdLen);
+    d->dFront = (const uint32_t *)(d->dMeta + oFront);
+    d->dUnclipped = (const uint32_t *)(d->dMeta + oFull);
+    HIPCHK(hipMemsetAsync(d->dIds + idTotal, 0, 16, s));
     HIPCHK(hipMalloc(&d->dBases, dBytes[0]));
     HIPCHK(hipMalloc(&d->dQuals, dBytes[1]));
     HIPCHK(hipMalloc(&d->dOffsets, dBytes[2]));
@@ -4352,10 +4442,15 @@ int fastqRun(snapgpu_aligner_t *a, const FastqArrival &arrival, const char *name
     if (n) {
         HIPCHK(hipEventRecord(F.ev[7], s));
         fqgpu::pack(text, nBytes, (const uint64_t *)F.nl.p, nNl, n, R, (const uint64_t *)F.baseStart.p,
-                    (const uint64_t *)F.idStart.p, d->dBases, d->dQuals, (char *)F.ids.p, d->dOffsets, d->dLengths, s);
+                    (const uint64_t *)F.idStart.p, d->dBases, d->dQuals, d->dIds, d->dOffsets, d->dLengths, s);
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(F.ev[8], s));
         evUsed[2] = true;
+        // the batch's own copies of what the next upload overwrites in the parser's buffers
+        HIPCHK(hipMemcpyAsync(d->dMeta, F.idStart.p, n * 8, hipMemcpyDeviceToDevice, s));
+        HIPCHK(hipMemcpyAsync(d->dMeta + oIdLen, R.idLen, n * 4, hipMemcpyDeviceToDevice, s));
+        HIPCHK(hipMemcpyAsync(d->dMeta + oFront, R.front, n * 4, hipMemcpyDeviceToDevice, s));
+        HIPCHK(hipMemcpyAsync(d->dMeta + oFull, R.baseLen, n * 4, hipMemcpyDeviceToDevice, s));
         if (int rc = waitLane(a, a->lane[0])) return rc;
     }
     // 4. offsets and lengths always come back (the extent hash is a sequential chain); the batch on request
@@ -4383,13 +4478,13 @@ int fastqRun(snapgpu_aligner_t *a, const FastqArrival &arrival, const char *name
         }
         memset(r->bases + total, 0, 64);   // the batch's zero slack
         memset(r->quals + total, 0, 64);
-        if (idTotal) HIPCHK(hipMemcpyAsync(r->ids, F.ids.p, idTotal, hipMemcpyDeviceToHost, cs));
+        if (idTotal) HIPCHK(hipMemcpyAsync(r->ids, d->dIds, idTotal, hipMemcpyDeviceToHost, cs));
         if (n) {
-            HIPCHK(hipMemcpyAsync(r->idOffsets, F.idStart.p, n * 8, hipMemcpyDeviceToHost, cs));
-            HIPCHK(hipMemcpyAsync(r->idLengths, R.idLen, n * 4, hipMemcpyDeviceToHost, cs));
+            HIPCHK(hipMemcpyAsync(r->idOffsets, d->dIdStart, n * 8, hipMemcpyDeviceToHost, cs));
+            HIPCHK(hipMemcpyAsync(r->idLengths, d->dIdLen, n * 4, hipMemcpyDeviceToHost, cs));
             if (clipping) {
-                HIPCHK(hipMemcpyAsync(r->frontClipped, R.front, n * 4, hipMemcpyDeviceToHost, cs));
-                HIPCHK(hipMemcpyAsync(r->unclippedLength, R.baseLen, n * 4, hipMemcpyDeviceToHost, cs));
+                HIPCHK(hipMemcpyAsync(r->frontClipped, d->dFront, n * 4, hipMemcpyDeviceToHost, cs));
+                HIPCHK(hipMemcpyAsync(r->unclippedLength, d->dUnclipped, n * 4, hipMemcpyDeviceToHost, cs));
             }
         }
     } else {
@@ -4412,6 +4507,13 @@ int fastqRun(snapgpu_aligner_t *a, const FastqArrival &arrival, const char *name
     }
     if (bytes > total) { snapgpu::setError("fastq_upload: a clipped read ends past the batch"); return SNAPGPU_EDEVICE; }
     d->bytes = bytes;
+    // the SAM / BAM lines print the unclipped SEQ and QUAL: what the zeroing takes stays in the tail
+    if (const uint64_t tail = total - bytes) {
+        if (tail > hTot.maxBaseLen) { snapgpu::setError("fastq_upload: the tail is longer than the longest read"); return SNAPGPU_EDEVICE; }
+        HIPCHK(hipMalloc(&d->dTail, 2 * tail));
+        HIPCHK(hipMemcpyAsync(d->dTail, d->dBases + bytes, tail, hipMemcpyDeviceToDevice, cs));
+        HIPCHK(hipMemcpyAsync(d->dTail + tail, d->dQuals + bytes, tail, hipMemcpyDeviceToDevice, cs));
+    }
     // zero from the largest clipped end on, as an upload of the clipped batch leaves it
     HIPCHK(hipMemsetAsync(d->dBases + bytes, 0, total + 64 - bytes, cs));
     HIPCHK(hipMemsetAsync(d->dQuals + bytes, 0, total + 64 - bytes, cs));
@@ -4640,6 +4742,34 @@ int snapgpu_device_reads_peek(snapgpu_aligner_t *a, snapgpu_device_reads_t *d, u
     if (lengths && d->n) HIPCHK(hipMemcpy(lengths, d->dLengths, d->n * 4, hipMemcpyDeviceToHost));
     if (bases) HIPCHK(hipMemcpy(bases, d->dBases, d->bytes + 64, hipMemcpyDeviceToHost));
     if (quals) HIPCHK(hipMemcpy(quals, d->dQuals, d->bytes + 64, hipMemcpyDeviceToHost));
+    return SNAPGPU_OK;
+}
+
+int snapgpu_device_reads_ids_download(snapgpu_aligner_t *a, snapgpu_device_reads_t *d, char *ids, uint64_t cap,
+                                      uint64_t *used, uint64_t *idOffsets, uint32_t *idLengths, uint32_t *frontClipped,
+                                      uint32_t *unclippedLength) {
+    if (!a || !d || !used || d->owner != a) { snapgpu::setError("device_reads_ids_download: bad argument"); return SNAPGPU_EINVAL; }
+    *used = 0;
+    if (a->failed) { snapgpu::setError("aligner failed earlier (device timeout)"); return SNAPGPU_EDEVICE; }
+    if (!d->hasIds) {
+        snapgpu::setError("device_reads_ids_download: the resident batch holds no ids of its own (only snapgpu_fastq_upload leaves them)");
+        return SNAPGPU_EINVAL;
+    }
+    *used = d->idTotal;
+    if (d->idTotal > cap || (!ids && d->idTotal)) {
+        snapgpu::setError("device_reads_ids_download: output buffer too small");
+        return SNAPGPU_EINVAL;
+    }
+    HIPCHK(hipSetDevice(a->device));
+    if (d->idTotal) HIPCHK(hipMemcpy(ids, d->dIds, d->idTotal, hipMemcpyDeviceToHost));
+    if (d->n) {
+        if (idOffsets) HIPCHK(hipMemcpy(idOffsets, d->dIdStart, d->n * 8, hipMemcpyDeviceToHost));
+        if (idLengths) HIPCHK(hipMemcpy(idLengths, d->dIdLen, d->n * 4, hipMemcpyDeviceToHost));
+        if (d->clipping) {
+            if (frontClipped) HIPCHK(hipMemcpy(frontClipped, d->dFront, d->n * 4, hipMemcpyDeviceToHost));
+            if (unclippedLength) HIPCHK(hipMemcpy(unclippedLength, d->dUnclipped, d->n * 4, hipMemcpyDeviceToHost));
+        }
+    }
     return SNAPGPU_OK;
 }
 

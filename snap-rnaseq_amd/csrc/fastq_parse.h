@@ -21,6 +21,7 @@ inline uint64_t textCapacity(uint64_t nBytes) { return ((nBytes + 63) & ~63ull) 
 struct Totals {
     unsigned long long firstBad;    // the first record without '@' header (starts as all ones)
     unsigned long long baseBytes;   // sum of the records' base lengths (starts as 0)
+    uint32_t maxBaseLen, maxIdLen;  // the longest unclipped read and the longest id (start as 0; limits())
 };
 
 struct Records {   // [n] each
@@ -35,6 +36,9 @@ void lineStarts(const char *text, uint64_t nBytes, const uint64_t *tileStart, ui
 // fastq_record.h over records 0 .. n (n > 0), a wave per record; *tot as initialised above
 void records(const char *text, uint64_t nBytes, const uint64_t *nl, uint64_t nNl, uint64_t n, int clipping,
              const Records &R, Totals *tot, hipStream_t st);
+// tot->maxBaseLen / maxIdLen = the largest of baseLen[0 .. n) / idLen[0 .. n) (n > 0): what the device
+// form of the SAM / BAM calls checks in place of the host loops over a host batch
+void limits(const uint32_t *baseLen, const uint32_t *idLen, uint64_t n, Totals *tot, hipStream_t st);
 // ids, bases and qualities (0x00 where the quality line is shorter) to ids[idStart[r] ..],
 // bases / quals[baseStart[r] ..]; offsets[r] / lengths[r] = the clipped extent
 void pack(const char *text, uint64_t nBytes, const uint64_t *nl, uint64_t nNl, uint64_t n, const Records &R,

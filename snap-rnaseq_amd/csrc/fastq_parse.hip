@@ -5,6 +5,8 @@
 //   4. fastq_record_kernel   fastq_record.h per record, a wave per record: trimmed line bounds, the
 //                            three lengths, Read::clip, the first record without '@' header (an
 //                            atomicMin per wave)
+//   4b. fastq_limits_kernel  the longest unclipped read and the longest id of the batch (a wave
+//                            reduction, then one atomicMax each per wave)
 //   5. samgpu::scanStarts    64-bit starts of the records' bases and ids
 //   6. fastq_pack_kernel     ids, bases and qualities to their places, staged through LDS so that
 //                            the stores are whole 16-byte chunks
@@ -129,6 +131,28 @@ __global__ __launch_bounds__(256) void fastq_record_kernel(const char *__restric
     }
 }
 
+// Maxima of the two length arrays: grid-stride over the records, a wave reduction, one atomic per
+// wave and array (a single-address atomic per record is what the record pass avoids).
+__global__ __launch_bounds__(256) void fastq_limits_kernel(const uint32_t *__restrict__ baseLen,
+                                                           const uint32_t *__restrict__ idLen, uint64_t n, Totals *tot) {
+    uint32_t mb = 0, mi = 0;
+    const uint64_t stride = (uint64_t)gridDim.x * 256u;
+    for (uint64_t r = (uint64_t)blockIdx.x * 256u + threadIdx.x; r < n; r += stride) {
+        const uint32_t b = baseLen[r], i = idLen[r];
+        mb = mb > b ? mb : b;
+        mi = mi > i ? mi : i;
+    }
+    for (int o = 32; o; o >>= 1) {
+        const uint32_t b = __shfl_xor(mb, o), i = __shfl_xor(mi, o);
+        mb = mb > b ? mb : b;
+        mi = mi > i ? mi : i;
+    }
+    if ((threadIdx.x & 63u) == 0) {
+        if (mb) atomicMax(&tot->maxBaseLen, mb);
+        if (mi) atomicMax(&tot->maxIdLen, mi);
+    }
+}
+
 // One output of the copy pass over the group's records [first, end): record j's piece is src[j]'s
 // first `valid` bytes, then 0x00, start[j + 1] - start[j] bytes in all, at out + start[j].  Windows
 // of kStageBytes of the output, 16-byte aligned, are filled in LDS by a wave per record and stored
@@ -211,6 +235,12 @@ void records(const char *text, uint64_t nBytes, const uint64_t *nl, uint64_t nNl
     const uint64_t blocks = (n + 3) / 4 < 2048 ? (n + 3) / 4 : 2048;
     hipLaunchKernelGGL(fastq_record_kernel, dim3((unsigned)blocks), dim3(256), 0, st, text, Lines{nl, nNl, nBytes}, n,
                        clipping, R, tot);
+}
+
+void limits(const uint32_t *baseLen, const uint32_t *idLen, uint64_t n, Totals *tot, hipStream_t st) {
+    // 16 records per lane until 256 workgroups (one per CU) are reached: 1,024 atomics per array at the most
+    const uint64_t blocks = (n + 4095) / 4096 < 256 ? (n + 4095) / 4096 : 256;
+    hipLaunchKernelGGL(fastq_limits_kernel, dim3((unsigned)blocks), dim3(256), 0, st, baseLen, idLen, n, tot);
 }
 
 void pack(const char *text, uint64_t nBytes, const uint64_t *nl, uint64_t nNl, uint64_t n, const Records &R,

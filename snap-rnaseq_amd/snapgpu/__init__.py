@@ -811,6 +811,29 @@ class DeviceReads:
             out.update(offsets=off[:n.value], lengths=ln[:n.value], bases=b.tobytes(), quals=q.tobytes())
         return out
 
+    def ids(self):
+        """The resident ids and clip state of a batch from upload_fastq
+        (snapgpu_device_reads_ids_download; waits) -> (list of bytes, front clips, unclipped lengths):
+        what Reads.ids() and Reads.clip() give for the host batch.  The two arrays are None for a
+        batch uploaded with clipping 0 (and for an empty one)."""
+        fn = lib().snapgpu_device_reads_ids_download
+        used = C.c_uint64()
+        rc = fn(self.aligner._h, self._h, None, 0, C.byref(used), None, None, None, None)
+        if rc != 0 and used.value == 0:
+            _check(rc, "device_reads_ids_download")
+        n = self.n
+        blob = np.zeros(max(1, used.value), np.uint8)
+        off, ln = np.zeros(max(1, n), np.uint64), np.zeros(max(1, n), np.uint32)
+        untouched = 0xffffffff                       # no length reaches it
+        front, full = np.full(max(1, n), untouched, np.uint32), np.full(max(1, n), untouched, np.uint32)
+        _check(fn(self.aligner._h, self._h, blob.ctypes.data, used.value, C.byref(used), off.ctypes.data,
+                  ln.ctypes.data, front.ctypes.data, full.ctypes.data), "device_reads_ids_download")
+        raw = blob.tobytes()
+        out = [raw[int(o):int(o) + int(l)] for o, l in zip(off[:n], ln[:n])]
+        if n == 0 or full[0] == untouched:
+            return out, None, None
+        return out, front[:n], full[:n]
+
     def run(self):
         """Launch the GPU passes (asynchronous)."""
         _check(lib().snapgpu_align_resident(self.aligner._h, self._h), "align_resident")
@@ -834,20 +857,21 @@ class DeviceReads:
                                             c.nOps.ctypes.data, c.ops.ctypes.data), "cigar_download")
         return c
 
-    def run_sam(self, reads, ids=None, read_group="FASTQ", sorted_output=False):
+    def run_sam(self, reads=None, ids=None, read_group="FASTQ", sorted_output=False):
         """SAM lines of the records and CIGARs run() + run_cigars() left in HBM, formatted on the
-        GPU (asynchronous).  reads: the batch this was uploaded from; ids: None for its own ids;
+        GPU (asynchronous).  reads: the batch this was uploaded from, or None for the resident ids
+        and clip state of a batch from upload_fastq (no host batch needed); ids: None for its own ids;
         sorted_output: the lines in coordinate order (`-so`), sam_order() then gives that order."""
         rg = None if read_group is None else read_group.encode()
         if ids is None:
             self._sam_keep = None
             args = [None, None, None]
         else:
-            blob, offs, lens = _id_arrays(ids, reads.n)
+            blob, offs, lens = _id_arrays(ids, self.n if reads is None else reads.n)
             self._sam_keep = (blob, offs, lens)
             args = [blob, offs.ctypes.data, lens.ctypes.data]
         fn = lib().snapgpu_sam_resident_sorted if sorted_output else lib().snapgpu_sam_resident
-        _check(fn(self.aligner._h, self._h, reads._p, *args, rg), "sam_resident")
+        _check(fn(self.aligner._h, self._h, None if reads is None else reads._p, *args, rg), "sam_resident")
 
     def sam_order(self):
         """The output order of the last run_sam(sorted_output=True) -> uint32[n] (waits): entry j is
@@ -870,9 +894,10 @@ class DeviceReads:
             timing["done"] = time.perf_counter()
         return buf[:used.value].tobytes()
 
-    def run_bam(self, reads, ids=None, read_group="FASTQ", sorted_output=False, nm_carry=0):
+    def run_bam(self, reads=None, ids=None, read_group="FASTQ", sorted_output=False, nm_carry=0):
         """BAM records of the records and CIGARs run() + run_cigars() left in HBM, encoded on the GPU
-        (asynchronous).  reads: the batch this was uploaded from; ids: None for its own ids;
+        (asynchronous).  reads: the batch this was uploaded from, or None as in run_sam(); ids: None
+        for its own ids;
         sorted_output: the records in coordinate order, bam_order() then gives that order; nm_carry:
         the NM that records without CIGAR ops repeat until the first record with ops (the previous
         batch's bam_nm_carry())."""
@@ -881,11 +906,12 @@ class DeviceReads:
             self._bam_keep = None
             args = [None, None, None]
         else:
-            blob, offs, lens = _id_arrays(ids, reads.n)
+            blob, offs, lens = _id_arrays(ids, self.n if reads is None else reads.n)
             self._bam_keep = (blob, offs, lens)
             args = [blob, offs.ctypes.data, lens.ctypes.data]
         fn = lib().snapgpu_bam_resident_sorted if sorted_output else lib().snapgpu_bam_resident
-        _check(fn(self.aligner._h, self._h, reads._p, *args, rg, int(nm_carry)), "bam_resident")
+        _check(fn(self.aligner._h, self._h, None if reads is None else reads._p, *args, rg, int(nm_carry)),
+               "bam_resident")
         self._bam_carry = None
 
     def bam_order(self):

@@ -315,6 +315,9 @@ _PROTOS = [
     ("snapgpu_device_reads_peek", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
                                             C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.c_void_p, C.c_void_p,
                                             C.c_void_p, C.c_void_p]),
+    ("snapgpu_device_reads_ids_download", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
+                                                    C.POINTER(C.c_uint64), C.c_void_p, C.c_void_p, C.c_void_p,
+                                                    C.c_void_p]),
     ("snapgpu_last_timing", C.c_int, [C.c_void_p, C.POINTER(Timing)]),
     ("snapgpu_aligner_get_stats", C.c_int, [C.c_void_p, C.POINTER(AlignerStats)]),
     ("snapgpu_aligner_max_k", C.c_int, [C.c_void_p]),
