@@ -780,6 +780,38 @@ int snapgpu_bgzf_compress_gpu(snapgpu_aligner_t *a, const char *in, uint64_t n, 
 int snapgpu_bgzf_compress_model(const char *in, uint64_t n, int eof, char *out, uint64_t cap, uint64_t *used);
 int snapgpu_bgzf_last_ms(snapgpu_aligner_t *a, double *kernelMs, double *downloadMs);
 
+/* The .bai index (SAMv1 5.2) of a coordinate-sorted record stream and a BGZF stream of it, in one
+ * canonical form (csrc/bai_index.h): per reference the records' own bins ascending, a
+ * bin's chunks the maximal runs of consecutive records that carry it, pseudo-bin 37450, the linear
+ * index back-filled as htslib does, then n_no_coor.  streamOffset: the compressed bytes that precede
+ * the record stream in the file (the BGZF of the BAM header), < 2^48.
+ * snapgpu_bai_build: the host model; bgzf is any BGZF stream of the n bytes at records (an EOF block
+ * may end it).  SNAPGPU_EFORMAT naming the record's index for a truncated record, refID outside
+ * [-1, nRef), pos < 0 with a refID, an end past 2^29 or records out of (refID, pos) order (-1 last);
+ * SNAPGPU_EINVAL when the members' ISIZEs do not sum to n.  Size contract as snapgpu_sam_format.
+ * snapgpu_bai_size_bound: what an index of nRecords records over nRef references can take at most.
+ * snapgpu_bam_bai_resident: asynchronous, on the stream of the BAM and BGZF passes (bai.hip): the
+ * index of the batch's last snapgpu_bam_resident_sorted records over the members of the
+ * snapgpu_bam_bgzf_resident that followed it (SNAPGPU_EINVAL when the last BAM call was not the sorted
+ * one, when no BGZF call followed it, when streamOffset >= 2^48); nRef is the genome's contig count.
+ * A later snapgpu_bam_resident* or snapgpu_bam_bgzf_resident makes it stale.
+ * snapgpu_bam_bai_download: waits; *used = the index's bytes, SNAPGPU_EINVAL if cap is too small or
+ * the index is stale; SNAPGPU_EDEVICE if the device counted a refused or unsorted record.
+ * snapgpu_bai_build_gpu: the batch form over n bytes of records: upload, device BGZF (no EOF block),
+ * index, both downloads.  A truncated record is SNAPGPU_EFORMAT; whatever else snapgpu_bai_build
+ * refuses is SNAPGPU_EDEVICE here.
+ * snapgpu_bai_last_ms: kernel time (HIP events over all passes) and download time of the aligner's
+ * last device index. */
+uint64_t snapgpu_bai_size_bound(uint64_t nRecords, uint64_t nRef, uint64_t recordBytes);
+int snapgpu_bai_build(const char *records, uint64_t n, int32_t nRef, const char *bgzf, uint64_t bgzfBytes,
+                      uint64_t streamOffset, char *out, uint64_t cap, uint64_t *used);
+int snapgpu_bam_bai_resident(snapgpu_aligner_t *a, snapgpu_device_reads_t *d, uint64_t streamOffset);
+int snapgpu_bam_bai_download(snapgpu_aligner_t *a, snapgpu_device_reads_t *d, char *out, uint64_t cap, uint64_t *used);
+int snapgpu_bai_build_gpu(snapgpu_aligner_t *a, const char *records, uint64_t n, int32_t nRef, uint64_t streamOffset,
+                          char *bgzfOut, uint64_t bgzfCap, uint64_t *bgzfUsed, char *baiOut, uint64_t baiCap,
+                          uint64_t *baiUsed);
+int snapgpu_bai_last_ms(snapgpu_aligner_t *a, double *kernelMs, double *downloadMs);
+
 /* BGZF inflated (host/inflate.cpp, inflate.hip over inflate_block.h): a stream of BGZF members, as
  * bgzip, samtools and the compressors above write them, back to its bytes.  Every form first walks
  * the members (magic, CM 8, FLG 4, a BC subfield anywhere in the extra field, BSIZE inside the

@@ -28,6 +28,7 @@
 #include "large_copy.h"
 #include "bam_format.h"
 #include "bgzf.h"
+#include "bai.h"
 #include "fastq_parse.h"
 #include "inflate.h"
 #include "sam_format.h"
@@ -1208,6 +1209,18 @@ struct BgzfState {
     double downloadMs = 0;
 };
 
+// Device BAI builder (bai.hip) state of one resident batch, or of the aligner's batch form: grow-only
+// device buffers -- the passes' work area (baigpu::Layout), the index, the batch form's record starts.
+struct BaiState {
+    SamState::Buf work, out, starts;
+    baigpu::Layout L{};
+    uint64_t n = 0, nRef = 0, outCap = 0;
+    bool ran = false;         // the index is that of the batch's last BAM and BGZF calls
+    bool launched = false;    // ev[kPasses] was recorded: kernels may still use the buffers
+    hipEvent_t ev[baigpu::kPasses + 1] = {};   // around the passes
+    double downloadMs = 0;
+};
+
 struct snapgpu_device_reads {
     snapgpu_aligner_t *owner = nullptr;
     char *dBases = nullptr, *dQuals = nullptr;
@@ -1237,6 +1250,7 @@ struct snapgpu_device_reads {
     SamState sam;
     BamState bam;
     BgzfState bgzf;
+    BaiState bai;
 };
 
 struct snapgpu_aligner {
@@ -1339,6 +1353,8 @@ struct snapgpu_aligner {
     BamState *bamLast = nullptr;   // snapgpu_bam_last_ms
     BgzfState bgzfBatch;
     BgzfState *bgzfLast = nullptr; // snapgpu_bgzf_last_ms
+    BaiState baiBatch;
+    BaiState *baiLast = nullptr;   // snapgpu_bai_last_ms
     int bgzfGrid = 0;              // workgroups of the compress pass: one per CU
     void *samPin[2] = {};
     hipEvent_t samPinDone[2] = {};
@@ -1714,6 +1730,17 @@ void bgzfStateFree(const snapgpu_aligner_t *a, BgzfState &S) {
             if (e) { hipEventDestroy(e); e = nullptr; }
 }
 
+void baiStateFree(const snapgpu_aligner_t *a, BaiState &S) {
+    for (auto *b : {&S.work, &S.out, &S.starts}) {
+        devFree(a, b->p);
+        b->p = nullptr;
+        b->cap = 0;
+    }
+    if (!(a && a->failed))
+        for (auto &e : S.ev)
+            if (e) { hipEventDestroy(e); e = nullptr; }
+}
+
 // Wait for an event, honouring SNAPGPU_TIMEOUT_S: on expiry the aligner is marked failed.
 int waitEvent(snapgpu_aligner_t *a, hipEvent_t ev) {
     if (a->failed) { snapgpu::setError("aligner failed earlier (device timeout): no further work accepted"); return SNAPGPU_EDEVICE; }
@@ -1972,6 +1999,7 @@ void snapgpu_aligner_free(snapgpu_aligner_t *a) {
     samStateFree(a, a->samBatch);
     bamStateFree(a, a->bamBatch);
     bgzfStateFree(a, a->bgzfBatch);
+    baiStateFree(a, a->baiBatch);
     for (int k = 0; k < 2; k++) {
         if (!a->failed) hostPinnedFree(a->samPin[k]);
         if (a->samPinDone[k]) hipEventDestroy(a->samPinDone[k]);
@@ -2213,6 +2241,8 @@ void snapgpu_device_reads_free(snapgpu_device_reads_t *d) {
     bamStateFree(a, d->bam);
     if (a && a->bgzfLast == &d->bgzf) const_cast<snapgpu_aligner_t *>(a)->bgzfLast = nullptr;
     bgzfStateFree(a, d->bgzf);
+    if (a && a->baiLast == &d->bai) const_cast<snapgpu_aligner_t *>(a)->baiLast = nullptr;
+    baiStateFree(a, d->bai);
     delete d;
 }
 
@@ -3868,7 +3898,7 @@ static int samResident(snapgpu_aligner_t *a, snapgpu_device_reads_t *d, const sn
         HIPCHK(hipEventRecord(L.done, L.stream));
         HIPCHK(hipStreamWaitEvent(st, L.done, 0));
     }
-    if (bam) d->bgzf.ran = false;   // the records change: a compressed stream of the earlier ones is stale
+    if (bam) d->bgzf.ran = d->bai.ran = false;   // the records change: a compressed stream of the earlier ones, and its index, are stale
     if (int rc = bam ? bamLaunch(a, d->bam, A, n, sorted, nmCarryIn) : samLaunch(a, S, A, n, sorted)) return rc;
     // the next pass set over these reads rewrites the records: it waits for the SAM / BAM kernels
     HIPCHK(hipEventRecord(a->residentSideDone, st));
@@ -4119,6 +4149,7 @@ int snapgpu_bam_bgzf_resident(snapgpu_aligner_t *a, snapgpu_device_reads_t *d) {
     // the records and their total are written by the BAM passes ahead on the side stream; the next
     // snapgpu_bam_resident rewrites them on that stream, after these passes
     const BamState &R = d->bam;
+    d->bai.ran = false;   // the member offsets change: an index over the earlier ones is stale
     if (R.n == 0) return bgzfLaunch(a, d->bgzf, nullptr, nullptr, 0, 0);
     return bgzfLaunch(a, d->bgzf, (const char *)R.text.p, (const uint64_t *)R.start.p + R.n, 0, R.textBound);
 }
@@ -4163,6 +4194,160 @@ int snapgpu_bgzf_last_ms(snapgpu_aligner_t *a, double *kernelMs, double *downloa
     }
     *kernelMs = f;
     *downloadMs = S.downloadMs;
+    return SNAPGPU_OK;
+}
+
+// ------------------------------------------------- BAI on the device (bai.hip)
+// The index passes on the side stream over n records at text + start[i], members at coff.
+static int baiLaunch(snapgpu_aligner_t *a, BaiState &S, const char *text, const uint64_t *start, uint64_t n, uint64_t recordBytes,
+                     uint32_t nRef, const uint64_t *coff, uint64_t streamOffset) {
+    for (auto &e : S.ev)
+        if (!e) HIPCHK(hipEventCreate(&e));
+    if (n > 0xfffffffeull) { snapgpu::setError("bai: batch too large"); return SNAPGPU_EINVAL; }
+    // an earlier call's kernels may still use the buffers that grow
+    if (S.launched) HIPCHK(hipEventSynchronize(S.ev[baigpu::kPasses]));
+    S.ran = false;
+    uint64_t temp = 0;
+    HIPCHK(baigpu::tempBytes(n, a->sideStream, &temp));
+    S.L = baigpu::layout(n, nRef, temp);
+    S.outCap = (baiindex::sizeBound(n, nRef, recordBytes) + 15) & ~15ull;
+    HIPCHK(samGrow(a, S.work, S.L.bytes));
+    HIPCHK(samGrow(a, S.out, S.outCap));
+    S.n = n;
+    S.nRef = nRef;
+    S.downloadMs = 0;
+    a->baiLast = &S;
+    HIPCHK(baigpu::launch((const uint8_t *)text, start, n, nRef, coff, streamOffset, (char *)S.work.p, S.L, (uint8_t *)S.out.p,
+                          S.outCap, a->sideStream, S.ev));
+    S.ran = S.launched = true;
+    return SNAPGPU_OK;
+}
+
+// Wait for S's kernels, check them, and copy the index to the caller.
+static int baiDownload(snapgpu_aligner_t *a, BaiState &S, char *out, uint64_t cap, uint64_t *used) {
+    *used = 0;
+    S.downloadMs = 0;
+    if (int rc = waitEvent(a, S.ev[baigpu::kPasses])) return rc;
+    const auto t0 = std::chrono::steady_clock::now();
+    baigpu::Result r{};
+    HIPCHK(hipMemcpy(&r, (const char *)S.work.p + S.L.res, sizeof r, hipMemcpyDeviceToHost));
+    if (r.bad || r.total > S.outCap) {
+        char msg[200];
+        snprintf(msg, sizeof msg, "bai: %u records are refused or out of (refID, pos) order, or the counts do not add up "
+                                  "(index %llu bytes, bound %llu)", r.bad, (unsigned long long)r.total, (unsigned long long)S.outCap);
+        snapgpu::setError(msg);
+        return SNAPGPU_EDEVICE;
+    }
+    *used = r.total;
+    if (r.total > cap || !out) { snapgpu::setError("bai_download: output buffer too small"); return SNAPGPU_EINVAL; }
+    HIPCHK(hipMemcpy(out, S.out.p, r.total, hipMemcpyDeviceToHost));
+    S.downloadMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return SNAPGPU_OK;
+}
+
+int snapgpu_bam_bai_resident(snapgpu_aligner_t *a, snapgpu_device_reads_t *d, uint64_t streamOffset) {
+    if (!a || !d) { snapgpu::setError("bam_bai_resident: null argument"); return SNAPGPU_EINVAL; }
+    if (a->failed) { snapgpu::setError("aligner failed earlier (device timeout)"); return SNAPGPU_EDEVICE; }
+    if (d->owner != a) { snapgpu::setError("bam_bai_resident: the resident batch belongs to another aligner"); return SNAPGPU_EINVAL; }
+    if (!d->bam.ran || !d->bam.sorted) {
+        snapgpu::setError("bam_bai_resident: the batch's last BAM call was not snapgpu_bam_resident_sorted (or there was none)");
+        return SNAPGPU_EINVAL;
+    }
+    if (!d->bgzf.ran) {
+        snapgpu::setError("bam_bai_resident: no snapgpu_bam_bgzf_resident since the batch's last snapgpu_bam_resident_sorted");
+        return SNAPGPU_EINVAL;
+    }
+    if (streamOffset >= baiindex::kStreamOffsetLimit) {
+        snapgpu::setError("bam_bai_resident: streamOffset does not fit a virtual offset");
+        return SNAPGPU_EINVAL;
+    }
+    HIPCHK(hipSetDevice(a->device));
+    const BamState &R = d->bam;
+    const uint32_t nRef = (uint32_t)a->idx->genome->pieceOffsets.size();
+    return baiLaunch(a, d->bai, (const char *)R.text.p, (const uint64_t *)R.start.p, R.n, R.n ? R.textBound : 0, nRef,
+                     (const uint64_t *)d->bgzf.offs.p, streamOffset);
+}
+
+int snapgpu_bam_bai_download(snapgpu_aligner_t *a, snapgpu_device_reads_t *d, char *out, uint64_t cap, uint64_t *used) {
+    if (!a || !d || !used) { snapgpu::setError("bam_bai_download: null argument"); return SNAPGPU_EINVAL; }
+    if (a->failed) { snapgpu::setError("aligner failed earlier (device timeout)"); return SNAPGPU_EDEVICE; }
+    if (!d->bai.ran) {
+        snapgpu::setError("bam_bai_download: no snapgpu_bam_bai_resident since the batch's last snapgpu_bam_resident or "
+                          "snapgpu_bam_bgzf_resident");
+        return SNAPGPU_EINVAL;
+    }
+    HIPCHK(hipSetDevice(a->device));
+    return baiDownload(a, d->bai, out, cap, used);
+}
+
+int snapgpu_bai_build_gpu(snapgpu_aligner_t *a, const char *records, uint64_t n, int32_t nRef, uint64_t streamOffset,
+                          char *bgzfOut, uint64_t bgzfCap, uint64_t *bgzfUsed, char *baiOut, uint64_t baiCap,
+                          uint64_t *baiUsed) {
+    if (!a || (!records && n) || !bgzfUsed || !baiUsed || nRef < 0) { snapgpu::setError("bai_build_gpu: bad argument"); return SNAPGPU_EINVAL; }
+    if (a->failed) { snapgpu::setError("aligner failed earlier (device timeout)"); return SNAPGPU_EDEVICE; }
+    if (streamOffset >= baiindex::kStreamOffsetLimit) {
+        snapgpu::setError("bai_build_gpu: streamOffset does not fit a virtual offset");
+        return SNAPGPU_EINVAL;
+    }
+    // the record starts: a walk over the block sizes on the host
+    std::vector<uint64_t> starts;
+    for (uint64_t u = 0; u < n;) {
+        starts.push_back(u);
+        const uint64_t bytes = n - u < 4 ? 0 : (uint64_t)baiindex::load32((const uint8_t *)records + u) + 4;
+        if (bytes < baiindex::kFixed || bytes > n - u) {
+            snapgpu::setError("bai_build_gpu: record " + std::to_string(starts.size() - 1) + ": truncated");
+            return SNAPGPU_EFORMAT;
+        }
+        u += bytes;
+    }
+    starts.push_back(n);
+    const uint64_t nRec = starts.size() - 1;
+    HIPCHK(hipSetDevice(a->device));
+    BgzfState &Z = a->bgzfBatch;
+    BaiState &S = a->baiBatch;
+    if (Z.ran && Z.maxBlocks) HIPCHK(hipEventSynchronize(Z.ev[3]));
+    if (S.launched) HIPCHK(hipEventSynchronize(S.ev[baigpu::kPasses]));
+    S.ran = false;
+    if (n) {
+        HIPCHK(samGrow(a, Z.in, n + 64));
+        HIPCHK(hipMemcpyAsync(Z.in.p, records, n, hipMemcpyHostToDevice, a->sideStream));
+    }
+    HIPCHK(samGrow(a, S.starts, starts.size() * 8));
+    HIPCHK(hipMemcpyAsync(S.starts.p, starts.data(), starts.size() * 8, hipMemcpyHostToDevice, a->sideStream));
+    HIPCHK(hipStreamSynchronize(a->sideStream));   // the host copies may go
+    if (int rc = bgzfLaunch(a, Z, (const char *)Z.in.p, nullptr, n, n)) return rc;
+    if (int rc = baiLaunch(a, S, (const char *)Z.in.p, (const uint64_t *)S.starts.p, nRec, n, (uint32_t)nRef,
+                           (const uint64_t *)Z.offs.p, streamOffset))
+        return rc;
+    if (int rc = bgzfDownload(a, Z, 0, bgzfOut, bgzfCap, bgzfUsed)) return rc;
+    return baiDownload(a, S, baiOut, baiCap, baiUsed);
+}
+
+int snapgpu_bai_last_ms(snapgpu_aligner_t *a, double *kernelMs, double *downloadMs) {
+    if (!a || !kernelMs || !downloadMs) return SNAPGPU_EINVAL;
+    if (!a->baiLast || !a->baiLast->ran) { snapgpu::setError("bai_last_ms: no device BAI call on this aligner"); return SNAPGPU_EINVAL; }
+    if (a->failed) { snapgpu::setError("aligner failed earlier (device timeout)"); return SNAPGPU_EDEVICE; }
+    HIPCHK(hipSetDevice(a->device));
+    BaiState &S = *a->baiLast;
+    float f = 0;
+    HIPCHK(hipEventSynchronize(S.ev[baigpu::kPasses]));
+    HIPCHK(hipEventElapsedTime(&f, S.ev[0], S.ev[baigpu::kPasses]));
+    *kernelMs = f;
+    *downloadMs = S.downloadMs;
+    return SNAPGPU_OK;
+}
+
+// ms[0 .. baigpu::kPasses): the passes of the last device BAI call (tools/bai_time.py)
+int snapgpu_internal_bai_pass_ms(snapgpu_aligner_t *a, double *ms) {
+    if (!a || !ms || !a->baiLast || !a->baiLast->ran || a->failed) return SNAPGPU_EINVAL;
+    HIPCHK(hipSetDevice(a->device));
+    BaiState &S = *a->baiLast;
+    HIPCHK(hipEventSynchronize(S.ev[baigpu::kPasses]));
+    for (int k = 0; k < baigpu::kPasses; k++) {
+        float f = 0;
+        HIPCHK(hipEventElapsedTime(&f, S.ev[k], S.ev[k + 1]));
+        ms[k] = f;
+    }
     return SNAPGPU_OK;
 }
 

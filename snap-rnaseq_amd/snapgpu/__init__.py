@@ -593,6 +593,27 @@ class BaseAligner:
         _check(lib().snapgpu_bgzf_last_ms(self._h, C.byref(k), C.byref(d)), "bgzf_last_ms")
         return k.value, d.value
 
+    def bai_build(self, records, n_ref, stream_offset=0):
+        """(BGZF members without the EOF block, .bai index) of the coordinate-sorted BAM records `records`,
+        both made on the GPU (snapgpu_bai_build_gpu: upload, device BGZF, index, two downloads).  The index
+        is byte-identical to the module-level bai_build over those members."""
+        src = np.frombuffer(bytes(records), dtype=np.uint8)
+        n = int(src.size)
+        zcap = n + (n // 0xff00 + 1) * 31 + 28
+        icap = int(lib().snapgpu_bai_size_bound(n // 36, int(n_ref), n))
+        zbuf, ibuf = np.empty(max(1, zcap), dtype=np.uint8), np.empty(max(1, icap), dtype=np.uint8)
+        zused, iused = C.c_uint64(), C.c_uint64()
+        _check(lib().snapgpu_bai_build_gpu(self._h, src.ctypes.data if n else None, n, int(n_ref), int(stream_offset),
+                                           zbuf.ctypes.data, zcap, C.byref(zused), ibuf.ctypes.data, icap, C.byref(iused)),
+               "bai_build_gpu")
+        return zbuf[:zused.value].tobytes(), ibuf[:iused.value].tobytes()
+
+    def bai_ms(self):
+        """(kernel ms, download ms) of the last device BAI call (snapgpu_bai_last_ms)."""
+        k, d = C.c_double(), C.c_double()
+        _check(lib().snapgpu_bai_last_ms(self._h, C.byref(k), C.byref(d)), "bai_last_ms")
+        return k.value, d.value
+
     def bgzf_inflate(self, data):
         """The bytes of the BGZF stream `data`, inflated on the GPU (snapgpu_bgzf_inflate_gpu: uploads the
         stream, one wave per member, downloads the bytes).  Byte-identical to the module-level
@@ -962,6 +983,26 @@ class DeviceReads:
             timing["done"] = time.perf_counter()
         return buf[:used.value].tobytes()
 
+    def run_bai(self, stream_offset=0):
+        """The .bai index of the records of the last run_bam(sorted_output=True) over the members of the
+        run_bgzf() after it, built on the GPU (asynchronous; snapgpu_bam_bai_resident).  stream_offset:
+        the compressed bytes ahead of the members in the file (the BGZF of the BAM header).  A later
+        run_bam() or run_bgzf() invalidates it."""
+        _check(lib().snapgpu_bam_bai_resident(self.aligner._h, self._h, int(stream_offset)), "bam_bai_resident")
+
+    def bai(self, timing=None):
+        """The index run_bai() built -> bytes (waits).  timing: as sam()."""
+        used = C.c_uint64()
+        fn = lib().snapgpu_bam_bai_download
+        rc = fn(self.aligner._h, self._h, None, 0, C.byref(used))
+        if rc != 0 and used.value == 0:
+            _check(rc, "bam_bai_download")
+        buf = np.empty(max(1, used.value), dtype=np.uint8)
+        _check(fn(self.aligner._h, self._h, buf.ctypes.data, used.value, C.byref(used)), "bam_bai_download")
+        if timing is not None:
+            timing["done"] = time.perf_counter()
+        return buf[:used.value].tobytes()
+
     def __del__(self):
         if getattr(self, "_h", None):
             lib().snapgpu_device_reads_free(self._h)
@@ -1194,6 +1235,41 @@ def bgzf_compress(data, eof=True):
     _check(lib().snapgpu_bgzf_compress(src.ctypes.data if n else None, n, int(bool(eof)), buf.ctypes.data, cap,
                                        C.byref(used)), "bgzf_compress")
     return buf[:used.value].tobytes()
+
+
+def bai_build(records, bgzf, n_ref, stream_offset=0):
+    """The .bai index of the coordinate-sorted BAM records `records` and a BGZF stream `bgzf` of them
+    (bgzf_compress's, bgzf_compress_model's or the device's; with or without the EOF block) -> bytes.
+    stream_offset: the compressed bytes ahead of that stream in the file.  The host model of the device
+    index (snapgpu_bai_build; needs no GPU)."""
+    rec = np.frombuffer(bytes(records), dtype=np.uint8)
+    z = np.frombuffer(bytes(bgzf), dtype=np.uint8)
+    fn = lib().snapgpu_bai_build
+    args = (rec.ctypes.data if rec.size else None, int(rec.size), int(n_ref), z.ctypes.data if z.size else None,
+            int(z.size), int(stream_offset))
+    used = C.c_uint64()
+    rc = fn(*args, None, 0, C.byref(used))
+    if rc != 0 and used.value == 0:
+        _check(rc, "bai_build")
+    buf = np.empty(max(1, used.value), dtype=np.uint8)
+    _check(fn(*args, buf.ctypes.data, used.value, C.byref(used)), "bai_build")
+    return buf[:used.value].tobytes()
+
+
+def write_sorted_bam(path, index, sam_header_text, dev):
+    """Write the coordinate-sorted BGZF BAM `path` and its index `path + ".bai"` from a resident batch
+    after run_bam(sorted_output=True): the BAM header compressed on the host (no EOF block), then
+    run_bgzf()'s members and the EOF block; the index is run_bai()'s, with the header's compressed
+    bytes as its stream offset."""
+    head = bgzf_compress(bam_header(index, sam_header_text), eof=False)
+    dev.run_bgzf()
+    dev.run_bai(stream_offset=len(head))
+    body, bai = dev.bgzf(), dev.bai()
+    with open(path, "wb") as f:
+        f.write(head)
+        f.write(body)
+    with open(path + ".bai", "wb") as f:
+        f.write(bai)
 
 
 def _bgzf_call(fn, data, eof, what):
