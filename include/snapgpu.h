@@ -812,6 +812,37 @@ int snapgpu_bai_build_gpu(snapgpu_aligner_t *a, const char *records, uint64_t n,
                           uint64_t *baiUsed);
 int snapgpu_bai_last_ms(snapgpu_aligner_t *a, double *kernelMs, double *downloadMs);
 
+/* Duplicate marking (FLAG 0x400) over a coordinate-sorted stream of single-end BAM records, in one
+ * canonical form (csrc/dupmark_rule.h): a record is considered when it has a refID, pos >= 0
+ * and FLAG 0x4 clear; the considered records of one (refID, pos, FLAG & 0x10) are a group; a record's
+ * score is the sum of its QUAL bytes, 0xff counting 0; the group's highest score is kept, the earliest
+ * of the stream among equals; every other record of the group gets 0x400 and every record that is not
+ * marked has it cleared.  Only byte 19 of a record ever changes, and a second application changes nothing.
+ * snapgpu_bam_mark_duplicates: the host model, in place over the n bytes at records; *nGroups counts the
+ * groups of two or more.  SNAPGPU_EFORMAT naming the record's index for what snapgpu_bai_build refuses
+ * (a truncated record, refID outside [-1, nRef), pos < 0 with a refID, an end past 2^29, records out of
+ * order), for l_seq > 2^24 and for QUAL passing the record's end; SNAPGPU_EINVAL for a record with a
+ * mate (FLAG 0x1: the mate rule is not built).  A refused stream is left as it was.
+ * snapgpu_bam_dupmark_resident: asynchronous, on the stream of the BAM passes (dupmark.hip): marks the
+ * records of the batch's last snapgpu_bam_resident_sorted where they lie (SNAPGPU_EINVAL when the last
+ * BAM call was not the sorted one).  The batch's compressed stream and index become stale, as after a
+ * new snapgpu_bam_resident*; snapgpu_bam_download then returns the marked records (SNAPGPU_EDEVICE if
+ * the device counted a refused or mate-carrying record, or marks that do not add up to the groups'
+ * sizes).  A later snapgpu_bam_resident* writes the records again, unmarked.
+ * snapgpu_bam_dupmark_stats: waits; the marked records and the groups of two or more; SNAPGPU_EINVAL
+ * without a mark call since the batch's last BAM call, SNAPGPU_EDEVICE as snapgpu_bam_download.
+ * snapgpu_bam_mark_duplicates_gpu: the batch form: upload, the same kernels, download in place.  A
+ * truncated record is SNAPGPU_EFORMAT; whatever else the model refuses is SNAPGPU_EDEVICE here, and
+ * the caller's records stay as they were.
+ * snapgpu_bam_dupmark_last_ms: kernel time (HIP events over all passes) and, for the batch form, the
+ * download time of the aligner's last device marking. */
+int snapgpu_bam_mark_duplicates(char *records, uint64_t n, int32_t nRef, uint64_t *nMarked, uint64_t *nGroups);
+int snapgpu_bam_dupmark_resident(snapgpu_aligner_t *a, snapgpu_device_reads_t *d);
+int snapgpu_bam_dupmark_stats(snapgpu_aligner_t *a, snapgpu_device_reads_t *d, uint64_t *nMarked, uint64_t *nGroups);
+int snapgpu_bam_mark_duplicates_gpu(snapgpu_aligner_t *a, char *records, uint64_t n, int32_t nRef, uint64_t *nMarked,
+                                    uint64_t *nGroups);
+int snapgpu_bam_dupmark_last_ms(snapgpu_aligner_t *a, double *kernelMs, double *downloadMs);
+
 /* BGZF inflated (host/inflate.cpp, inflate.hip over inflate_block.h): a stream of BGZF members, as
  * bgzip, samtools and the compressors above write them, back to its bytes.  Every form first walks
  * the members (magic, CM 8, FLG 4, a BC subfield anywhere in the extra field, BSIZE inside the

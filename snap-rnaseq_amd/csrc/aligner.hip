@@ -29,6 +29,7 @@
 #include "bam_format.h"
 #include "bgzf.h"
 #include "bai.h"
+#include "dupmark.h"
 #include "fastq_parse.h"
 #include "inflate.h"
 #include "sam_format.h"
@@ -1221,6 +1222,17 @@ struct BaiState {
     double downloadMs = 0;
 };
 
+// Device duplicate marking (dupmark.hip) state of one resident batch, or of the aligner's batch form:
+// grow-only device buffers -- the passes' work area (dupgpu::Layout), the batch form's records and starts.
+struct DupState {
+    SamState::Buf work, in, starts;
+    dupgpu::Layout L{};
+    bool ran = false;         // the batch's records are the marked ones of its last BAM call
+    bool launched = false;    // ev[kPasses] was recorded: kernels may still use the buffers
+    hipEvent_t ev[dupgpu::kPasses + 1] = {};   // around the passes
+    double downloadMs = 0;
+};
+
 struct snapgpu_device_reads {
     snapgpu_aligner_t *owner = nullptr;
     char *dBases = nullptr, *dQuals = nullptr;
@@ -1251,6 +1263,7 @@ struct snapgpu_device_reads {
     BamState bam;
     BgzfState bgzf;
     BaiState bai;
+    DupState dup;
 };
 
 struct snapgpu_aligner {
@@ -1355,6 +1368,8 @@ struct snapgpu_aligner {
     BgzfState *bgzfLast = nullptr; // snapgpu_bgzf_last_ms
     BaiState baiBatch;
     BaiState *baiLast = nullptr;   // snapgpu_bai_last_ms
+    DupState dupBatch;
+    DupState *dupLast = nullptr;   // snapgpu_bam_dupmark_last_ms
     int bgzfGrid = 0;              // workgroups of the compress pass: one per CU
     void *samPin[2] = {};
     hipEvent_t samPinDone[2] = {};
@@ -1741,6 +1756,17 @@ void baiStateFree(const snapgpu_aligner_t *a, BaiState &S) {
             if (e) { hipEventDestroy(e); e = nullptr; }
 }
 
+void dupStateFree(const snapgpu_aligner_t *a, DupState &S) {
+    for (auto *b : {&S.work, &S.in, &S.starts}) {
+        devFree(a, b->p);
+        b->p = nullptr;
+        b->cap = 0;
+    }
+    if (!(a && a->failed))
+        for (auto &e : S.ev)
+            if (e) { hipEventDestroy(e); e = nullptr; }
+}
+
 // Wait for an event, honouring SNAPGPU_TIMEOUT_S: on expiry the aligner is marked failed.
 int waitEvent(snapgpu_aligner_t *a, hipEvent_t ev) {
     if (a->failed) { snapgpu::setError("aligner failed earlier (device timeout): no further work accepted"); return SNAPGPU_EDEVICE; }
@@ -2000,6 +2026,7 @@ void snapgpu_aligner_free(snapgpu_aligner_t *a) {
     bamStateFree(a, a->bamBatch);
     bgzfStateFree(a, a->bgzfBatch);
     baiStateFree(a, a->baiBatch);
+    dupStateFree(a, a->dupBatch);
     for (int k = 0; k < 2; k++) {
         if (!a->failed) hostPinnedFree(a->samPin[k]);
         if (a->samPinDone[k]) hipEventDestroy(a->samPinDone[k]);
@@ -2243,6 +2270,8 @@ void snapgpu_device_reads_free(snapgpu_device_reads_t *d) {
     bgzfStateFree(a, d->bgzf);
     if (a && a->baiLast == &d->bai) const_cast<snapgpu_aligner_t *>(a)->baiLast = nullptr;
     baiStateFree(a, d->bai);
+    if (a && a->dupLast == &d->dup) const_cast<snapgpu_aligner_t *>(a)->dupLast = nullptr;
+    dupStateFree(a, d->dup);
     delete d;
 }
 
@@ -3767,6 +3796,21 @@ static int bamDownload(snapgpu_aligner_t *a, BamState &S, char *out, uint64_t ca
     return SNAPGPU_OK;
 }
 
+// Wait for the mark passes of S and take their counts; SNAPGPU_EDEVICE unless they add up.
+static int dupResult(snapgpu_aligner_t *a, DupState &S, dupgpu::Result *r) {
+    if (int rc = waitEvent(a, S.ev[dupgpu::kPasses])) return rc;
+    HIPCHK(hipMemcpy(r, (const char *)S.work.p + S.L.res, sizeof *r, hipMemcpyDeviceToHost));
+    if (r->refused || r->mates || r->marked != r->expected) {
+        char msg[240];
+        snprintf(msg, sizeof msg, "dupmark: %u records are refused or out of (refID, pos) order, %u carry a mate (FLAG 0x1), "
+                                  "%llu records marked where the groups' sizes give %llu",
+                 r->refused, r->mates, r->marked, r->expected);
+        snapgpu::setError(msg);
+        return SNAPGPU_EDEVICE;
+    }
+    return SNAPGPU_OK;
+}
+
 // snapgpu_sam_resident and snapgpu_sam_resident_sorted; bam: snapgpu_bam_resident and
 // snapgpu_bam_resident_sorted, the same checks and ordering over the batch's BAM state
 static int samResident(snapgpu_aligner_t *a, snapgpu_device_reads_t *d, const snapgpu_reads_t *reads,
@@ -3898,7 +3942,8 @@ static int samResident(snapgpu_aligner_t *a, snapgpu_device_reads_t *d, const sn
         HIPCHK(hipEventRecord(L.done, L.stream));
         HIPCHK(hipStreamWaitEvent(st, L.done, 0));
     }
-    if (bam) d->bgzf.ran = d->bai.ran = false;   // the records change: a compressed stream of the earlier ones, and its index, are stale
+    // the records change: a compressed stream of the earlier ones, its index and their marking are stale
+    if (bam) d->bgzf.ran = d->bai.ran = d->dup.ran = false;
     if (int rc = bam ? bamLaunch(a, d->bam, A, n, sorted, nmCarryIn) : samLaunch(a, S, A, n, sorted)) return rc;
     // the next pass set over these reads rewrites the records: it waits for the SAM / BAM kernels
     HIPCHK(hipEventRecord(a->residentSideDone, st));
@@ -4033,6 +4078,10 @@ int snapgpu_bam_download(snapgpu_aligner_t *a, snapgpu_device_reads_t *d, char *
     if (a->failed) { snapgpu::setError("aligner failed earlier (device timeout)"); return SNAPGPU_EDEVICE; }
     if (!d->bam.ran) { snapgpu::setError("bam_download: no snapgpu_bam_resident before snapgpu_bam_download"); return SNAPGPU_EINVAL; }
     HIPCHK(hipSetDevice(a->device));
+    if (d->dup.ran) {   // the records are the marked ones: the mark passes have to be through, and sound
+        dupgpu::Result r{};
+        if (int rc = dupResult(a, d->dup, &r)) { *used = 0; return rc; }
+    }
     return bamDownload(a, d->bam, out, cap, used, nmCarryOut);
 }
 
@@ -4344,6 +4393,127 @@ int snapgpu_internal_bai_pass_ms(snapgpu_aligner_t *a, double *ms) {
     BaiState &S = *a->baiLast;
     HIPCHK(hipEventSynchronize(S.ev[baigpu::kPasses]));
     for (int k = 0; k < baigpu::kPasses; k++) {
+        float f = 0;
+        HIPCHK(hipEventElapsedTime(&f, S.ev[k], S.ev[k + 1]));
+        ms[k] = f;
+    }
+    return SNAPGPU_OK;
+}
+
+// ------------------------------------------------- duplicate marking on the device (dupmark.hip)
+// The mark passes on the side stream over n records at text + start[i].
+static int dupLaunch(snapgpu_aligner_t *a, DupState &S, char *text, const uint64_t *start, uint64_t n, uint32_t nRef) {
+    for (auto &e : S.ev)
+        if (!e) HIPCHK(hipEventCreate(&e));
+    if (n > 0xfffffffeull) { snapgpu::setError("dupmark: batch too large"); return SNAPGPU_EINVAL; }
+    // an earlier call's kernels may still use the buffers that grow
+    if (S.launched) HIPCHK(hipEventSynchronize(S.ev[dupgpu::kPasses]));
+    S.ran = false;
+    uint64_t temp = 0;
+    HIPCHK(dupgpu::tempBytes(n, a->sideStream, &temp));
+    S.L = dupgpu::layout(n, temp);
+    HIPCHK(samGrow(a, S.work, S.L.bytes));
+    S.downloadMs = 0;
+    a->dupLast = &S;
+    HIPCHK(dupgpu::launch((uint8_t *)text, start, n, nRef, (char *)S.work.p, S.L, a->sideStream, S.ev));
+    S.ran = S.launched = true;
+    return SNAPGPU_OK;
+}
+
+int snapgpu_bam_dupmark_resident(snapgpu_aligner_t *a, snapgpu_device_reads_t *d) {
+    if (!a || !d) { snapgpu::setError("bam_dupmark_resident: null argument"); return SNAPGPU_EINVAL; }
+    if (a->failed) { snapgpu::setError("aligner failed earlier (device timeout)"); return SNAPGPU_EDEVICE; }
+    if (d->owner != a) { snapgpu::setError("bam_dupmark_resident: the resident batch belongs to another aligner"); return SNAPGPU_EINVAL; }
+    if (!d->bam.ran || !d->bam.sorted) {
+        snapgpu::setError("bam_dupmark_resident: the batch's last BAM call was not snapgpu_bam_resident_sorted (or there was none)");
+        return SNAPGPU_EINVAL;
+    }
+    HIPCHK(hipSetDevice(a->device));
+    BamState &R = d->bam;
+    const uint32_t nRef = (uint32_t)a->idx->genome->pieceOffsets.size();
+    d->bgzf.ran = d->bai.ran = false;   // the records change: a compressed stream of the earlier ones, and its index, are stale
+    if (int rc = dupLaunch(a, d->dup, (char *)R.text.p, (const uint64_t *)R.start.p, R.n, nRef)) return rc;
+    // the next pass set over these reads rewrites the records: it waits for the mark kernels too
+    HIPCHK(hipEventRecord(a->residentSideDone, a->sideStream));
+    a->residentSidePending = true;
+    return SNAPGPU_OK;
+}
+
+int snapgpu_bam_dupmark_stats(snapgpu_aligner_t *a, snapgpu_device_reads_t *d, uint64_t *nMarked, uint64_t *nGroups) {
+    if (!a || !d || !nMarked || !nGroups) { snapgpu::setError("bam_dupmark_stats: null argument"); return SNAPGPU_EINVAL; }
+    if (a->failed) { snapgpu::setError("aligner failed earlier (device timeout)"); return SNAPGPU_EDEVICE; }
+    if (!d->dup.ran) {
+        snapgpu::setError("bam_dupmark_stats: no snapgpu_bam_dupmark_resident since the batch's last snapgpu_bam_resident");
+        return SNAPGPU_EINVAL;
+    }
+    HIPCHK(hipSetDevice(a->device));
+    dupgpu::Result r{};
+    *nMarked = *nGroups = 0;
+    if (int rc = dupResult(a, d->dup, &r)) return rc;
+    *nMarked = r.marked;
+    *nGroups = r.groups;
+    return SNAPGPU_OK;
+}
+
+int snapgpu_bam_mark_duplicates_gpu(snapgpu_aligner_t *a, char *records, uint64_t n, int32_t nRef, uint64_t *nMarked,
+                                    uint64_t *nGroups) {
+    if (!a || (!records && n) || !nMarked || !nGroups || nRef < 0) { snapgpu::setError("bam_mark_duplicates_gpu: bad argument"); return SNAPGPU_EINVAL; }
+    if (a->failed) { snapgpu::setError("aligner failed earlier (device timeout)"); return SNAPGPU_EDEVICE; }
+    *nMarked = *nGroups = 0;
+    // the record starts: a walk over the block sizes on the host
+    std::vector<uint64_t> starts;
+    for (uint64_t u = 0; u < n;) {
+        starts.push_back(u);
+        const uint64_t bytes = n - u < 4 ? 0 : (uint64_t)baiindex::load32((const uint8_t *)records + u) + 4;
+        if (bytes < baiindex::kFixed || bytes > n - u) {
+            snapgpu::setError("bam_mark_duplicates_gpu: record " + std::to_string(starts.size() - 1) + ": truncated");
+            return SNAPGPU_EFORMAT;
+        }
+        u += bytes;
+    }
+    starts.push_back(n);
+    const uint64_t nRec = starts.size() - 1;
+    HIPCHK(hipSetDevice(a->device));
+    DupState &S = a->dupBatch;
+    if (S.launched) HIPCHK(hipEventSynchronize(S.ev[dupgpu::kPasses]));
+    S.ran = false;
+    HIPCHK(samGrow(a, S.in, n + 64));
+    if (n) HIPCHK(hipMemcpyAsync(S.in.p, records, n, hipMemcpyHostToDevice, a->sideStream));
+    HIPCHK(samGrow(a, S.starts, starts.size() * 8));
+    HIPCHK(hipMemcpyAsync(S.starts.p, starts.data(), starts.size() * 8, hipMemcpyHostToDevice, a->sideStream));
+    HIPCHK(hipStreamSynchronize(a->sideStream));   // the host copies may go
+    if (int rc = dupLaunch(a, S, (char *)S.in.p, (const uint64_t *)S.starts.p, nRec, (uint32_t)nRef)) return rc;
+    dupgpu::Result r{};
+    if (int rc = dupResult(a, S, &r)) return rc;   // the caller's records stay as they were
+    const auto t0 = std::chrono::steady_clock::now();
+    if (n) HIPCHK(hipMemcpy(records, S.in.p, n, hipMemcpyDeviceToHost));
+    S.downloadMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    *nMarked = r.marked;
+    *nGroups = r.groups;
+    return SNAPGPU_OK;
+}
+
+int snapgpu_bam_dupmark_last_ms(snapgpu_aligner_t *a, double *kernelMs, double *downloadMs) {
+    if (!a || !kernelMs || !downloadMs) return SNAPGPU_EINVAL;
+    if (!a->dupLast || !a->dupLast->ran) { snapgpu::setError("bam_dupmark_last_ms: no device duplicate marking on this aligner"); return SNAPGPU_EINVAL; }
+    if (a->failed) { snapgpu::setError("aligner failed earlier (device timeout)"); return SNAPGPU_EDEVICE; }
+    HIPCHK(hipSetDevice(a->device));
+    DupState &S = *a->dupLast;
+    float f = 0;
+    HIPCHK(hipEventSynchronize(S.ev[dupgpu::kPasses]));
+    HIPCHK(hipEventElapsedTime(&f, S.ev[0], S.ev[dupgpu::kPasses]));
+    *kernelMs = f;
+    *downloadMs = S.downloadMs;
+    return SNAPGPU_OK;
+}
+
+// ms[0 .. dupgpu::kPasses): the passes of the last device duplicate marking (tools/dupmark_time.py)
+int snapgpu_internal_dupmark_pass_ms(snapgpu_aligner_t *a, double *ms) {
+    if (!a || !ms || !a->dupLast || !a->dupLast->ran || a->failed) return SNAPGPU_EINVAL;
+    HIPCHK(hipSetDevice(a->device));
+    DupState &S = *a->dupLast;
+    HIPCHK(hipEventSynchronize(S.ev[dupgpu::kPasses]));
+    for (int k = 0; k < dupgpu::kPasses; k++) {
         float f = 0;
         HIPCHK(hipEventElapsedTime(&f, S.ev[k], S.ev[k + 1]));
         ms[k] = f;

@@ -614,6 +614,22 @@ class BaseAligner:
         _check(lib().snapgpu_bai_last_ms(self._h, C.byref(k), C.byref(d)), "bai_last_ms")
         return k.value, d.value
 
+    def bam_mark_duplicates(self, records, n_ref):
+        """(records with FLAG 0x400 on the duplicates, n_marked, n_groups) of the coordinate-sorted single-end
+        BAM records `records`, marked on the GPU (snapgpu_bam_mark_duplicates_gpu: upload, the mark passes,
+        download).  Byte-identical to the module-level bam_mark_duplicates."""
+        buf = np.frombuffer(bytes(records), dtype=np.uint8).copy()
+        marked, groups = C.c_uint64(), C.c_uint64()
+        _check(lib().snapgpu_bam_mark_duplicates_gpu(self._h, buf.ctypes.data if buf.size else None, int(buf.size), int(n_ref),
+                                                     C.byref(marked), C.byref(groups)), "bam_mark_duplicates_gpu")
+        return buf.tobytes(), marked.value, groups.value
+
+    def dupmark_ms(self):
+        """(kernel ms, download ms) of the last device duplicate marking (snapgpu_bam_dupmark_last_ms)."""
+        k, d = C.c_double(), C.c_double()
+        _check(lib().snapgpu_bam_dupmark_last_ms(self._h, C.byref(k), C.byref(d)), "bam_dupmark_last_ms")
+        return k.value, d.value
+
     def bgzf_inflate(self, data):
         """The bytes of the BGZF stream `data`, inflated on the GPU (snapgpu_bgzf_inflate_gpu: uploads the
         stream, one wave per member, downloads the bytes).  Byte-identical to the module-level
@@ -983,6 +999,20 @@ class DeviceReads:
             timing["done"] = time.perf_counter()
         return buf[:used.value].tobytes()
 
+    def run_dupmark(self):
+        """Mark the duplicates (FLAG 0x400) among the records of the last run_bam(sorted_output=True), where
+        they lie on the GPU (asynchronous; snapgpu_bam_dupmark_resident).  bam() then returns the marked
+        records; an earlier run_bgzf() or run_bai() is stale and has to be run again.  A later run_bam()
+        writes the records again, unmarked."""
+        _check(lib().snapgpu_bam_dupmark_resident(self.aligner._h, self._h), "bam_dupmark_resident")
+
+    def dupmark_stats(self):
+        """(n_marked, n_groups) of the last run_dupmark() (waits): the records that carry 0x400 and the
+        groups of two or more."""
+        marked, groups = C.c_uint64(), C.c_uint64()
+        _check(lib().snapgpu_bam_dupmark_stats(self.aligner._h, self._h, C.byref(marked), C.byref(groups)), "bam_dupmark_stats")
+        return marked.value, groups.value
+
     def run_bai(self, stream_offset=0):
         """The .bai index of the records of the last run_bam(sorted_output=True) over the members of the
         run_bgzf() after it, built on the GPU (asynchronous; snapgpu_bam_bai_resident).  stream_offset:
@@ -1256,12 +1286,26 @@ def bai_build(records, bgzf, n_ref, stream_offset=0):
     return buf[:used.value].tobytes()
 
 
-def write_sorted_bam(path, index, sam_header_text, dev):
+def bam_mark_duplicates(records, n_ref):
+    """(records with FLAG 0x400 on the duplicates, n_marked, n_groups) of the coordinate-sorted single-end
+    BAM records `records`: the host model of the device marking (snapgpu_bam_mark_duplicates; needs no
+    GPU).  n_groups counts the groups of two or more."""
+    buf = np.frombuffer(bytes(records), dtype=np.uint8).copy()
+    marked, groups = C.c_uint64(), C.c_uint64()
+    _check(lib().snapgpu_bam_mark_duplicates(buf.ctypes.data if buf.size else None, int(buf.size), int(n_ref),
+                                             C.byref(marked), C.byref(groups)), "bam_mark_duplicates")
+    return buf.tobytes(), marked.value, groups.value
+
+
+def write_sorted_bam(path, index, sam_header_text, dev, mark_duplicates=False):
     """Write the coordinate-sorted BGZF BAM `path` and its index `path + ".bai"` from a resident batch
     after run_bam(sorted_output=True): the BAM header compressed on the host (no EOF block), then
     run_bgzf()'s members and the EOF block; the index is run_bai()'s, with the header's compressed
-    bytes as its stream offset."""
+    bytes as its stream offset.  mark_duplicates: run_dupmark() ahead of the compressor, so that the
+    file's records carry FLAG 0x400 on the duplicates."""
     head = bgzf_compress(bam_header(index, sam_header_text), eof=False)
+    if mark_duplicates:
+        dev.run_dupmark()
     dev.run_bgzf()
     dev.run_bai(stream_offset=len(head))
     body, bai = dev.bgzf(), dev.bai()

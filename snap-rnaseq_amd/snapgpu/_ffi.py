@@ -412,6 +412,12 @@ _PROTOS = [
     ("snapgpu_bai_build_gpu", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32, C.c_uint64, C.c_void_p, C.c_uint64,
                                         C.POINTER(C.c_uint64), C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
     ("snapgpu_bai_last_ms", C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    ("snapgpu_bam_mark_duplicates", C.c_int, [C.c_void_p, C.c_uint64, C.c_int32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    ("snapgpu_bam_dupmark_resident", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("snapgpu_bam_dupmark_stats", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    ("snapgpu_bam_mark_duplicates_gpu", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32, C.POINTER(C.c_uint64),
+                                                  C.POINTER(C.c_uint64)]),
+    ("snapgpu_bam_dupmark_last_ms", C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     ("snapgpu_bgzf_inflate_size", C.c_int, [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     ("snapgpu_bgzf_inflate", C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
     ("snapgpu_bgzf_inflate_model", C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
