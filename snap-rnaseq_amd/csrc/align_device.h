@@ -53,6 +53,14 @@ constexpr uint32_t NONE = 0xffffffffu;
 constexpr uint32_t ELCAP = 6;             // Elem64 kernels: elements 0..ELCAP-1 of a read are kept in LDS
                                          // (32 fit 4 waves/SIMD; 6 keep <128> within the 8 KB of 5 waves/SIMD)
 
+// seed_lookup_kernel's output (seed_lookup.h): 16 bytes per (read, seed k of the sequence, k < SEEDS_PER_READ)
+struct SeedRec {
+    uint32_t meta;      // bit31 valid, [7:0] offset, bit8 found, bit9 comp, bit10 palindrome, [30:16] probes
+    uint32_t v1, v2;    // slot values (GenomeIndex.cpp:1004-1010 swaps them when comp)
+    uint32_t cnt;       // overflow counts, u16 each, saturated: [15:0] value1 side, [31:16] value2 side
+};
+constexpr int SEEDS_PER_READ = 16;   // = lanes per read in seed_lookup_kernel: 4 reads per wave
+
 struct DevTables {
     double indel[64];
     double phred[256];

@@ -1,9 +1,10 @@
 // aligner.hip -- gfx950 kernels for batched BaseAligner::AlignRead and the C-ABI
-// aligner of include/snapgpu.h.  See align_device.h for the device data layout.
+// aligner of include/snapgpu.h.  See align_device.h for the device data layout.  The resident I/O
+// chain's host side is in fastq_upload.hip (in) and output_chain.hip (out); aligner_state.h holds the
+// state they share with this file.
 #include <hip/hip_runtime.h>
 
 #include <chrono>
-#include <functional>
 #include <cmath>
 #include <cstring>
 #include <algorithm>
@@ -14,10 +15,6 @@
 #include <type_traits>
 #include <vector>
 
-#include <fcntl.h>
-#include <sys/stat.h>
-#include <unistd.h>
-
 #include "align_device.h"
 #include "align_score.h"
 #include "seed_lookup.h"
@@ -26,13 +23,7 @@
 #include "internal.h"
 #include "resident_grid.h"
 #include "large_copy.h"
-#include "bam_format.h"
-#include "bgzf.h"
-#include "bai.h"
-#include "dupmark.h"
-#include "fastq_parse.h"
-#include "inflate.h"
-#include "sam_format.h"
+#include "aligner_state.h"
 
 using namespace sgk;
 using snapgpu::uploadLarge;
@@ -995,30 +986,6 @@ namespace {
 
 std::mutex g_errMu;
 
-#define HIPCHK(x)                                                                       \
-    do {                                                                                \
-        hipError_t e_ = (x);                                                            \
-        if (e_ != hipSuccess) {                                                         \
-            snapgpu::setError(std::string(#x) + ": " + hipGetErrorString(e_));          \
-            return SNAPGPU_EDEVICE;                                                     \
-        }                                                                               \
-    } while (0)
-// inside a loop whose exit path cleans up (sets rc and leaves the enclosing loop)
-#define HIPBRK(x)                                                                       \
-    if (hipError_t e_ = (x); e_ != hipSuccess) {                                        \
-        snapgpu::setError(std::string(#x) + ": " + hipGetErrorString(e_));              \
-        rc = SNAPGPU_EDEVICE;                                                           \
-        break;                                                                          \
-    }
-#define HIPCHKN(x)                                                                      \
-    do {                                                                                \
-        hipError_t e_ = (x);                                                            \
-        if (e_ != hipSuccess) {                                                         \
-            snapgpu::setError(std::string(#x) + ": " + hipGetErrorString(e_));          \
-            return nullptr;                                                             \
-        }                                                                               \
-    } while (0)
-
 // libgcc __powidf2 (see oracle / DESIGN.md): the reference's pow(double, int).
 double powi_libgcc(double x, int m) {
     unsigned nn = m < 0 ? -(unsigned)m : (unsigned)m;
@@ -1111,295 +1078,8 @@ int hostMapq(double pAll, double pBest, int score, int popular) {   // mapq.h:32
 
 }  // namespace
 
-// One execution lane = one HIP stream with what the align passes of a pass set need to run
-// beside the other lane: its own element arenas (persistent waves index them by blockIdx) and
-// lookup statistics.  Lane 0 serves the resident API (snapgpu_reads_upload /
-// snapgpu_align_resident); snapgpu_align_batch alternates chunks over both lanes so one chunk's
-// copies and host tail overlap the other chunk's kernels, and the second lane's align kernel
-// fills the first one's tail.  The front stage of every pass set (counter clear, record
-// pre-fill, pass 0, order_long_kernel, the simple pass) runs on the aligner's one front stream,
-// a chunk or two ahead of the lanes; it writes only per-chunk buffers (ChunkSlot, EvSet).
-// One chunk's input/output staging of the pipelined snapgpu_align_batch and the buffers its
-// front stage writes.  Two per lane: the H2D of a lane's next chunk (on the aligner's copy stream)
-// and its front stage run while the lane's current chunk is still in its align kernels, so the
-// lane's next align kernel can start the moment the current one frees wave slots.
-struct ChunkSlot {
-    char *dBases = nullptr, *dQuals = nullptr;  // device inputs
-    uint64_t *dOffsets = nullptr;
-    uint32_t *dLengths = nullptr;
-    uint32_t *dDefer = nullptr;                 // pass-1 / pass-2 defers, arena overflows
-    snapgpu_result_t *dOut = nullptr;
-    SeedRec *dSeeds = nullptr;
-    uint64_t *hOffsets = nullptr;               // pinned staging
-    uint32_t *hLengths = nullptr;
-    snapgpu_result_t *hOut = nullptr;
-    hipEvent_t h2d = nullptr;                   // inputs on the device (copy stream)
-    hipEvent_t done = nullptr;                  // records back in host memory (lane stream)
-    bool pending = false;
-    uint64_t seq = 0, chunkBegin = 0, chunkN = 0, chunkEv = 0;
-    snapgpu_result_t *chunkOut = nullptr;       // the caller's record array of the pending chunk
-};
-
-struct ExecLane {
-    hipStream_t stream = nullptr;
-    void *arena = nullptr;                     // main passes: arenaCap elements per wave
-    void *bigArena = nullptr;                  // big-arena pass: arenaElems per wave (only when arenaCap < arenaElems)
-    unsigned long long *lookupStats = nullptr; // seed_lookup_kernel: [256][4] seeds, probes, overflow counts (per call)
-    hipEvent_t done = nullptr;                 // scratch event: waitLane, cross-lane ordering
-    // chunk buffers of the pipelined snapgpu_align_batch (grown on demand)
-    uint64_t capReads = 0, capBytes = 0;
-    ChunkSlot slot[2];
-    uint32_t nextSlot = 0;
-    unsigned long long *hLookupStats = nullptr; // pinned copy of lookupStats
-};
-
-// Timing events of one pass set (one chunk), its device work counters and their pinned copy.
-struct EvSet {
-    // front stream: 3 before pass 0, 0 after pass 0 (and order_long_kernel), 4 after the simple
-    // pass (the lane stream waits for it); lane stream: 5 before pass 1, 1 after pass 1, 2 after
-    // passes 2 and 3
-    hipEvent_t e[6] = {};
-    // [0] pass-1 work, [1] pass-3 work, [2] pass-1 defers, [3] pass-2 work, [4] pass-2 defers,
-    // [5] long reads (pass 0), [6] arena overflows, [7] big-arena pass work, [8..9] simple pass work /
-    // bails, [10..11] forced-mode statistics, [12..13] simple pass reads / wide.  One per pass set:
-    // the front stage clears it while the lanes' align kernels still use the earlier sets' counters.
-    uint32_t *dCounter = nullptr;
-    uint32_t *hCounter = nullptr;
-};
-
-// Device SAM formatter (sam_format.hip) state of one resident batch, or of the aligner's batch-form
-// calls: grow-only device buffers, as the CIGAR buffers are.
-struct SamState {
-    struct Buf { void *p = nullptr; uint64_t cap = 0; };
-    Buf aux;            // ids, id offsets / lengths, clip arrays, piece names, read group (one packed upload)
-    Buf len, scans, start, sums, text, bad;
-    Buf bases, quals;   // the reads where the unclipped extents pass the resident upload (or the batch form's reads)
-    Buf res, ed, nOps, ops;   // batch form: records and CIGARs from the host
-    // coordinate-sorted calls (samgpu::SortBuffers): keys, their sorted copy, 0 .. n - 1, the output
-    // order, the lengths in that order, rocPRIM's temporary storage
-    Buf key, keySorted, iota, order, slotLen, sortTemp;
-    bool sorted = false;      // the last call was a sorted one: `order` holds its n record indices
-    samline::SortArgs sortArgs{};   // samline::sortKey's per-piece tables in aux (samPrepare)
-    std::vector<char> hAux;   // host copy of aux (alive while its upload may be in flight)
-    uint64_t fullBytes = 0;   // bytes of bases / quals valid in `bases` / `quals` (resident: 0 = the batch's own)
-    bool idsCached = false;   // aux holds the batch's own ids (reads->ids), with this read group:
-    std::string cachedRg;
-    bool cachedHasRg = false;
-    bool cachedDevForm = false;   // ... laid out for a call without a host batch (reads == NULL): no ids, no clip arrays
-    uint64_t n = 0, textBound = 0;
-    bool ran = false;
-    // before the length pass, after the check; after the length pass, after the scan; after the sort step
-    hipEvent_t ev[5] = {};
-    double downloadMs = 0;
-};
-
-// Device BAM encoder (bam_format.hip) state: the SAM formatter's buffers (its own copies: a batch's
-// SAM and BAM calls do not disturb each other) and the NM carry's.
-struct BamState : SamState {
-    Buf nm, nmTiles;
-    int32_t carryIn = 0;
-};
-
-// Device BGZF compressor (bgzf.hip) state of one resident batch, or of the aligner's batch form:
-// grow-only device buffers (bgzfgpu::Buffers), the batch form's copy of its input.
-struct BgzfState {
-    SamState::Buf in, slots, sizes, offs, tokens, packed, res;
-    uint64_t maxBlocks = 0;   // what the last call's buffers were sized for (0: nothing to compress)
-    bool ran = false;         // the compressed stream is that of the batch's last BAM call
-    hipEvent_t ev[4] = {};    // before the compress pass, after it, after the scan, after the check
-    double downloadMs = 0;
-};
-
-// Device BAI builder (bai.hip) state of one resident batch, or of the aligner's batch form: grow-only
-// device buffers -- the passes' work area (baigpu::Layout), the index, the batch form's record starts.
-struct BaiState {
-    SamState::Buf work, out, starts;
-    baigpu::Layout L{};
-    uint64_t n = 0, nRef = 0, outCap = 0;
-    bool ran = false;         // the index is that of the batch's last BAM and BGZF calls
-    bool launched = false;    // ev[kPasses] was recorded: kernels may still use the buffers
-    hipEvent_t ev[baigpu::kPasses + 1] = {};   // around the passes
-    double downloadMs = 0;
-};
-
-// Device duplicate marking (dupmark.hip) state of one resident batch, or of the aligner's batch form:
-// grow-only device buffers -- the passes' work area (dupgpu::Layout), the batch form's records and starts.
-struct DupState {
-    SamState::Buf work, in, starts;
-    dupgpu::Layout L{};
-    bool ran = false;         // the batch's records are the marked ones of its last BAM call
-    bool launched = false;    // ev[kPasses] was recorded: kernels may still use the buffers
-    hipEvent_t ev[dupgpu::kPasses + 1] = {};   // around the passes
-    double downloadMs = 0;
-};
-
-struct snapgpu_device_reads {
-    snapgpu_aligner_t *owner = nullptr;
-    char *dBases = nullptr, *dQuals = nullptr;
-    uint64_t *dOffsets = nullptr;
-    uint32_t *dLengths = nullptr;
-    snapgpu_result_t *dOut = nullptr;
-    uint32_t *dDefer = nullptr;   // pass 1 -> pass 2 read list
-    SeedRec *dSeeds = nullptr;    // seed_lookup_kernel records, SEEDS_PER_READ per read
-    int32_t *dCigEd = nullptr;    // cigar_kernel outputs (allocated by the first snapgpu_cigar_resident)
-    uint32_t *dCigN = nullptr, *dCigOps = nullptr;
-    uint64_t n = 0;
-    uint32_t maxLen = 0;
-    int device = 0;
-    uint64_t bytes = 0;       // bases / quals bytes uploaded: the largest clipped end
-    uint64_t extentHash = 0;  // of the offsets and lengths uploaded (snapgpu_sam_resident checks its batch)
-    // What the device FASTQ parser leaves for the SAM / BAM calls without a host batch (reads == NULL);
-    // a batch from snapgpu_reads_upload has none of it.
-    bool hasIds = false;
-    int clipping = 0;             // 0: no clip arrays (front / unclipped below are not used)
-    char *dIds = nullptr;         // the packed ids, idTotal + 16 bytes
-    char *dMeta = nullptr;        // one allocation: idStart, idLen, front, baseLen (16-byte aligned each)
-    const uint64_t *dIdStart = nullptr;
-    const uint32_t *dIdLen = nullptr, *dFront = nullptr, *dUnclipped = nullptr;
-    char *dTail = nullptr;        // bases, then qualities, of [bytes, total): what the zeroing from `bytes` on took
-    uint64_t total = 0, idTotal = 0;        // bytes of all unclipped reads, of all ids
-    uint32_t maxUnclipped = 0, maxIdLen = 0;
-    SamState sam;
-    BamState bam;
-    BgzfState bgzf;
-    BaiState bai;
-    DupState dup;
-};
-
-struct snapgpu_aligner {
-    int device = 0;
-    const snapgpu_index_t *idx = nullptr;
-    snapgpu_aligner_params_t p{};
-    uint32_t *dOverflow = nullptr, *dPieces = nullptr;
-    // the seed tables' bucket image (bucket_table.h), built on the device at creation
-    uint4 *dBuckets = nullptr;
-    uint64_t *dBucketBase = nullptr;
-    uint32_t *dBucketCount = nullptr;
-    snapgpu_bucket_info_t bucketInfo{};
-    char *dGenomeAlloc = nullptr;
-    GPlane *dGPlanes = nullptr;   // genome bit planes (KArgs::gpl)
-    const char *dGenome = nullptr;
-    DevTables *dTab = nullptr;
-    ExecLane lane[2];
-    std::vector<EvSet> evs;       // one per pass set of the current call (grown on demand)
-    uint64_t nEvUsed = 0;
-    // Pass sets of the two lanes run concurrently: the second lane's waves fill the tail of the
-    // first one's persistent kernel (the last, heavy reads of a launch).  SNAPGPU_OVERLAP=0 runs
-    // them one after the other (copies and host tails still overlap).  With overlap, launch
-    // durations overlap too: snapgpu_timing_t also carries the union of the launch intervals.
-    bool overlapKernels = true;
-    // snapgpu_align_batch_submit: chunks of consecutive batches stream through the lanes until
-    // snapgpu_align_batch_wait; timing and statistics cover that whole stream
-    bool streamOpen = false;
-    uint64_t nextLane = 0;
-    uint64_t chunkSeq = 0;        // submission order of pipelined chunks (finished oldest first)
-    hipStream_t copyStream = nullptr;   // H2D of the pipelined chunks
-    // CIGAR (cigar_kernel) and seed-census (charseeds.hip) calls: their own stream and buffers, so a
-    // host thread can run them while another thread's align call keeps the lanes busy (the RNA
-    // paired path's sub-batch pipeline); a caller serialises them among themselves
-    hipStream_t sideStream = nullptr;
-    // the front stage of every pass set, both lanes' (launch_passes): one stream, so the front
-    // stages run in submission order -- its small kernels take the wave slots a lane's persistent
-    // kernel frees in its tail without queueing behind the other lane's passes 2 / 3 and record copy
-    // (normal priority; SNAPGPU_FRONT_PRIORITY=1: the device's highest)
-    hipStream_t frontStream = nullptr;
-    hipEvent_t frontDone = nullptr;     // scratch event: waitFront, lane -> front ordering
-    uint32_t *dSink = nullptr;          // 64 B nobody reads (snapgpu_gather_peak's result sink)
-    std::chrono::steady_clock::time_point streamStart;
-    uint64_t arenaElems = 0;      // worst case per read: (maxSeeds + 2) * maxHits (+ 64)
-    uint64_t arenaCap = 0;        // per wave in the main passes (= arenaElems unless that cannot fit the grid)
-    int grid = 0, grid256 = 0, grid512 = 0, gridBig = 0;
-    // resident workgroups per CU of each persistent kernel (resident_grid.h) behind those grids
-    int perCU128 = 0, perCU256 = 0, perCU512 = 0, perCUSimple = 0, perCUCigar = 0;
-    bool shortRows = false;       // pass 1 runs align_kernel<128, EXT, SHORT_ROWS>: maxK + extraSearchDepth <= SHORT_ROWS
-    // snapgpu_align_batch chunk (SNAPGPU_CHUNK_READS): a streaming caller's 1M-read batches go
-    // as one chunk each, alternating lanes (fewest persistent-kernel tails; A/B in
-    // profiles/r02/ab/chunk_size_slots.txt); resident runs keep 2^18-read chunks over both lanes
-    uint64_t chunkReads = 1u << 20;
-    uint64_t residentChunk = 1u << 18;
-    // forced mode: reads with at least this many elements get a radix-sorted pop order instead of
-    // windowed ranks (SNAPGPU_RADIX_MIN; beyond SKCAP the ranks stage keys from HBM per window)
-    uint32_t radixMin = SKCAP + 1;
-    bool simplePass = true;       // simple_align_kernel ahead of pass 1 (SNAPGPU_SIMPLE_PASS=0: off)
-    int gridSimple = 0;
-    bool orderLong = true;        // pass 2's list longest-first (SNAPGPU_ORDER_LONG=0: pass 0's order)
-    uint32_t tripRead = 0xffffffffu;   // test hook (snapgpu_aligner_debug_trip): trip the watchdog at this read
-    snapgpu_timing_t timing{};
-    snapgpu_aligner_stats_t stats{};
-    snapgpu_device_reads_t *lastReads = nullptr;
-    bool pendingTiming = false;
-    uint32_t *dDiag = nullptr;    // this aligner's watchdog record (KArgs::diag)
-    unsigned long long *dPhase = nullptr;   // [grid][PH_SLOTS] (SNAPGPU_PHASES=1 diagnostics)
-    double timeoutSec = 0;        // SNAPGPU_TIMEOUT_S
-    // A wait that timed out leaves kernels running on buffers this aligner owns: from then on
-    // nothing is freed or reused (hipFree would block on the running kernel, a reuse could
-    // fault it); every call fails and the process is expected to exit.
-    bool failed = false;
-    hipError_t (*eventQuery)(hipEvent_t) = hipEventQuery;   // test hook (snapgpu_selftest_timeout_path)
-    hipEvent_t cev[2] = {};       // cigar_kernel timing
-    // snapgpu_cigar_resident reads a resident batch's records (d->dOut) on the side stream; the
-    // next pass set over resident reads (launch_resident: its 0xff pre-fill and the passes rewrite
-    // those records) waits for this event on both lanes first
-    hipEvent_t residentSideDone = nullptr;
-    bool residentSidePending = false;
-    int cigarGrid = 0;
-    // snapgpu_align_batch_ex buffers, kept across calls (grow-only): search windows, multi-hit
-    // scratch per block, found counts, hit rows, compaction offsets and the packed hits
-    struct ExBuf { void *p = nullptr; uint64_t cap = 0; } exSearch, exScratch, exFound, exHits, exOff, exDense;
-    // snapgpu_cigar_batch (device inputs, device outputs, pinned staging of the packed inputs) and
-    // the internal scratch slots of snapgpu_internal_devbuf (charseeds.hip), grow-only: a
-    // hipMalloc / hipFree pair per call cost more than the kernels, and hipFree waits for the
-    // whole device (the RNA path's other host thread included)
-    ExBuf cgIn, cgOut, aux[8];
-    // snapgpu_internal_align_batch_packed: its device reads, kept (grow-only) across calls -- a
-    // snapgpu_reads_upload / _free per call is ten hipMalloc / hipFree pairs, and each hipFree waits
-    // for the whole device, the RNA path's concurrent genome aligner included
-    snapgpu_device_reads_t *exReads = nullptr;
-    uint64_t exReadsCapN = 0, exReadsCapBytes = 0;
-    void *cgPin = nullptr, *cgPinOut = nullptr;
-    uint64_t cgPinCap = 0, cgPinOutCap = 0;
-    // device SAM formatter: the batch form's state, the state the last call used (snapgpu_sam_last_ms)
-    // and the pinned staging of the text download (two chunks in flight)
-    SamState samBatch;
-    SamState *samLast = nullptr;
-    BamState bamBatch;
-    BamState *bamLast = nullptr;   // snapgpu_bam_last_ms
-    BgzfState bgzfBatch;
-    BgzfState *bgzfLast = nullptr; // snapgpu_bgzf_last_ms
-    BaiState baiBatch;
-    BaiState *baiLast = nullptr;   // snapgpu_bai_last_ms
-    DupState dupBatch;
-    DupState *dupLast = nullptr;   // snapgpu_bam_dupmark_last_ms
-    int bgzfGrid = 0;              // workgroups of the compress pass: one per CU
-    void *samPin[2] = {};
-    hipEvent_t samPinDone[2] = {};
-    // device FASTQ parser (snapgpu_fastq_upload): the text, newline positions and per-record arrays,
-    // grow-only; the pinned staging of the text upload (two chunks in flight); the last call's times
-    struct FastqState {
-        ExBuf text, counts, tileStart, sums, nl, rec, baseStart, idStart, sums2, tot;
-        void *pin[2] = {};
-        hipEvent_t pinDone[2] = {};
-        hipEvent_t ev[9] = {};   // 0-2 count, scan; 3-6 line starts, record pass, scans; 7-8 copy pass
-        bool ran = false;
-        double uploadMs = 0, kernelMs = 0, downloadMs = 0;
-        double passMs[6] = {};   // count, scan, line starts, records, scans, copy (snapgpu_internal_fastq_pass_ms)
-        double arriveKernelMs = 0;   // kernels that brought the text (the BGZF form's inflate kernel)
-    } fq;
-    // device BGZF inflater (inflate.hip): the compressed stream, its member table, the members'
-    // statuses with the lowest refused index after them, and the batch form's output, grow-only;
-    // the last call's times (snapgpu_bgzf_inflate_last_ms)
-    struct InflateState {
-        ExBuf in, members, status, out;
-        hipEvent_t ev[2] = {};
-        int waves = 0;           // waves of the inflate kernel: inflategpu::kWavesPerCu per CU
-        bool ran = false;
-        double uploadMs = 0, kernelMs = 0, downloadMs = 0;
-    } inf;
-    hipStream_t stream() const { return lane[0].stream; }
-};
-
 static const size_t kDevGuard = 1024;
-static std::atomic<uint64_t> g_devFrees{0};   // hipFree calls made by devFree (selftest)
+std::atomic<uint64_t> g_devFrees{0};
 
 // Random-gather ceiling of the hash-table memory (roofline calibration for
 // seed_lookup_kernel): one independent 64-byte bucket line per load, four
@@ -1703,8 +1383,9 @@ std::vector<std::pair<void *, size_t>> g_pinParked;            // (block, capaci
 std::vector<std::pair<void *, size_t>> g_pinLive;              // blocks handed out, with their capacity
 size_t g_pinParkedBytes = 0;
 
-// Every device free goes through here: after a timeout the aligner's buffers may still be
-// in use by a running kernel, so they are left alone (see snapgpu_aligner::failed).
+}  // namespace
+
+// devFree .. extentMix: what aligner_state.h declares for output_chain.hip and fastq_upload.hip too
 void devFree(const snapgpu_aligner_t *a, void *p) {
     if (!p || (a && a->failed)) return;
     g_devFrees++;
@@ -1713,61 +1394,17 @@ void devFree(const snapgpu_aligner_t *a, void *p) {
 
 void hostPinnedFree(void *p) { if (p) hipHostFree(p); }
 
-void samStateFree(const snapgpu_aligner_t *a, SamState &S) {
-    for (auto *b : {&S.aux, &S.len, &S.scans, &S.start, &S.sums, &S.text, &S.bad, &S.bases, &S.quals, &S.res, &S.ed, &S.nOps, &S.ops,
-                    &S.key, &S.keySorted, &S.iota, &S.order, &S.slotLen, &S.sortTemp}) {
-        devFree(a, b->p);
-        b->p = nullptr;
-        b->cap = 0;
-    }
-    if (!(a && a->failed))
-        for (auto &e : S.ev)
-            if (e) { hipEventDestroy(e); e = nullptr; }
+hipError_t devGrow(const snapgpu_aligner_t *a, DevBuf &b, uint64_t bytes) {
+    const uint64_t want = growBytes(b, bytes);
+    if (!want) return hipSuccess;
+    devFree(a, b.p);
+    b.p = nullptr;
+    b.cap = 0;
+    const hipError_t e = hipMalloc(&b.p, want);
+    if (e == hipSuccess) b.cap = want;
+    return e;
 }
 
-void bamStateFree(const snapgpu_aligner_t *a, BamState &S) {
-    for (auto *b : {&S.nm, &S.nmTiles}) {
-        devFree(a, b->p);
-        b->p = nullptr;
-        b->cap = 0;
-    }
-    samStateFree(a, S);
-}
-
-void bgzfStateFree(const snapgpu_aligner_t *a, BgzfState &S) {
-    for (auto *b : {&S.in, &S.slots, &S.sizes, &S.offs, &S.tokens, &S.packed, &S.res}) {
-        devFree(a, b->p);
-        b->p = nullptr;
-        b->cap = 0;
-    }
-    if (!(a && a->failed))
-        for (auto &e : S.ev)
-            if (e) { hipEventDestroy(e); e = nullptr; }
-}
-
-void baiStateFree(const snapgpu_aligner_t *a, BaiState &S) {
-    for (auto *b : {&S.work, &S.out, &S.starts}) {
-        devFree(a, b->p);
-        b->p = nullptr;
-        b->cap = 0;
-    }
-    if (!(a && a->failed))
-        for (auto &e : S.ev)
-            if (e) { hipEventDestroy(e); e = nullptr; }
-}
-
-void dupStateFree(const snapgpu_aligner_t *a, DupState &S) {
-    for (auto *b : {&S.work, &S.in, &S.starts}) {
-        devFree(a, b->p);
-        b->p = nullptr;
-        b->cap = 0;
-    }
-    if (!(a && a->failed))
-        for (auto &e : S.ev)
-            if (e) { hipEventDestroy(e); e = nullptr; }
-}
-
-// Wait for an event, honouring SNAPGPU_TIMEOUT_S: on expiry the aligner is marked failed.
 int waitEvent(snapgpu_aligner_t *a, hipEvent_t ev) {
     if (a->failed) { snapgpu::setError("aligner failed earlier (device timeout): no further work accepted"); return SNAPGPU_EDEVICE; }
     if (a->timeoutSec > 0) {
@@ -1789,22 +1426,25 @@ int waitEvent(snapgpu_aligner_t *a, hipEvent_t ev) {
     return SNAPGPU_OK;
 }
 
-// Wait for everything queued on a lane's stream (an event recorded now, then waitEvent).
 int waitLane(snapgpu_aligner_t *a, ExecLane &L) {
     if (a->failed) return waitEvent(a, nullptr);
     HIPCHK(hipEventRecord(L.done, L.stream));
     return waitEvent(a, L.done);
 }
 
+uint64_t extentMix(uint64_t h, uint64_t off, uint32_t len) {
+    h = (h ^ off) * 0x9e3779b97f4a7c15ull;
+    h = (h ^ len) * 0xc2b2ae3d27d4eb4full;
+    return h ^ (h >> 29);
+}
+
 // Wait for everything queued on the front stream (a front stage whose lane part was never queued
 // -- a launch that failed half way -- is waited for by nothing else).
-int waitFront(snapgpu_aligner_t *a) {
+static int waitFront(snapgpu_aligner_t *a) {
     if (a->failed) return waitEvent(a, nullptr);
     HIPCHK(hipEventRecord(a->frontDone, a->frontStream));
     return waitEvent(a, a->frontDone);
 }
-
-}  // namespace
 
 namespace snapgpu {
 void *hostAlloc(size_t bytes, bool *pinned, bool zero) {
@@ -2022,25 +1662,12 @@ void snapgpu_aligner_free(snapgpu_aligner_t *a) {
     for (auto &b : a->aux) devFree(a, b.p);
     hostPinnedFree(a->cgPin);
     hostPinnedFree(a->cgPinOut);
-    samStateFree(a, a->samBatch);
-    bamStateFree(a, a->bamBatch);
-    bgzfStateFree(a, a->bgzfBatch);
-    baiStateFree(a, a->baiBatch);
-    dupStateFree(a, a->dupBatch);
+    for (StageState *S : a->batchStages) stageFree(a, *S);
     for (int k = 0; k < 2; k++) {
         if (!a->failed) hostPinnedFree(a->samPin[k]);
         if (a->samPinDone[k]) hipEventDestroy(a->samPinDone[k]);
     }
-    for (auto *b : {&a->fq.text, &a->fq.counts, &a->fq.tileStart, &a->fq.sums, &a->fq.nl, &a->fq.rec, &a->fq.baseStart,
-                    &a->fq.idStart, &a->fq.sums2, &a->fq.tot})
-        devFree(a, b->p);
-    for (int k = 0; k < 2; k++) {
-        if (!a->failed) hostPinnedFree(a->fq.pin[k]);
-        if (a->fq.pinDone[k]) hipEventDestroy(a->fq.pinDone[k]);
-    }
-    for (auto &e : a->fq.ev) if (e) hipEventDestroy(e);
-    for (auto *b : {&a->inf.in, &a->inf.members, &a->inf.status, &a->inf.out}) devFree(a, b->p);
-    for (auto &e : a->inf.ev) if (e) hipEventDestroy(e);
+    fastqStateFree(a);
     snapgpu_device_reads_free(a->exReads);
     for (auto *b : {&a->exSearch, &a->exScratch, &a->exFound, &a->exHits, &a->exOff, &a->exDense}) devFree(a, b->p);
     delete a;
@@ -2211,13 +1838,6 @@ snapgpu_aligner_t *snapgpu_aligner_create(int device, const snapgpu_index_t *idx
     return a;
 }
 
-// running hash of a batch's (offset, length) pairs
-static inline uint64_t extentMix(uint64_t h, uint64_t off, uint32_t len) {
-    h = (h ^ off) * 0x9e3779b97f4a7c15ull;
-    h = (h ^ len) * 0xc2b2ae3d27d4eb4full;
-    return h ^ (h >> 29);
-}
-
 snapgpu_device_reads_t *snapgpu_reads_upload(snapgpu_aligner_t *a, const snapgpu_reads_t *r) {
     if (!a || !r) { snapgpu::setError("reads_upload: null"); return nullptr; }
     if (a->failed) { snapgpu::setError("aligner failed earlier (device timeout)"); return nullptr; }
@@ -2262,16 +1882,10 @@ void snapgpu_device_reads_free(snapgpu_device_reads_t *d) {
     devFree(a, d->dOut); devFree(a, d->dDefer); devFree(a, d->dSeeds);
     devFree(a, d->dCigEd); devFree(a, d->dCigN); devFree(a, d->dCigOps);
     devFree(a, d->dIds); devFree(a, d->dMeta); devFree(a, d->dTail);
-    if (a && a->samLast == &d->sam) const_cast<snapgpu_aligner_t *>(a)->samLast = nullptr;
-    samStateFree(a, d->sam);
-    if (a && a->bamLast == &d->bam) const_cast<snapgpu_aligner_t *>(a)->bamLast = nullptr;
-    bamStateFree(a, d->bam);
-    if (a && a->bgzfLast == &d->bgzf) const_cast<snapgpu_aligner_t *>(a)->bgzfLast = nullptr;
-    bgzfStateFree(a, d->bgzf);
-    if (a && a->baiLast == &d->bai) const_cast<snapgpu_aligner_t *>(a)->baiLast = nullptr;
-    baiStateFree(a, d->bai);
-    if (a && a->dupLast == &d->dup) const_cast<snapgpu_aligner_t *>(a)->dupLast = nullptr;
-    dupStateFree(a, d->dup);
+    for (int st = 0; st < kStages; st++) {   // the aligner must not keep pointing at what goes
+        if (a && a->last[st] == d->stages[st]) d->owner->last[st] = nullptr;
+        stageFree(a, *d->stages[st]);
+    }
     delete d;
 }
 
@@ -3040,31 +2654,21 @@ static int alignPacked(snapgpu_aligner_t *a, const snapgpu_reads_t *const *parts
     AlignExt x;
     // grow-only device buffers of the aligner (hipMalloc / hipFree of the hit rows, ~1 GB for
     // the RNA path's 1000 hits per read, cost more than the kernels)
-    auto ensure = [a](snapgpu_aligner::ExBuf &b, uint64_t bytes) -> hipError_t {
-        if (bytes <= b.cap) return hipSuccess;
-        devFree(a, b.p);
-        b.p = nullptr;
-        b.cap = 0;
-        const uint64_t want = bytes + bytes / 4 + 256;
-        hipError_t e = hipMalloc(&b.p, want);
-        if (e == hipSuccess) b.cap = want;
-        return e;
-    };
     auto cleanup = [&]() { a->lastReads = nullptr; };   // d stays the aligner's (grow-only)
     hipError_t e = hipSuccess;
     const uint64_t n = nAll;
     void *dScratch = nullptr, *dFound = nullptr, *dHits = nullptr;
     if (search) {
-        if ((e = ensure(a->exSearch, n * sizeof(snapgpu_search_t))) == hipSuccess)
+        if ((e = devGrow(a, a->exSearch, n * sizeof(snapgpu_search_t))) == hipSuccess)
             e = hipMemcpyAsync(a->exSearch.p, search, n * sizeof(snapgpu_search_t), hipMemcpyHostToDevice, a->stream());
         x.search = (const snapgpu_search_t *)a->exSearch.p;
     }
     if (e == hipSuccess && maxHitsToGet) {
         const uint64_t blocks = (uint64_t)(a->grid > a->grid512 ? a->grid : a->grid512);
         const uint64_t stride = multiHitStride(maxHitsToGet);
-        if ((e = ensure(a->exScratch, blocks * stride * 4)) == hipSuccess &&
-            (e = ensure(a->exFound, n * sizeof(int32_t))) == hipSuccess)
-            e = ensure(a->exHits, n * maxHitsToGet * sizeof(snapgpu_multi_hit_t));
+        if ((e = devGrow(a, a->exScratch, blocks * stride * 4)) == hipSuccess &&
+            (e = devGrow(a, a->exFound, n * sizeof(int32_t))) == hipSuccess)
+            e = devGrow(a, a->exHits, n * maxHitsToGet * sizeof(snapgpu_multi_hit_t));
         dScratch = a->exScratch.p; dFound = a->exFound.p; dHits = a->exHits.p;
         x.maxHitsToGet = maxHitsToGet;
         x.hitScratch = (uint32_t *)dScratch;
@@ -3093,8 +2697,8 @@ static int alignPacked(snapgpu_aligner_t *a, const snapgpu_reads_t *const *parts
             const uint64_t total = off[n];
             if (total) {
                 dense.resize(total);
-                if ((e = ensure(a->exOff, (n + 1) * sizeof(uint64_t))) == hipSuccess &&
-                    (e = ensure(a->exDense, total * sizeof(snapgpu_multi_hit_t))) == hipSuccess &&
+                if ((e = devGrow(a, a->exOff, (n + 1) * sizeof(uint64_t))) == hipSuccess &&
+                    (e = devGrow(a, a->exDense, total * sizeof(snapgpu_multi_hit_t))) == hipSuccess &&
                     ((dOff = a->exOff.p), (dDense = a->exDense.p), true) &&
                     (e = hipMemcpyAsync(dOff, off.data(), (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice,
                                         a->stream())) == hipSuccess) {
@@ -3530,1671 +3134,6 @@ int snapgpu_cigar_last_ms(snapgpu_aligner_t *a, double *ms) {
     return SNAPGPU_OK;
 }
 
-// ------------------------------------------------- SAM text on the device (sam_format.hip)
-static const uint64_t kSamChunk = 16ull << 20;   // bytes per pinned staging chunk of the text download
-
-static hipError_t samGrow(snapgpu_aligner_t *a, SamState::Buf &b, uint64_t bytes) {
-    if (bytes <= b.cap) return hipSuccess;
-    devFree(a, b.p);
-    b.p = nullptr;
-    b.cap = 0;
-    const uint64_t want = bytes + bytes / 4 + 256;
-    const hipError_t e = hipMalloc(&b.p, want);
-    if (e == hipSuccess) b.cap = want;
-    return e;
-}
-
-// The small host-side inputs of the formatter, packed for one upload.
-struct SamHostIn {
-    uint64_t n = 0;
-    const uint64_t *offsets = nullptr;   // null: already on the device (resident batch)
-    const uint32_t *lengths = nullptr;
-    const char *ids = nullptr;
-    const uint64_t *idOffsets = nullptr;
-    const uint32_t *idLengths = nullptr;
-    const uint32_t *front = nullptr, *unclipped = nullptr;
-    const char *rg = nullptr;
-    // the device form (a resident batch's own state, no host batch): what is set here is already in
-    // device memory and is pointed at, not uploaded
-    const char *dIds = nullptr;            // with dIdOffsets / dIdLengths, when ids is null
-    const uint64_t *dIdOffsets = nullptr;
-    const uint32_t *dIdLengths = nullptr;
-    const uint32_t *dFront = nullptr, *dUnclipped = nullptr;
-    bool device = false;                   // lengths is null: the bound comes from the totals below
-    uint64_t idTotal = 0, baseTotal = 0;   // bytes of all ids (the caller's, if it passed ids), of all unclipped reads
-};
-
-// Upload H's arrays, the piece names and the read group into S.aux (unless S still holds them:
-// skip) and point A at them; textBound = a bound on the bytes of text from the host's side.
-static int samPrepare(snapgpu_aligner_t *a, SamState &S, const SamHostIn &H, bool skip, samline::Args &A) {
-    const uint64_t n = H.n;
-    const snapgpu::Genome &g = *a->idx->genome;
-    std::vector<uint32_t> nameOff;
-    std::string names;
-    snapgpu::samPieceNames(g, nameOff, names);
-    std::vector<uint32_t> sortBase;
-    std::vector<uint8_t> sortNone;
-    snapgpu::samSortBases(g, sortBase, sortNone);
-    const uint32_t rgLen = H.rg ? (uint32_t)strlen(H.rg) : 0u;
-    uint64_t idBytes = 0, bound = 0;
-    uint32_t maxName = 1;
-    for (size_t p = 0; p + 1 < nameOff.size(); p++) maxName = std::max(maxName, nameOff[p + 1] - nameOff[p]);
-    // per line: flags, POS, MAPQ, tabs, mate fields, tags and NM (< 64), RNAME, two soft clips and
-    // SNAPGPU_CIGAR_MAX_OPS ops of at most 11 bytes each
-    const uint64_t perLine = 64 + maxName + (H.rg ? 6 + rgLen : 0) + 22 + 11ull * SNAPGPU_CIGAR_MAX_OPS;
-    if (H.ids)
-        for (uint64_t i = 0; i < n; i++) idBytes = std::max<uint64_t>(idBytes, H.idOffsets[i] + H.idLengths[i]);
-    if (H.device) {
-        bound = H.idTotal + 2 * H.baseTotal + n * perLine;
-    } else {
-        for (uint64_t i = 0; i < n; i++) {
-            const uint32_t len = H.unclipped ? H.unclipped[i] : H.lengths[i];
-            bound += H.idLengths[i] + 2ull * std::min(len, samline::kMaxSeq) + perLine;
-        }
-    }
-    S.textBound = bound;
-    auto al16 = [](uint64_t x) { return (x + 15) & ~15ull; };
-    const uint64_t nIds = H.ids ? n : 0;   // the id arrays ride in aux only when they come from the host
-    const uint64_t oIdOff = 0, oIdLen = al16(oIdOff + nIds * 8), oFront = al16(oIdLen + nIds * 4),
-                   oFull = al16(oFront + (H.unclipped ? n * 4 : 0)), oOff = al16(oFull + (H.unclipped ? n * 4 : 0)),
-                   oLen = al16(oOff + (H.offsets ? n * 8 : 0)), oNameOff = al16(oLen + (H.offsets ? n * 4 : 0)),
-                   oNames = al16(oNameOff + nameOff.size() * 4), oSortBase = al16(oNames + names.size()),
-                   oSortNone = al16(oSortBase + sortBase.size() * 4), oRg = al16(oSortNone + sortNone.size()),
-                   oIds = al16(oRg + rgLen), bytes = al16(oIds + idBytes) + 16;
-    if (!skip) {
-        if (S.ran && S.ev[1]) HIPCHK(hipEventSynchronize(S.ev[1]));   // an earlier call's kernels may still read aux
-        HIPCHK(samGrow(a, S.aux, bytes));
-        S.hAux.assign(bytes, 0);
-        char *h = S.hAux.data();
-        if (n) {
-            if (nIds) { memcpy(h + oIdOff, H.idOffsets, n * 8); memcpy(h + oIdLen, H.idLengths, n * 4); }
-            if (H.unclipped) { memcpy(h + oFront, H.front, n * 4); memcpy(h + oFull, H.unclipped, n * 4); }
-            if (H.offsets) { memcpy(h + oOff, H.offsets, n * 8); memcpy(h + oLen, H.lengths, n * 4); }
-        }
-        memcpy(h + oNameOff, nameOff.data(), nameOff.size() * 4);
-        memcpy(h + oNames, names.data(), names.size());
-        memcpy(h + oSortBase, sortBase.data(), sortBase.size() * 4);
-        memcpy(h + oSortNone, sortNone.data(), sortNone.size());
-        if (rgLen) memcpy(h + oRg, H.rg, rgLen);
-        if (idBytes) memcpy(h + oIds, H.ids, idBytes);
-        // on the otherwise idle copy stream, and waited for: the host copy may go, and the side
-        // stream (which may still be in the CIGAR kernel) is not waited for
-        HIPCHK(hipMemcpyAsync(S.aux.p, h, bytes, hipMemcpyHostToDevice, a->copyStream));
-        HIPCHK(hipStreamSynchronize(a->copyStream));
-    }
-    const char *d = (const char *)S.aux.p;
-    A.idOffsets = H.ids ? (const uint64_t *)(d + oIdOff) : H.dIdOffsets;
-    A.idLengths = H.ids ? (const uint32_t *)(d + oIdLen) : H.dIdLengths;
-    A.front = H.unclipped ? (const uint32_t *)(d + oFront) : H.dFront;
-    A.unclipped = H.unclipped ? (const uint32_t *)(d + oFull) : H.dUnclipped;
-    if (H.offsets) { A.offsets = (const uint64_t *)(d + oOff); A.lengths = (const uint32_t *)(d + oLen); }
-    A.pieceOffsets = a->dPieces;
-    A.pieceNameOff = (const uint32_t *)(d + oNameOff);
-    A.pieceNames = d + oNames;
-    S.sortArgs = samline::SortArgs{(const uint32_t *)(d + oSortBase), (const uint8_t *)(d + oSortNone)};
-    A.nPieces = (int32_t)g.pieceOffsets.size();
-    A.rg = H.rg ? d + oRg : nullptr;
-    A.rgLen = rgLen;
-    A.ids = H.ids ? d + oIds : H.dIds;
-    return SNAPGPU_OK;
-}
-
-// Length pass, scan, write pass and check of n records on the side stream, into S's buffers;
-// sorted: in the stable order of the records' coordinate-sort keys (S.order keeps that order).
-static int samLaunch(snapgpu_aligner_t *a, SamState &S, const samline::Args &A, uint64_t n, bool sorted) {
-    for (auto &e : S.ev)
-        if (!e) HIPCHK(hipEventCreate(&e));
-    S.n = n;
-    S.ran = true;
-    S.sorted = sorted;
-    a->samLast = &S;
-    if (n == 0) return SNAPGPU_OK;
-    if (n > 0xffffffffull) { snapgpu::setError("batch too large"); return SNAPGPU_EINVAL; }
-    HIPCHK(samGrow(a, S.len, n * 4));
-    HIPCHK(samGrow(a, S.scans, n * sizeof(samline::Scans)));
-    HIPCHK(samGrow(a, S.start, (n + 1) * 8));
-    HIPCHK(samGrow(a, S.sums, samgpu::scanTiles(n) * 8));
-    HIPCHK(samGrow(a, S.bad, 16));
-    HIPCHK(samGrow(a, S.text, S.textBound + 16));
-    const samgpu::Buffers B{(uint32_t *)S.len.p, (samline::Scans *)S.scans.p, (uint64_t *)S.start.p, (uint64_t *)S.sums.p, (char *)S.text.p,
-                            S.textBound, (uint32_t *)S.bad.p, {S.ev[2], S.ev[3]}};
-    samgpu::SortBuffers SB{};
-    if (sorted) {
-        HIPCHK(samgpu::sortTempBytes(n, a->sideStream, &SB.tempBytes));
-        for (SamState::Buf *b : {&S.key, &S.keySorted, &S.iota, &S.order, &S.slotLen}) HIPCHK(samGrow(a, *b, n * 4));
-        HIPCHK(samGrow(a, S.sortTemp, SB.tempBytes));
-        SB.key = (uint32_t *)S.key.p; SB.keySorted = (uint32_t *)S.keySorted.p;
-        SB.iota = (uint32_t *)S.iota.p; SB.order = (uint32_t *)S.order.p;
-        SB.slotLen = (uint32_t *)S.slotLen.p;
-        SB.temp = S.sortTemp.p;
-        SB.keys = S.sortArgs;
-        SB.done = S.ev[4];
-    }
-    HIPCHK(hipEventRecord(S.ev[0], a->sideStream));
-    HIPCHK(samgpu::launch(A, n, B, a->sideStream, sorted ? &SB : nullptr));
-    HIPCHK(hipEventRecord(S.ev[1], a->sideStream));
-    return SNAPGPU_OK;
-}
-
-// `total` bytes at device address `text` to the caller's (pageable) buffer, in chunks through two
-// pinned staging buffers: chunk k + 1 crosses PCIe while host threads copy chunk k out.
-static int textDownload(snapgpu_aligner_t *a, const char *text, uint64_t total, char *out) {
-    for (int k = 0; k < 2; k++) {
-        if (!a->samPin[k]) HIPCHK(hipHostMalloc(&a->samPin[k], kSamChunk, hipHostMallocDefault));
-        if (!a->samPinDone[k]) HIPCHK(hipEventCreateWithFlags(&a->samPinDone[k], hipEventDisableTiming));
-    }
-    const uint64_t nChunks = (total + kSamChunk - 1) / kSamChunk;
-    auto issue = [&](uint64_t k) -> hipError_t {
-        const uint64_t b = k * kSamChunk, m = std::min(kSamChunk, total - b);
-        hipError_t e = hipMemcpyAsync(a->samPin[k & 1], text + b, m, hipMemcpyDeviceToHost, a->sideStream);
-        return e != hipSuccess ? e : hipEventRecord(a->samPinDone[k & 1], a->sideStream);
-    };
-    const unsigned nt = snapgpu::hostThreads(16);
-    HIPCHK(issue(0));
-    for (uint64_t k = 0; k < nChunks; k++) {
-        if (k + 1 < nChunks) HIPCHK(issue(k + 1));
-        if (int rc = waitEvent(a, a->samPinDone[k & 1])) return rc;
-        const uint64_t b = k * kSamChunk, m = std::min(kSamChunk, total - b);
-        const char *src = (const char *)a->samPin[k & 1];
-        const unsigned t = m < (1u << 20) ? 1u : nt;
-        std::vector<std::thread> th;
-        for (unsigned j = 1; j < t; j++)
-            th.emplace_back([=] { memcpy(out + b + m * j / t, src + m * j / t, m * (j + 1) / t - m * j / t); });
-        memcpy(out + b, src, m / t);
-        for (auto &x : th) x.join();
-    }
-    return SNAPGPU_OK;
-}
-
-// Wait for S's kernels, check them, and copy the text to the caller's buffer (textDownload).
-static int samDownload(snapgpu_aligner_t *a, SamState &S, char *out, uint64_t cap, uint64_t *used) {
-    *used = 0;
-    S.downloadMs = 0;
-    if (S.n == 0) return SNAPGPU_OK;
-    if (int rc = waitEvent(a, S.ev[1])) return rc;
-    const auto t0 = std::chrono::steady_clock::now();
-    uint64_t total = 0;
-    uint32_t bad = 0;
-    HIPCHK(hipMemcpy(&total, (const uint64_t *)S.start.p + S.n, 8, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(&bad, S.bad.p, 4, hipMemcpyDeviceToHost));
-    if (bad || total > S.textBound) {
-        char msg[160];
-        snprintf(msg, sizeof msg, "sam: %u of %llu lines do not end where the scan placed them (text %llu bytes, bound %llu)",
-                 bad, (unsigned long long)S.n, (unsigned long long)total, (unsigned long long)S.textBound);
-        snapgpu::setError(msg);
-        return SNAPGPU_EDEVICE;
-    }
-    *used = total;
-    if (total > cap || !out) { snapgpu::setError("sam_download: output buffer too small"); return SNAPGPU_EINVAL; }
-    if (int rc = textDownload(a, (const char *)S.text.p, total, out)) return rc;
-    S.downloadMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    return SNAPGPU_OK;
-}
-
-// The device BAM encoder's passes over n records on the side stream, into S's buffers (samLaunch's
-// counterpart; S.textBound is samPrepare's bound on the SAM text, which exceeds the records' bytes:
-// per record the id, 1.5 bytes per base and at most 36 + 1 + 4 * 66 + 4 + 15 more, plus the read group).
-static int bamLaunch(snapgpu_aligner_t *a, BamState &S, const samline::Args &A, uint64_t n, bool sorted, int32_t nmCarryIn) {
-    for (auto &e : S.ev)
-        if (!e) HIPCHK(hipEventCreate(&e));
-    S.n = n;
-    S.ran = true;
-    S.sorted = sorted;
-    S.carryIn = nmCarryIn;
-    a->bamLast = &S;
-    if (n == 0) return SNAPGPU_OK;
-    if (n > 0xffffffffull) { snapgpu::setError("batch too large"); return SNAPGPU_EINVAL; }
-    HIPCHK(samGrow(a, S.len, n * 4));
-    HIPCHK(samGrow(a, S.nm, n * 4));
-    HIPCHK(samGrow(a, S.nmTiles, samgpu::scanTiles(n) * 4));
-    HIPCHK(samGrow(a, S.start, (n + 1) * 8));
-    HIPCHK(samGrow(a, S.sums, samgpu::scanTiles(n) * 8));
-    HIPCHK(samGrow(a, S.bad, 16));
-    HIPCHK(samGrow(a, S.text, S.textBound + 16));
-    const bamgpu::Buffers B{(uint32_t *)S.len.p, (int32_t *)S.nm.p, (int32_t *)S.nmTiles.p, (uint64_t *)S.start.p,
-                            (uint64_t *)S.sums.p, (char *)S.text.p, S.textBound, (uint32_t *)S.bad.p};
-    samgpu::SortBuffers SB{};
-    if (sorted) {
-        HIPCHK(samgpu::sortTempBytes(n, a->sideStream, &SB.tempBytes));
-        for (SamState::Buf *b : {&S.key, &S.keySorted, &S.iota, &S.order, &S.slotLen}) HIPCHK(samGrow(a, *b, n * 4));
-        HIPCHK(samGrow(a, S.sortTemp, SB.tempBytes));
-        SB.key = (uint32_t *)S.key.p; SB.keySorted = (uint32_t *)S.keySorted.p;
-        SB.iota = (uint32_t *)S.iota.p; SB.order = (uint32_t *)S.order.p;
-        SB.slotLen = (uint32_t *)S.slotLen.p;
-        SB.temp = S.sortTemp.p;
-    }
-    HIPCHK(hipEventRecord(S.ev[0], a->sideStream));
-    HIPCHK(bamgpu::launch(A, n, nmCarryIn, B, a->sideStream, sorted ? &SB : nullptr));
-    HIPCHK(hipEventRecord(S.ev[1], a->sideStream));
-    return SNAPGPU_OK;
-}
-
-// Wait for S's kernels, check them, and copy the records and the carry-out to the caller.
-static int bamDownload(snapgpu_aligner_t *a, BamState &S, char *out, uint64_t cap, uint64_t *used, int32_t *nmCarryOut) {
-    *used = 0;
-    S.downloadMs = 0;
-    if (nmCarryOut) *nmCarryOut = S.carryIn;
-    if (S.n == 0) return SNAPGPU_OK;
-    if (int rc = waitEvent(a, S.ev[1])) return rc;
-    const auto t0 = std::chrono::steady_clock::now();
-    uint64_t total = 0;
-    uint32_t bad = 0;
-    HIPCHK(hipMemcpy(&total, (const uint64_t *)S.start.p + S.n, 8, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(&bad, S.bad.p, 4, hipMemcpyDeviceToHost));
-    if (bad || total > S.textBound) {
-        char msg[160];
-        snprintf(msg, sizeof msg, "bam: %u of %llu records do not carry the size the scan gave them (output %llu bytes, bound %llu)",
-                 bad, (unsigned long long)S.n, (unsigned long long)total, (unsigned long long)S.textBound);
-        snapgpu::setError(msg);
-        return SNAPGPU_EDEVICE;
-    }
-    if (nmCarryOut) HIPCHK(hipMemcpy(nmCarryOut, (const int32_t *)S.nm.p + S.n - 1, 4, hipMemcpyDeviceToHost));
-    *used = total;
-    if (total > cap || !out) { snapgpu::setError("bam_download: output buffer too small"); return SNAPGPU_EINVAL; }
-    if (int rc = textDownload(a, (const char *)S.text.p, total, out)) return rc;
-    S.downloadMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    return SNAPGPU_OK;
-}
-
-// Wait for the mark passes of S and take their counts; SNAPGPU_EDEVICE unless they add up.
-static int dupResult(snapgpu_aligner_t *a, DupState &S, dupgpu::Result *r) {
-    if (int rc = waitEvent(a, S.ev[dupgpu::kPasses])) return rc;
-    HIPCHK(hipMemcpy(r, (const char *)S.work.p + S.L.res, sizeof *r, hipMemcpyDeviceToHost));
-    if (r->refused || r->mates || r->marked != r->expected) {
-        char msg[240];
-        snprintf(msg, sizeof msg, "dupmark: %u records are refused or out of (refID, pos) order, %u carry a mate (FLAG 0x1), "
-                                  "%llu records marked where the groups' sizes give %llu",
-                 r->refused, r->mates, r->marked, r->expected);
-        snapgpu::setError(msg);
-        return SNAPGPU_EDEVICE;
-    }
-    return SNAPGPU_OK;
-}
-
-// snapgpu_sam_resident and snapgpu_sam_resident_sorted; bam: snapgpu_bam_resident and
-// snapgpu_bam_resident_sorted, the same checks and ordering over the batch's BAM state
-static int samResident(snapgpu_aligner_t *a, snapgpu_device_reads_t *d, const snapgpu_reads_t *reads,
-                       const char *ids, const uint64_t *idOffsets, const uint32_t *idLengths,
-                       const char *readGroup, bool sorted, bool bam = false, int32_t nmCarryIn = 0) {
-    const std::string who = bam ? "bam_resident" : "sam_resident";
-    if (!a || !d) { snapgpu::setError(who + ": null argument"); return SNAPGPU_EINVAL; }
-    if (a->failed) { snapgpu::setError("aligner failed earlier (device timeout)"); return SNAPGPU_EDEVICE; }
-    if (d->owner != a) { snapgpu::setError(who + ": the resident batch belongs to another aligner"); return SNAPGPU_EINVAL; }
-    // reads == NULL: the batch's own resident ids and clip state (the device FASTQ parser's), nothing
-    // to compare the extents with
-    const bool devForm = !reads;
-    const uint64_t n = d->n;
-    if (devForm && !d->hasIds) {
-        snapgpu::setError(who + ": reads is NULL and the resident batch holds no ids or clip state of its own "
-                                "(only snapgpu_fastq_upload leaves them; pass the batch it was uploaded from)");
-        return SNAPGPU_EINVAL;
-    }
-    if (!devForm) {
-        uint64_t bytes = 0, hash = 0;
-        if (reads->n == d->n)
-            for (uint64_t i = 0; i < reads->n; i++) {
-                bytes = std::max<uint64_t>(bytes, reads->offsets[i] + reads->lengths[i]);
-                hash = extentMix(hash, reads->offsets[i], reads->lengths[i]);
-            }
-        if (reads->n != d->n || bytes != d->bytes || hash != d->extentHash) {
-            snapgpu::setError(who + ": the reads batch does not match the resident batch (n, offsets or lengths differ)");
-            return SNAPGPU_EINVAL;
-        }
-    }
-    const bool ownIds = !ids;
-    if (ownIds && !devForm) { ids = reads->ids; idOffsets = reads->idOffsets; idLengths = reads->idLengths; }
-    if (!(ownIds && devForm) && (!ids || !idOffsets || !idLengths)) {
-        snapgpu::setError(who + ": no read ids (pass ids, or use a batch that carries them)");
-        return SNAPGPU_EINVAL;
-    }
-    const uint32_t *front = nullptr, *unclipped = nullptr;
-    if (devForm) {
-        // the host loops' verdicts from the maxima the upload fetched, with their messages
-        const uint32_t one[1] = {ownIds ? d->maxIdLen : 0u};
-        if (bam)
-            if (int rc = ownIds ? snapgpu::bamCheckIds(one, 1) : snapgpu::bamCheckIds(idLengths, n)) return rc;
-        if (d->maxUnclipped > 1024) {
-            snapgpu::setError("sam_format: nOps > SNAPGPU_CIGAR_MAX_OPS, read longer than 1024 bases or bad clip arrays");
-            return SNAPGPU_EINVAL;
-        }
-    } else {
-        if (bam)
-            if (int rc = snapgpu::bamCheckIds(idLengths, n)) return rc;
-        if (int rc = snapgpu::samCheckClips(reads, nullptr, &front, &unclipped)) return rc;
-    }
-    if (!d->dCigEd) {
-        snapgpu::setError(who + ": no snapgpu_cigar_resident before snapgpu_" + who);
-        return SNAPGPU_EINVAL;
-    }
-    HIPCHK(hipSetDevice(a->device));
-    SamState &S = bam ? d->bam : d->sam;
-    hipStream_t st = a->sideStream;
-    // snapgpu_reads_upload copied bases and qualities up to the largest clipped end: where the
-    // unclipped extents (SEQ / QUAL) pass it, the formatter reads a copy that holds them all
-    uint64_t need = d->bytes;
-    if (devForm && d->dTail) need = d->total;   // the last read's unclipped end
-    if (unclipped)
-        for (uint64_t i = 0; i < reads->n; i++)
-            need = std::max<uint64_t>(need, reads->offsets[i] - front[i] + unclipped[i]);
-    if (need > d->bytes && S.fullBytes != need) {
-        if (S.ran && S.ev[1]) HIPCHK(hipEventSynchronize(S.ev[1]));
-        const uint64_t tail = need - d->bytes;
-        if (!devForm) {
-            S.hAux.assign(2 * tail, 0);
-            memcpy(S.hAux.data(), reads->bases + d->bytes, tail);
-            memcpy(S.hAux.data() + tail, reads->quals + d->bytes, tail);
-        }
-        for (int q = 0; q < 2; q++) {
-            SamState::Buf &b = q ? S.quals : S.bases;
-            HIPCHK(samGrow(a, b, need + 64));
-            HIPCHK(hipMemsetAsync((char *)b.p + need, 0, 64, a->copyStream));
-            HIPCHK(hipMemcpyAsync(b.p, q ? d->dQuals : d->dBases, d->bytes, hipMemcpyDeviceToDevice, a->copyStream));
-            if (devForm)   // the resident tail: no host bytes
-                HIPCHK(hipMemcpyAsync((char *)b.p + d->bytes, d->dTail + q * tail, tail, hipMemcpyDeviceToDevice, a->copyStream));
-            else
-                HIPCHK(hipMemcpyAsync((char *)b.p + d->bytes, S.hAux.data() + q * tail, tail, hipMemcpyHostToDevice, a->copyStream));
-        }
-        HIPCHK(hipStreamSynchronize(a->copyStream));
-        S.fullBytes = need;
-    }
-    samline::Args A;
-    memset(&A, 0, sizeof(A));
-    const bool full = need > d->bytes;
-    A.bases = full ? (const char *)S.bases.p : d->dBases;
-    A.quals = full ? (const char *)S.quals.p : d->dQuals;
-    A.offsets = d->dOffsets;
-    A.lengths = d->dLengths;
-    A.res = d->dOut;
-    A.ed = d->dCigEd;
-    A.nOps = d->dCigN;
-    A.ops = d->dCigOps;
-    SamHostIn H;
-    H.n = n;
-    H.ids = ids; H.idOffsets = idOffsets; H.idLengths = idLengths;
-    H.rg = readGroup;
-    if (devForm) {
-        // aux carries only the piece names, the sort bases and the read group (and a caller's ids)
-        H.device = true;
-        H.baseTotal = d->total;
-        H.idTotal = d->idTotal;
-        if (ownIds) {
-            H.dIds = d->dIds; H.dIdOffsets = d->dIdStart; H.dIdLengths = d->dIdLen;
-        } else {
-            H.idTotal = 0;
-            for (uint64_t i = 0; i < n; i++) H.idTotal += idLengths[i];
-        }
-        if (d->clipping) { H.dFront = d->dFront; H.dUnclipped = d->dUnclipped; }
-    } else {
-        H.lengths = reads->lengths;   // offsets and lengths are resident: the lengths only bound the text
-        H.front = front; H.unclipped = unclipped;
-    }
-    // the batch's own ids do not change: their upload (or, in the device form, the upload without them)
-    // is kept for the next call of the same form with the same read group
-    const bool skip = ownIds && S.idsCached && S.cachedDevForm == devForm && S.cachedHasRg == (readGroup != nullptr) &&
-                      (!readGroup || S.cachedRg == readGroup);
-    if (int rc = samPrepare(a, S, H, skip, A)) return rc;
-    S.idsCached = ownIds;
-    S.cachedDevForm = devForm;
-    S.cachedHasRg = readGroup != nullptr;
-    S.cachedRg = readGroup ? readGroup : "";
-    // the records may come from pass sets on both lanes; the CIGAR kernel is ahead on this stream
-    for (auto &L : a->lane) {
-        HIPCHK(hipEventRecord(L.done, L.stream));
-        HIPCHK(hipStreamWaitEvent(st, L.done, 0));
-    }
-    // the records change: a compressed stream of the earlier ones, its index and their marking are stale
-    if (bam) d->bgzf.ran = d->bai.ran = d->dup.ran = false;
-    if (int rc = bam ? bamLaunch(a, d->bam, A, n, sorted, nmCarryIn) : samLaunch(a, S, A, n, sorted)) return rc;
-    // the next pass set over these reads rewrites the records: it waits for the SAM / BAM kernels
-    HIPCHK(hipEventRecord(a->residentSideDone, st));
-    a->residentSidePending = true;
-    return SNAPGPU_OK;
-}
-
-int snapgpu_sam_resident(snapgpu_aligner_t *a, snapgpu_device_reads_t *d, const snapgpu_reads_t *reads,
-                         const char *ids, const uint64_t *idOffsets, const uint32_t *idLengths,
-                         const char *readGroup) {
-    return samResident(a, d, reads, ids, idOffsets, idLengths, readGroup, false);
-}
-
-int snapgpu_sam_resident_sorted(snapgpu_aligner_t *a, snapgpu_device_reads_t *d, const snapgpu_reads_t *reads,
-                                const char *ids, const uint64_t *idOffsets, const uint32_t *idLengths,
-                                const char *readGroup) {
-    return samResident(a, d, reads, ids, idOffsets, idLengths, readGroup, true);
-}
-
-// Wait for S's kernels and copy the output order of its last (sorted) call to the host.
-static int samOrderDownload(snapgpu_aligner_t *a, SamState &S, uint32_t *order) {
-    if (S.n == 0) return SNAPGPU_OK;
-    if (int rc = waitEvent(a, S.ev[1])) return rc;
-    HIPCHK(hipMemcpy(order, S.order.p, S.n * 4, hipMemcpyDeviceToHost));
-    return SNAPGPU_OK;
-}
-
-int snapgpu_sam_order_download(snapgpu_aligner_t *a, snapgpu_device_reads_t *d, uint32_t *order) {
-    if (!a || !d) { snapgpu::setError("sam_order_download: null argument"); return SNAPGPU_EINVAL; }
-    if (a->failed) { snapgpu::setError("aligner failed earlier (device timeout)"); return SNAPGPU_EDEVICE; }
-    if (!d->sam.ran || !d->sam.sorted) {
-        snapgpu::setError("sam_order_download: the batch's last SAM call was not snapgpu_sam_resident_sorted (or there was none)");
-        return SNAPGPU_EINVAL;
-    }
-    if (!order && d->sam.n) { snapgpu::setError("sam_order_download: null argument"); return SNAPGPU_EINVAL; }
-    HIPCHK(hipSetDevice(a->device));
-    return samOrderDownload(a, d->sam, order);
-}
-
-int snapgpu_sam_download(snapgpu_aligner_t *a, snapgpu_device_reads_t *d, char *out, uint64_t cap, uint64_t *used) {
-    if (!a || !d || !used) { snapgpu::setError("sam_download: null argument"); return SNAPGPU_EINVAL; }
-    if (a->failed) { snapgpu::setError("aligner failed earlier (device timeout)"); return SNAPGPU_EDEVICE; }
-    if (!d->sam.ran) { snapgpu::setError("sam_download: no snapgpu_sam_resident before snapgpu_sam_download"); return SNAPGPU_EINVAL; }
-    HIPCHK(hipSetDevice(a->device));
-    return samDownload(a, d->sam, out, cap, used);
-}
-
-// snapgpu_sam_format_gpu and snapgpu_sam_format_gpu_sorted (order: the output order, or null)
-static int samFormatBatch(snapgpu_aligner_t *a, const snapgpu_reads_t *reads, const char *ids,
-                          const uint64_t *idOffsets, const uint32_t *idLengths, const snapgpu_result_t *results,
-                          const int32_t *editDistance, const uint32_t *nOps, const uint32_t *ops,
-                          const char *readGroup, const uint32_t *frontClipped, const uint32_t *unclippedLength,
-                          char *out, uint64_t cap, uint64_t *used, bool sorted, uint32_t *order, bool bam = false,
-                          int32_t nmCarryIn = 0, int32_t *nmCarryOut = nullptr) {
-    if (!a || !reads || !ids || !idOffsets || !idLengths || !results || !editDistance || !nOps || !ops || !used) {
-        snapgpu::setError(bam ? "bam_format: null argument" : "sam_format: null argument");
-        return SNAPGPU_EINVAL;
-    }
-    if (a->failed) { snapgpu::setError("aligner failed earlier (device timeout)"); return SNAPGPU_EDEVICE; }
-    if (int rc = snapgpu::samCheckClips(reads, nOps, &frontClipped, &unclippedLength)) return rc;
-    if (bam)
-        if (int rc = snapgpu::bamCheckIds(idLengths, reads->n)) return rc;
-    HIPCHK(hipSetDevice(a->device));
-    SamState &S = bam ? a->bamBatch : a->samBatch;
-    hipStream_t st = a->sideStream;
-    const uint64_t n = reads->n;
-    if (S.ran && S.ev[1]) HIPCHK(hipEventSynchronize(S.ev[1]));
-    uint64_t need = 0;
-    for (uint64_t i = 0; i < n; i++)
-        need = std::max<uint64_t>(need, unclippedLength ? reads->offsets[i] - frontClipped[i] + unclippedLength[i]
-                                                        : reads->offsets[i] + reads->lengths[i]);
-    samline::Args A;
-    memset(&A, 0, sizeof(A));
-    struct Up { SamState::Buf *b; const void *src; uint64_t bytes; };
-    const Up ups[] = {{&S.bases, reads->bases, need}, {&S.quals, reads->quals, need},
-                      {&S.res, results, n * sizeof(snapgpu_result_t)}, {&S.ed, editDistance, n * 4},
-                      {&S.nOps, nOps, n * 4}, {&S.ops, ops, n * SNAPGPU_CIGAR_MAX_OPS * 4}};
-    for (const Up &u : ups) {
-        HIPCHK(samGrow(a, *u.b, u.bytes + 64));
-        HIPCHK(hipMemsetAsync((char *)u.b->p + u.bytes, 0, 64, st));
-        if (u.bytes) HIPCHK(hipMemcpyAsync(u.b->p, u.src, u.bytes, hipMemcpyHostToDevice, st));
-    }
-    A.bases = (const char *)S.bases.p;
-    A.quals = (const char *)S.quals.p;
-    A.res = (const snapgpu_result_t *)S.res.p;
-    A.ed = (const int32_t *)S.ed.p;
-    A.nOps = (const uint32_t *)S.nOps.p;
-    A.ops = (const uint32_t *)S.ops.p;
-    SamHostIn H;
-    H.n = n; H.offsets = reads->offsets; H.lengths = reads->lengths;
-    H.ids = ids; H.idOffsets = idOffsets; H.idLengths = idLengths;
-    H.front = frontClipped; H.unclipped = unclippedLength; H.rg = readGroup;
-    if (int rc = samPrepare(a, S, H, false, A)) return rc;
-    if (int rc = bam ? bamLaunch(a, a->bamBatch, A, n, sorted, nmCarryIn) : samLaunch(a, S, A, n, sorted)) return rc;
-    if (int rc = bam ? bamDownload(a, a->bamBatch, out, cap, used, nmCarryOut) : samDownload(a, S, out, cap, used)) return rc;
-    return sorted && order ? samOrderDownload(a, S, order) : SNAPGPU_OK;
-}
-
-int snapgpu_sam_format_gpu(snapgpu_aligner_t *a, const snapgpu_reads_t *reads, const char *ids,
-                           const uint64_t *idOffsets, const uint32_t *idLengths, const snapgpu_result_t *results,
-                           const int32_t *editDistance, const uint32_t *nOps, const uint32_t *ops,
-                           const char *readGroup, const uint32_t *frontClipped, const uint32_t *unclippedLength,
-                           char *out, uint64_t cap, uint64_t *used) {
-    return samFormatBatch(a, reads, ids, idOffsets, idLengths, results, editDistance, nOps, ops, readGroup, frontClipped,
-                          unclippedLength, out, cap, used, false, nullptr);
-}
-
-int snapgpu_sam_format_gpu_sorted(snapgpu_aligner_t *a, const snapgpu_reads_t *reads, const char *ids,
-                                  const uint64_t *idOffsets, const uint32_t *idLengths, const snapgpu_result_t *results,
-                                  const int32_t *editDistance, const uint32_t *nOps, const uint32_t *ops,
-                                  const char *readGroup, const uint32_t *frontClipped, const uint32_t *unclippedLength,
-                                  char *out, uint64_t cap, uint64_t *used, uint32_t *order) {
-    return samFormatBatch(a, reads, ids, idOffsets, idLengths, results, editDistance, nOps, ops, readGroup, frontClipped,
-                          unclippedLength, out, cap, used, true, order);
-}
-
-int snapgpu_bam_resident(snapgpu_aligner_t *a, snapgpu_device_reads_t *d, const snapgpu_reads_t *reads,
-                         const char *ids, const uint64_t *idOffsets, const uint32_t *idLengths,
-                         const char *readGroup, int32_t nmCarryIn) {
-    return samResident(a, d, reads, ids, idOffsets, idLengths, readGroup, false, true, nmCarryIn);
-}
-
-int snapgpu_bam_resident_sorted(snapgpu_aligner_t *a, snapgpu_device_reads_t *d, const snapgpu_reads_t *reads,
-                                const char *ids, const uint64_t *idOffsets, const uint32_t *idLengths,
-                                const char *readGroup, int32_t nmCarryIn) {
-    return samResident(a, d, reads, ids, idOffsets, idLengths, readGroup, true, true, nmCarryIn);
-}
-
-int snapgpu_bam_download(snapgpu_aligner_t *a, snapgpu_device_reads_t *d, char *out, uint64_t cap, uint64_t *used,
-                         int32_t *nmCarryOut) {
-    if (!a || !d || !used) { snapgpu::setError("bam_download: null argument"); return SNAPGPU_EINVAL; }
-    if (a->failed) { snapgpu::setError("aligner failed earlier (device timeout)"); return SNAPGPU_EDEVICE; }
-    if (!d->bam.ran) { snapgpu::setError("bam_download: no snapgpu_bam_resident before snapgpu_bam_download"); return SNAPGPU_EINVAL; }
-    HIPCHK(hipSetDevice(a->device));
-    if (d->dup.ran) {   // the records are the marked ones: the mark passes have to be through, and sound
-        dupgpu::Result r{};
-        if (int rc = dupResult(a, d->dup, &r)) { *used = 0; return rc; }
-    }
-    return bamDownload(a, d->bam, out, cap, used, nmCarryOut);
-}
-
-int snapgpu_bam_order_download(snapgpu_aligner_t *a, snapgpu_device_reads_t *d, uint32_t *order) {
-    if (!a || !d) { snapgpu::setError("bam_order_download: null argument"); return SNAPGPU_EINVAL; }
-    if (a->failed) { snapgpu::setError("aligner failed earlier (device timeout)"); return SNAPGPU_EDEVICE; }
-    if (!d->bam.ran || !d->bam.sorted) {
-        snapgpu::setError("bam_order_download: the batch's last BAM call was not snapgpu_bam_resident_sorted (or there was none)");
-        return SNAPGPU_EINVAL;
-    }
-    if (!order && d->bam.n) { snapgpu::setError("bam_order_download: null argument"); return SNAPGPU_EINVAL; }
-    HIPCHK(hipSetDevice(a->device));
-    return samOrderDownload(a, d->bam, order);
-}
-
-int snapgpu_bam_format_gpu(snapgpu_aligner_t *a, const snapgpu_reads_t *reads, const char *ids,
-                           const uint64_t *idOffsets, const uint32_t *idLengths, const snapgpu_result_t *results,
-                           const int32_t *editDistance, const uint32_t *nOps, const uint32_t *ops,
-                           const char *readGroup, const uint32_t *frontClipped, const uint32_t *unclippedLength,
-                           int32_t nmCarryIn, int32_t *nmCarryOut, char *out, uint64_t cap, uint64_t *used, int sorted,
-                           uint32_t *order) {
-    return samFormatBatch(a, reads, ids, idOffsets, idLengths, results, editDistance, nOps, ops, readGroup, frontClipped,
-                          unclippedLength, out, cap, used, sorted != 0, order, true, nmCarryIn, nmCarryOut);
-}
-
-int snapgpu_bam_last_ms(snapgpu_aligner_t *a, double *kernelMs, double *downloadMs) {
-    if (!a || !kernelMs || !downloadMs) return SNAPGPU_EINVAL;
-    if (!a->bamLast) { snapgpu::setError("bam_last_ms: no device BAM call on this aligner"); return SNAPGPU_EINVAL; }
-    if (a->failed) { snapgpu::setError("aligner failed earlier (device timeout)"); return SNAPGPU_EDEVICE; }
-    HIPCHK(hipSetDevice(a->device));
-    BamState &S = *a->bamLast;
-    float f = 0;
-    if (S.n) {
-        HIPCHK(hipEventSynchronize(S.ev[1]));
-        HIPCHK(hipEventElapsedTime(&f, S.ev[0], S.ev[1]));
-    }
-    *kernelMs = f;
-    *downloadMs = S.downloadMs;
-    return SNAPGPU_OK;
-}
-
-// ------------------------------------------------- BGZF on the device (bgzf.hip)
-// The compressor's passes on the side stream over the bytes at `in`: their count is *nDev (the
-// resident records' total, written by the BAM passes ahead on that stream) or n, at most capBytes.
-static int bgzfLaunch(snapgpu_aligner_t *a, BgzfState &S, const char *in, const uint64_t *nDev, uint64_t n, uint64_t capBytes) {
-    for (auto &e : S.ev)
-        if (!e) HIPCHK(hipEventCreate(&e));
-    S.ran = true;
-    S.downloadMs = 0;
-    a->bgzfLast = &S;
-    S.maxBlocks = bgzfgpu::blocksOf(nDev ? capBytes : std::min(n, capBytes));
-    if (S.maxBlocks == 0) return SNAPGPU_OK;
-    if (S.maxBlocks > 0x7fffffffull) { snapgpu::setError("bgzf: input too large"); return SNAPGPU_EINVAL; }
-    if (!a->bgzfGrid) {
-        hipDeviceProp_t prop;
-        HIPCHK(hipGetDeviceProperties(&prop, a->device));
-        a->bgzfGrid = std::max(1, prop.multiProcessorCount);
-    }
-    const uint32_t grid = (uint32_t)std::min<uint64_t>(S.maxBlocks, (uint64_t)a->bgzfGrid);
-    HIPCHK(samGrow(a, S.slots, S.maxBlocks * bgzfblock::kSlot));
-    HIPCHK(samGrow(a, S.packed, S.maxBlocks * bgzfblock::kSlot));
-    HIPCHK(samGrow(a, S.sizes, S.maxBlocks * 4));
-    HIPCHK(samGrow(a, S.offs, (S.maxBlocks + 1) * 8));
-    HIPCHK(samGrow(a, S.tokens, (uint64_t)grid * bgzfblock::kBlockIn * 4));
-    HIPCHK(samGrow(a, S.res, sizeof(bgzfgpu::Result)));
-    const bgzfgpu::Buffers B{(uint8_t *)S.slots.p, (uint32_t *)S.sizes.p, (uint64_t *)S.offs.p, (uint32_t *)S.tokens.p,
-                             (uint8_t *)S.packed.p, (bgzfgpu::Result *)S.res.p, grid};
-    HIPCHK(hipEventRecord(S.ev[0], a->sideStream));
-    HIPCHK(bgzfgpu::launch((const uint8_t *)in, nDev, n, capBytes, B, a->sideStream, S.ev[1], S.ev[2]));
-    HIPCHK(hipEventRecord(S.ev[3], a->sideStream));
-    return SNAPGPU_OK;
-}
-
-// Wait for S's kernels, check them, and copy the packed members (and the EOF block) to the caller.
-static int bgzfDownload(snapgpu_aligner_t *a, BgzfState &S, int eof, char *out, uint64_t cap, uint64_t *used) {
-    static const unsigned char kEof[28] = {31, 139, 8, 4, 0, 0, 0, 0, 0, 255, 6, 0, 66, 67, 2, 0, 27, 0,
-                                           3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    *used = 0;
-    S.downloadMs = 0;
-    uint64_t total = 0;
-    const auto t0 = std::chrono::steady_clock::now();
-    if (S.maxBlocks) {
-        if (int rc = waitEvent(a, S.ev[3])) return rc;
-        bgzfgpu::Result r{};
-        HIPCHK(hipMemcpy(&r, S.res.p, sizeof r, hipMemcpyDeviceToHost));
-        if (r.bad || r.nBlocks > S.maxBlocks || r.total > S.maxBlocks * bgzfblock::kSlot) {
-            char msg[160];
-            snprintf(msg, sizeof msg, "bgzf: %u of %u members are not what the size array says (stream %llu bytes, %llu slots)",
-                     r.bad, r.nBlocks, (unsigned long long)r.total, (unsigned long long)S.maxBlocks);
-            snapgpu::setError(msg);
-            return SNAPGPU_EDEVICE;
-        }
-        total = r.total;
-    }
-    const uint64_t need = total + (eof ? 28 : 0);
-    *used = need;
-    if (need > cap || (!out && need)) { snapgpu::setError("bgzf_download: output buffer too small"); return SNAPGPU_EINVAL; }
-    if (total)
-        if (int rc = textDownload(a, (const char *)S.packed.p, total, out)) return rc;
-    if (eof) memcpy(out + total, kEof, 28);
-    S.downloadMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    return SNAPGPU_OK;
-}
-
-int snapgpu_bam_bgzf_resident(snapgpu_aligner_t *a, snapgpu_device_reads_t *d) {
-    if (!a || !d) { snapgpu::setError("bam_bgzf_resident: null argument"); return SNAPGPU_EINVAL; }
-    if (a->failed) { snapgpu::setError("aligner failed earlier (device timeout)"); return SNAPGPU_EDEVICE; }
-    if (d->owner != a) { snapgpu::setError("bam_bgzf_resident: the resident batch belongs to another aligner"); return SNAPGPU_EINVAL; }
-    if (!d->bam.ran) {
-        snapgpu::setError("bam_bgzf_resident: no snapgpu_bam_resident before snapgpu_bam_bgzf_resident");
-        return SNAPGPU_EINVAL;
-    }
-    HIPCHK(hipSetDevice(a->device));
-    // the records and their total are written by the BAM passes ahead on the side stream; the next
-    // snapgpu_bam_resident rewrites them on that stream, after these passes
-    const BamState &R = d->bam;
-    d->bai.ran = false;   // the member offsets change: an index over the earlier ones is stale
-    if (R.n == 0) return bgzfLaunch(a, d->bgzf, nullptr, nullptr, 0, 0);
-    return bgzfLaunch(a, d->bgzf, (const char *)R.text.p, (const uint64_t *)R.start.p + R.n, 0, R.textBound);
-}
-
-int snapgpu_bam_bgzf_download(snapgpu_aligner_t *a, snapgpu_device_reads_t *d, int eof, char *out, uint64_t cap,
-                              uint64_t *used) {
-    if (!a || !d || !used) { snapgpu::setError("bam_bgzf_download: null argument"); return SNAPGPU_EINVAL; }
-    if (a->failed) { snapgpu::setError("aligner failed earlier (device timeout)"); return SNAPGPU_EDEVICE; }
-    if (!d->bgzf.ran) {
-        snapgpu::setError("bam_bgzf_download: no snapgpu_bam_bgzf_resident since the batch's last snapgpu_bam_resident");
-        return SNAPGPU_EINVAL;
-    }
-    HIPCHK(hipSetDevice(a->device));
-    return bgzfDownload(a, d->bgzf, eof, out, cap, used);
-}
-
-int snapgpu_bgzf_compress_gpu(snapgpu_aligner_t *a, const char *in, uint64_t n, int eof, char *out, uint64_t cap,
-                              uint64_t *used) {
-    if (!a || (!in && n) || !used) { snapgpu::setError("bgzf_compress_gpu: null argument"); return SNAPGPU_EINVAL; }
-    if (a->failed) { snapgpu::setError("aligner failed earlier (device timeout)"); return SNAPGPU_EDEVICE; }
-    HIPCHK(hipSetDevice(a->device));
-    BgzfState &S = a->bgzfBatch;
-    if (S.ran && S.maxBlocks) HIPCHK(hipEventSynchronize(S.ev[3]));
-    if (n) {
-        HIPCHK(samGrow(a, S.in, n + 64));
-        HIPCHK(hipMemcpyAsync(S.in.p, in, n, hipMemcpyHostToDevice, a->sideStream));
-    }
-    if (int rc = bgzfLaunch(a, S, (const char *)S.in.p, nullptr, n, n)) return rc;
-    return bgzfDownload(a, S, eof, out, cap, used);
-}
-
-int snapgpu_bgzf_last_ms(snapgpu_aligner_t *a, double *kernelMs, double *downloadMs) {
-    if (!a || !kernelMs || !downloadMs) return SNAPGPU_EINVAL;
-    if (!a->bgzfLast) { snapgpu::setError("bgzf_last_ms: no device BGZF call on this aligner"); return SNAPGPU_EINVAL; }
-    if (a->failed) { snapgpu::setError("aligner failed earlier (device timeout)"); return SNAPGPU_EDEVICE; }
-    HIPCHK(hipSetDevice(a->device));
-    BgzfState &S = *a->bgzfLast;
-    float f = 0;
-    if (S.maxBlocks) {
-        HIPCHK(hipEventSynchronize(S.ev[3]));
-        HIPCHK(hipEventElapsedTime(&f, S.ev[0], S.ev[3]));
-    }
-    *kernelMs = f;
-    *downloadMs = S.downloadMs;
-    return SNAPGPU_OK;
-}
-
-// ------------------------------------------------- BAI on the device (bai.hip)
-// The index passes on the side stream over n records at text + start[i], members at coff.
-static int baiLaunch(snapgpu_aligner_t *a, BaiState &S, const char *text, const uint64_t *start, uint64_t n, uint64_t recordBytes,
-                     uint32_t nRef, const uint64_t *coff, uint64_t streamOffset) {
-    for (auto &e : S.ev)
-        if (!e) HIPCHK(hipEventCreate(&e));
-    if (n > 0xfffffffeull) { snapgpu::setError("bai: batch too large"); return SNAPGPU_EINVAL; }
-    // an earlier call's kernels may still use the buffers that grow
-    if (S.launched) HIPCHK(hipEventSynchronize(S.ev[baigpu::kPasses]));
-    S.ran = false;
-    uint64_t temp = 0;
-    HIPCHK(baigpu::tempBytes(n, a->sideStream, &temp));
-    S.L = baigpu::layout(n, nRef, temp);
-    S.outCap = (baiindex::sizeBound(n, nRef, recordBytes) + 15) & ~15ull;
-    HIPCHK(samGrow(a, S.work, S.L.bytes));
-    HIPCHK(samGrow(a, S.out, S.outCap));
-    S.n = n;
-    S.nRef = nRef;
-    S.downloadMs = 0;
-    a->baiLast = &S;
-    HIPCHK(baigpu::launch((const uint8_t *)text, start, n, nRef, coff, streamOffset, (char *)S.work.p, S.L, (uint8_t *)S.out.p,
-                          S.outCap, a->sideStream, S.ev));
-    S.ran = S.launched = true;
-    return SNAPGPU_OK;
-}
-
-// Wait for S's kernels, check them, and copy the index to the caller.
-static int baiDownload(snapgpu_aligner_t *a, BaiState &S, char *out, uint64_t cap, uint64_t *used) {
-    *used = 0;
-    S.downloadMs = 0;
-    if (int rc = waitEvent(a, S.ev[baigpu::kPasses])) return rc;
-    const auto t0 = std::chrono::steady_clock::now();
-    baigpu::Result r{};
-    HIPCHK(hipMemcpy(&r, (const char *)S.work.p + S.L.res, sizeof r, hipMemcpyDeviceToHost));
-    if (r.bad || r.total > S.outCap) {
-        char msg[200];
-        snprintf(msg, sizeof msg, "bai: %u records are refused or out of (refID, pos) order, or the counts do not add up "
-                                  "(index %llu bytes, bound %llu)", r.bad, (unsigned long long)r.total, (unsigned long long)S.outCap);
-        snapgpu::setError(msg);
-        return SNAPGPU_EDEVICE;
-    }
-    *used = r.total;
-    if (r.total > cap || !out) { snapgpu::setError("bai_download: output buffer too small"); return SNAPGPU_EINVAL; }
-    HIPCHK(hipMemcpy(out, S.out.p, r.total, hipMemcpyDeviceToHost));
-    S.downloadMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    return SNAPGPU_OK;
-}
-
-int snapgpu_bam_bai_resident(snapgpu_aligner_t *a, snapgpu_device_reads_t *d, uint64_t streamOffset) {
-    if (!a || !d) { snapgpu::setError("bam_bai_resident: null argument"); return SNAPGPU_EINVAL; }
-    if (a->failed) { snapgpu::setError("aligner failed earlier (device timeout)"); return SNAPGPU_EDEVICE; }
-    if (d->owner != a) { snapgpu::setError("bam_bai_resident: the resident batch belongs to another aligner"); return SNAPGPU_EINVAL; }
-    if (!d->bam.ran || !d->bam.sorted) {
-        snapgpu::setError("bam_bai_resident: the batch's last BAM call was not snapgpu_bam_resident_sorted (or there was none)");
-        return SNAPGPU_EINVAL;
-    }
-    if (!d->bgzf.ran) {
-        snapgpu::setError("bam_bai_resident: no snapgpu_bam_bgzf_resident since the batch's last snapgpu_bam_resident_sorted");
-        return SNAPGPU_EINVAL;
-    }
-    if (streamOffset >= baiindex::kStreamOffsetLimit) {
-        snapgpu::setError("bam_bai_resident: streamOffset does not fit a virtual offset");
-        return SNAPGPU_EINVAL;
-    }
-    HIPCHK(hipSetDevice(a->device));
-    const BamState &R = d->bam;
-    const uint32_t nRef = (uint32_t)a->idx->genome->pieceOffsets.size();
-    return baiLaunch(a, d->bai, (const char *)R.text.p, (const uint64_t *)R.start.p, R.n, R.n ? R.textBound : 0, nRef,
-                     (const uint64_t *)d->bgzf.offs.p, streamOffset);
-}
-
-int snapgpu_bam_bai_download(snapgpu_aligner_t *a, snapgpu_device_reads_t *d, char *out, uint64_t cap, uint64_t *used) {
-    if (!a || !d || !used) { snapgpu::setError("bam_bai_download: null argument"); return SNAPGPU_EINVAL; }
-    if (a->failed) { snapgpu::setError("aligner failed earlier (device timeout)"); return SNAPGPU_EDEVICE; }
-    if (!d->bai.ran) {
-        snapgpu::setError("bam_bai_download: no snapgpu_bam_bai_resident since the batch's last snapgpu_bam_resident or "
-                          "snapgpu_bam_bgzf_resident");
-        return SNAPGPU_EINVAL;
-    }
-    HIPCHK(hipSetDevice(a->device));
-    return baiDownload(a, d->bai, out, cap, used);
-}
-
-int snapgpu_bai_build_gpu(snapgpu_aligner_t *a, const char *records, uint64_t n, int32_t nRef, uint64_t streamOffset,
-                          char *bgzfOut, uint64_t bgzfCap, uint64_t *bgzfUsed, char *baiOut, uint64_t baiCap,
-                          uint64_t *baiUsed) {
-    if (!a || (!records && n) || !bgzfUsed || !baiUsed || nRef < 0) { snapgpu::setError("bai_build_gpu: bad argument"); return SNAPGPU_EINVAL; }
-    if (a->failed) { snapgpu::setError("aligner failed earlier (device timeout)"); return SNAPGPU_EDEVICE; }
-    if (streamOffset >= baiindex::kStreamOffsetLimit) {
-        snapgpu::setError("bai_build_gpu: streamOffset does not fit a virtual offset");
-        return SNAPGPU_EINVAL;
-    }
-    // the record starts: a walk over the block sizes on the host
-    std::vector<uint64_t> starts;
-    for (uint64_t u = 0; u < n;) {
-        starts.push_back(u);
-        const uint64_t bytes = n - u < 4 ? 0 : (uint64_t)baiindex::load32((const uint8_t *)records + u) + 4;
-        if (bytes < baiindex::kFixed || bytes > n - u) {
-            snapgpu::setError("bai_build_gpu: record " + std::to_string(starts.size() - 1) + ": truncated");
-            return SNAPGPU_EFORMAT;
-        }
-        u += bytes;
-    }
-    starts.push_back(n);
-    const uint64_t nRec = starts.size() - 1;
-    HIPCHK(hipSetDevice(a->device));
-    BgzfState &Z = a->bgzfBatch;
-    BaiState &S = a->baiBatch;
-    if (Z.ran && Z.maxBlocks) HIPCHK(hipEventSynchronize(Z.ev[3]));
-    if (S.launched) HIPCHK(hipEventSynchronize(S.ev[baigpu::kPasses]));
-    S.ran = false;
-    if (n) {
-        HIPCHK(samGrow(a, Z.in, n + 64));
-        HIPCHK(hipMemcpyAsync(Z.in.p, records, n, hipMemcpyHostToDevice, a->sideStream));
-    }
-    HIPCHK(samGrow(a, S.starts, starts.size() * 8));
-    HIPCHK(hipMemcpyAsync(S.starts.p, starts.data(), starts.size() * 8, hipMemcpyHostToDevice, a->sideStream));
-    HIPCHK(hipStreamSynchronize(a->sideStream));   // the host copies may go
-    if (int rc = bgzfLaunch(a, Z, (const char *)Z.in.p, nullptr, n, n)) return rc;
-    if (int rc = baiLaunch(a, S, (const char *)Z.in.p, (const uint64_t *)S.starts.p, nRec, n, (uint32_t)nRef,
-                           (const uint64_t *)Z.offs.p, streamOffset))
-        return rc;
-    if (int rc = bgzfDownload(a, Z, 0, bgzfOut, bgzfCap, bgzfUsed)) return rc;
-    return baiDownload(a, S, baiOut, baiCap, baiUsed);
-}
-
-int snapgpu_bai_last_ms(snapgpu_aligner_t *a, double *kernelMs, double *downloadMs) {
-    if (!a || !kernelMs || !downloadMs) return SNAPGPU_EINVAL;
-    if (!a->baiLast || !a->baiLast->ran) { snapgpu::setError("bai_last_ms: no device BAI call on this aligner"); return SNAPGPU_EINVAL; }
-    if (a->failed) { snapgpu::setError("aligner failed earlier (device timeout)"); return SNAPGPU_EDEVICE; }
-    HIPCHK(hipSetDevice(a->device));
-    BaiState &S = *a->baiLast;
-    float f = 0;
-    HIPCHK(hipEventSynchronize(S.ev[baigpu::kPasses]));
-    HIPCHK(hipEventElapsedTime(&f, S.ev[0], S.ev[baigpu::kPasses]));
-    *kernelMs = f;
-    *downloadMs = S.downloadMs;
-    return SNAPGPU_OK;
-}
-
-// ms[0 .. baigpu::kPasses): the passes of the last device BAI call (tools/bai_time.py)
-int snapgpu_internal_bai_pass_ms(snapgpu_aligner_t *a, double *ms) {
-    if (!a || !ms || !a->baiLast || !a->baiLast->ran || a->failed) return SNAPGPU_EINVAL;
-    HIPCHK(hipSetDevice(a->device));
-    BaiState &S = *a->baiLast;
-    HIPCHK(hipEventSynchronize(S.ev[baigpu::kPasses]));
-    for (int k = 0; k < baigpu::kPasses; k++) {
-        float f = 0;
-        HIPCHK(hipEventElapsedTime(&f, S.ev[k], S.ev[k + 1]));
-        ms[k] = f;
-    }
-    return SNAPGPU_OK;
-}
-
-// ------------------------------------------------- duplicate marking on the device (dupmark.hip)
-// The mark passes on the side stream over n records at text + start[i].
-static int dupLaunch(snapgpu_aligner_t *a, DupState &S, char *text, const uint64_t *start, uint64_t n, uint32_t nRef) {
-    for (auto &e : S.ev)
-        if (!e) HIPCHK(hipEventCreate(&e));
-    if (n > 0xfffffffeull) { snapgpu::setError("dupmark: batch too large"); return SNAPGPU_EINVAL; }
-    // an earlier call's kernels may still use the buffers that grow
-    if (S.launched) HIPCHK(hipEventSynchronize(S.ev[dupgpu::kPasses]));
-    S.ran = false;
-    uint64_t temp = 0;
-    HIPCHK(dupgpu::tempBytes(n, a->sideStream, &temp));
-    S.L = dupgpu::layout(n, temp);
-    HIPCHK(samGrow(a, S.work, S.L.bytes));
-    S.downloadMs = 0;
-    a->dupLast = &S;
-    HIPCHK(dupgpu::launch((uint8_t *)text, start, n, nRef, (char *)S.work.p, S.L, a->sideStream, S.ev));
-    S.ran = S.launched = true;
-    return SNAPGPU_OK;
-}
-
-int snapgpu_bam_dupmark_resident(snapgpu_aligner_t *a, snapgpu_device_reads_t *d) {
-    if (!a || !d) { snapgpu::setError("bam_dupmark_resident: null argument"); return SNAPGPU_EINVAL; }
-    if (a->failed) { snapgpu::setError("aligner failed earlier (device timeout)"); return SNAPGPU_EDEVICE; }
-    if (d->owner != a) { snapgpu::setError("bam_dupmark_resident: the resident batch belongs to another aligner"); return SNAPGPU_EINVAL; }
-    if (!d->bam.ran || !d->bam.sorted) {
-        snapgpu::setError("bam_dupmark_resident: the batch's last BAM call was not snapgpu_bam_resident_sorted (or there was none)");
-        return SNAPGPU_EINVAL;
-    }
-    HIPCHK(hipSetDevice(a->device));
-    BamState &R = d->bam;
-    const uint32_t nRef = (uint32_t)a->idx->genome->pieceOffsets.size();
-    d->bgzf.ran = d->bai.ran = false;   // the records change: a compressed stream of the earlier ones, and its index, are stale
-    if (int rc = dupLaunch(a, d->dup, (char *)R.text.p, (const uint64_t *)R.start.p, R.n, nRef)) return rc;
-    // the next pass set over these reads rewrites the records: it waits for the mark kernels too
-    HIPCHK(hipEventRecord(a->residentSideDone, a->sideStream));
-    a->residentSidePending = true;
-    return SNAPGPU_OK;
-}
-
-int snapgpu_bam_dupmark_stats(snapgpu_aligner_t *a, snapgpu_device_reads_t *d, uint64_t *nMarked, uint64_t *nGroups) {
-    if (!a || !d || !nMarked || !nGroups) { snapgpu::setError("bam_dupmark_stats: null argument"); return SNAPGPU_EINVAL; }
-    if (a->failed) { snapgpu::setError("aligner failed earlier (device timeout)"); return SNAPGPU_EDEVICE; }
-    if (!d->dup.ran) {
-        snapgpu::setError("bam_dupmark_stats: no snapgpu_bam_dupmark_resident since the batch's last snapgpu_bam_resident");
-        return SNAPGPU_EINVAL;
-    }
-    HIPCHK(hipSetDevice(a->device));
-    dupgpu::Result r{};
-    *nMarked = *nGroups = 0;
-    if (int rc = dupResult(a, d->dup, &r)) return rc;
-    *nMarked = r.marked;
-    *nGroups = r.groups;
-    return SNAPGPU_OK;
-}
-
-int snapgpu_bam_mark_duplicates_gpu(snapgpu_aligner_t *a, char *records, uint64_t n, int32_t nRef, uint64_t *nMarked,
-                                    uint64_t *nGroups) {
-    if (!a || (!records && n) || !nMarked || !nGroups || nRef < 0) { snapgpu::setError("bam_mark_duplicates_gpu: bad argument"); return SNAPGPU_EINVAL; }
-    if (a->failed) { snapgpu::setError("aligner failed earlier (device timeout)"); return SNAPGPU_EDEVICE; }
-    *nMarked = *nGroups = 0;
-    // the record starts: a walk over the block sizes on the host
-    std::vector<uint64_t> starts;
-    for (uint64_t u = 0; u < n;) {
-        starts.push_back(u);
-        const uint64_t bytes = n - u < 4 ? 0 : (uint64_t)baiindex::load32((const uint8_t *)records + u) + 4;
-        if (bytes < baiindex::kFixed || bytes > n - u) {
-            snapgpu::setError("bam_mark_duplicates_gpu: record " + std::to_string(starts.size() - 1) + ": truncated");
-            return SNAPGPU_EFORMAT;
-        }
-        u += bytes;
-    }
-    starts.push_back(n);
-    const uint64_t nRec = starts.size() - 1;
-    HIPCHK(hipSetDevice(a->device));
-    DupState &S = a->dupBatch;
-    if (S.launched) HIPCHK(hipEventSynchronize(S.ev[dupgpu::kPasses]));
-    S.ran = false;
-    HIPCHK(samGrow(a, S.in, n + 64));
-    if (n) HIPCHK(hipMemcpyAsync(S.in.p, records, n, hipMemcpyHostToDevice, a->sideStream));
-    HIPCHK(samGrow(a, S.starts, starts.size() * 8));
-    HIPCHK(hipMemcpyAsync(S.starts.p, starts.data(), starts.size() * 8, hipMemcpyHostToDevice, a->sideStream));
-    HIPCHK(hipStreamSynchronize(a->sideStream));   // the host copies may go
-    if (int rc = dupLaunch(a, S, (char *)S.in.p, (const uint64_t *)S.starts.p, nRec, (uint32_t)nRef)) return rc;
-    dupgpu::Result r{};
-    if (int rc = dupResult(a, S, &r)) return rc;   // the caller's records stay as they were
-    const auto t0 = std::chrono::steady_clock::now();
-    if (n) HIPCHK(hipMemcpy(records, S.in.p, n, hipMemcpyDeviceToHost));
-    S.downloadMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    *nMarked = r.marked;
-    *nGroups = r.groups;
-    return SNAPGPU_OK;
-}
-
-int snapgpu_bam_dupmark_last_ms(snapgpu_aligner_t *a, double *kernelMs, double *downloadMs) {
-    if (!a || !kernelMs || !downloadMs) return SNAPGPU_EINVAL;
-    if (!a->dupLast || !a->dupLast->ran) { snapgpu::setError("bam_dupmark_last_ms: no device duplicate marking on this aligner"); return SNAPGPU_EINVAL; }
-    if (a->failed) { snapgpu::setError("aligner failed earlier (device timeout)"); return SNAPGPU_EDEVICE; }
-    HIPCHK(hipSetDevice(a->device));
-    DupState &S = *a->dupLast;
-    float f = 0;
-    HIPCHK(hipEventSynchronize(S.ev[dupgpu::kPasses]));
-    HIPCHK(hipEventElapsedTime(&f, S.ev[0], S.ev[dupgpu::kPasses]));
-    *kernelMs = f;
-    *downloadMs = S.downloadMs;
-    return SNAPGPU_OK;
-}
-
-// ms[0 .. dupgpu::kPasses): the passes of the last device duplicate marking (tools/dupmark_time.py)
-int snapgpu_internal_dupmark_pass_ms(snapgpu_aligner_t *a, double *ms) {
-    if (!a || !ms || !a->dupLast || !a->dupLast->ran || a->failed) return SNAPGPU_EINVAL;
-    HIPCHK(hipSetDevice(a->device));
-    DupState &S = *a->dupLast;
-    HIPCHK(hipEventSynchronize(S.ev[dupgpu::kPasses]));
-    for (int k = 0; k < dupgpu::kPasses; k++) {
-        float f = 0;
-        HIPCHK(hipEventElapsedTime(&f, S.ev[k], S.ev[k + 1]));
-        ms[k] = f;
-    }
-    return SNAPGPU_OK;
-}
-
-// ------------------------------------------------- FASTQ parsed on the device (fastq_parse.hip)
-}  // extern "C"
-
-namespace {
-
-const uint64_t kFastqChunk = 16ull << 20;   // bytes per pinned staging chunk of the text upload
-
-// Bytes a grow-only buffer would newly allocate for `bytes` (ensure's policy), 0 when it fits.
-uint64_t growBytes(const snapgpu_aligner::ExBuf &b, uint64_t bytes) { return bytes <= b.cap ? 0 : bytes + bytes / 4 + 256; }
-
-hipError_t fqEnsure(snapgpu_aligner_t *a, snapgpu_aligner::ExBuf &b, uint64_t bytes) {
-    if (bytes <= b.cap) return hipSuccess;
-    devFree(a, b.p);
-    b.p = nullptr;
-    b.cap = 0;
-    const uint64_t want = growBytes(b, bytes);
-    const hipError_t e = hipMalloc(&b.p, want);
-    if (e == hipSuccess) b.cap = want;
-    return e;
-}
-
-// hipMemGetInfo before a group of allocations, as the device index builder asks: the group must fit
-// in what is free now.
-int fqFits(uint64_t need, const char *what) {
-    size_t freeB = 0, totalB = 0;
-    HIPCHK(hipMemGetInfo(&freeB, &totalB));
-    if (need > freeB) {
-        char msg[200];
-        snprintf(msg, sizeof msg, "fastq_upload: %s needs %llu bytes of device memory, %llu are free", what,
-                 (unsigned long long)need, (unsigned long long)freeB);
-        snapgpu::setError(msg);
-        return SNAPGPU_ENOMEM;
-    }
-    return SNAPGPU_OK;
-}
-
-// fill(dst, off, m): bytes [off, off + m) of the text into a staging chunk (false: setError was called)
-using FastqFill = std::function<bool(char *, uint64_t, uint64_t)>;
-
-// nBytes of text (or of a compressed stream) to dst[0 .. cap) in device memory, zeros after them,
-// through two pinned staging chunks: chunk k + 1 is filled by the host while chunk k crosses PCIe
-// (textDownload's reverse).  *last = the last byte.
-int fastqTextUpload(snapgpu_aligner_t *a, char *dst, uint64_t cap, uint64_t nBytes, const FastqFill &fill, char *last) {
-    auto &F = a->fq;
-    for (int k = 0; k < 2; k++) {
-        if (!F.pin[k]) HIPCHK(hipHostMalloc(&F.pin[k], kFastqChunk, hipHostMallocDefault));
-        if (!F.pinDone[k]) HIPCHK(hipEventCreateWithFlags(&F.pinDone[k], hipEventDisableTiming));
-    }
-    HIPCHK(hipMemsetAsync(dst + nBytes, 0, cap - nBytes, a->copyStream));
-    const uint64_t nChunks = (nBytes + kFastqChunk - 1) / kFastqChunk;
-    for (uint64_t k = 0; k < nChunks; k++) {
-        const uint64_t b = k * kFastqChunk, m = std::min(kFastqChunk, nBytes - b);
-        char *pin = (char *)F.pin[k & 1];
-        if (k >= 2)
-            if (int rc = waitEvent(a, F.pinDone[k & 1])) return rc;
-        if (!fill(pin, b, m)) return SNAPGPU_EIO;
-        if (k + 1 == nChunks) *last = pin[m - 1];
-        HIPCHK(hipMemcpyAsync(dst + b, pin, m, hipMemcpyHostToDevice, a->copyStream));
-        HIPCHK(hipEventRecord(F.pinDone[k & 1], a->copyStream));
-    }
-    HIPCHK(hipStreamSynchronize(a->copyStream));
-    return SNAPGPU_OK;
-}
-
-// [0, m) split over this rank's host threads (one below 1 MB)
-template <class Fn>
-void fastqParallel(uint64_t m, Fn fn) {
-    const unsigned t = m < (1u << 20) ? 1u : snapgpu::hostThreads(16);
-    std::vector<std::thread> th;
-    for (unsigned j = 1; j < t; j++) th.emplace_back([=] { fn(m * j / t, m * (j + 1) / t); });
-    fn(0, m / t);
-    for (auto &x : th) x.join();
-}
-
-// ---- BGZF inflated on the device (inflate.hip)
-using inflateblock::Member;
-
-int inflateWaves(snapgpu_aligner_t *a) {
-    if (!a->inf.waves) {
-        hipDeviceProp_t prop;
-        HIPCHK(hipGetDeviceProperties(&prop, a->device));
-        a->inf.waves = std::max(1, prop.multiProcessorCount) * (int)inflategpu::kWavesPerCu;
-    }
-    return SNAPGPU_OK;
-}
-
-// what the inflater's own buffers would newly allocate for a stream of n bytes in nMembers members
-uint64_t inflateGrowBytes(const snapgpu_aligner_t *a, uint64_t n, uint64_t nMembers) {
-    return growBytes(a->inf.in, n + inflategpu::kInSlack) + growBytes(a->inf.members, nMembers * sizeof(Member) + 16) +
-           growBytes(a->inf.status, (nMembers + 1) * 4 + 16);
-}
-
-// The stream to device memory through the text upload's staging chunks, its member table beside
-// it, the kernel over all members into dst (device memory with room for every member's output),
-// and the verdict: SNAPGPU_EFORMAT with the lowest refused member.  The caller has checked
-// inflateGrowBytes and dst against the device's free memory.  Waits.
-int inflateOnDevice(snapgpu_aligner_t *a, const char *what, const char *in, uint64_t n, const std::vector<Member> &members,
-                    char *dst) {
-    using clk = std::chrono::steady_clock;
-    auto &I = a->inf;
-    I.ran = false;
-    I.uploadMs = I.kernelMs = I.downloadMs = 0;
-    const uint64_t nm = members.size();
-    if (nm >= inflategpu::kNoBad) { snapgpu::setError(std::string(what) + ": too many members"); return SNAPGPU_EINVAL; }
-    if (int rc = inflateWaves(a)) return rc;
-    for (auto &e : I.ev)
-        if (!e) HIPCHK(hipEventCreate(&e));
-    HIPCHK(fqEnsure(a, I.in, n + inflategpu::kInSlack));
-    HIPCHK(fqEnsure(a, I.members, nm * sizeof(Member) + 16));
-    HIPCHK(fqEnsure(a, I.status, (nm + 1) * 4 + 16));
-    auto t0 = clk::now();
-    const FastqFill fill = [in](char *pin, uint64_t off, uint64_t m) {
-        fastqParallel(m, [=](uint64_t b, uint64_t e) { memcpy(pin + b, in + off + b, e - b); });
-        return true;
-    };
-    char last = 0;
-    if (int rc = fastqTextUpload(a, (char *)I.in.p, n + inflategpu::kInSlack, n, fill, &last)) return rc;
-    if (nm) HIPCHK(hipMemcpyAsync(I.members.p, members.data(), nm * sizeof(Member), hipMemcpyHostToDevice, a->copyStream));
-    HIPCHK(hipStreamSynchronize(a->copyStream));
-    I.uploadMs = std::chrono::duration<double, std::milli>(clk::now() - t0).count();
-    hipStream_t s = a->stream();
-    uint32_t *status = (uint32_t *)I.status.p, *firstBad = status + nm;
-    HIPCHK(hipEventRecord(I.ev[0], s));
-    HIPCHK(inflategpu::launch((const uint8_t *)I.in.p, (const Member *)I.members.p, (uint32_t)nm, (uint8_t *)dst, status,
-                              firstBad, (uint32_t)I.waves, s));
-    HIPCHK(hipEventRecord(I.ev[1], s));
-    uint32_t bad = inflategpu::kNoBad;
-    HIPCHK(hipMemcpyAsync(&bad, firstBad, 4, hipMemcpyDeviceToHost, s));
-    if (int rc = waitLane(a, a->lane[0])) return rc;
-    float f = 0;
-    HIPCHK(hipEventElapsedTime(&f, I.ev[0], I.ev[1]));
-    I.kernelMs = f;
-    I.ran = true;
-    if (bad != inflategpu::kNoBad) {
-        if (bad >= nm) { snapgpu::setError(std::string(what) + ": the kernel names a member the stream does not have"); return SNAPGPU_EDEVICE; }
-        uint32_t st = 0;
-        HIPCHK(hipMemcpy(&st, status + bad, 4, hipMemcpyDeviceToHost));
-        return snapgpu::bgzfRefused(what, bad, members[bad].inStart, st);
-    }
-    return SNAPGPU_OK;
-}
-
-// How the text reaches the parser's device buffer, which fastqRun sizes: the plain form uploads it
-// (fastqTextUpload), the BGZF form uploads the compressed stream and inflates it there.
-struct FastqArrival {
-    uint64_t nBytes = 0;      // the text's bytes
-    uint64_t extraNeed = 0;   // device bytes the arrival itself newly allocates (fastqRun's memory check counts them)
-    // the text into text[0 .. nBytes), zeros from there to cap; *last = its last byte (nBytes > 0);
-    // *kernelMs = what its own kernels took
-    std::function<int(char *text, uint64_t cap, char *last, double *kernelMs)> arrive;
-};
-
-// d and r: what the call has allocated so far (the caller frees them when the call fails)
-int fastqRun(snapgpu_aligner_t *a, const FastqArrival &arrival, const char *name, int clipping, bool hostBatch,
-             snapgpu_device_reads_t *&d, snapgpu_reads_t *&r) {
-    const uint64_t nBytes = arrival.nBytes;
-    using clk = std::chrono::steady_clock;
-    auto ms = [](clk::time_point t0) { return std::chrono::duration<double, std::milli>(clk::now() - t0).count(); };
-    auto &F = a->fq;
-    hipStream_t s = a->stream(), cs = a->copyStream;
-    for (auto &e : F.ev)
-        if (!e) HIPCHK(hipEventCreate(&e));
-    F.ran = false;
-    F.uploadMs = F.kernelMs = F.downloadMs = F.arriveKernelMs = 0;
-    for (double &m : F.passMs) m = 0;
-    bool evUsed[3] = {false, false, false};
-    // 1. the text, its tiles' newline counts and their scan
-    const uint64_t nTiles = fqgpu::tiles(nBytes), textCap = fqgpu::textCapacity(nBytes);
-    const uint64_t needTiles[4] = {textCap, nTiles * 4 + 16, (nTiles + 1) * 8, samgpu::scanTiles(nTiles) * 8 + 16};
-    snapgpu_aligner::ExBuf *bufTiles[4] = {&F.text, &F.counts, &F.tileStart, &F.sums};
-    uint64_t need = arrival.extraNeed;
-    for (int k = 0; k < 4; k++) need += growBytes(*bufTiles[k], needTiles[k]);
-    if (int rc = fqFits(need, "the text")) return rc;
-    for (int k = 0; k < 4; k++) HIPCHK(fqEnsure(a, *bufTiles[k], needTiles[k]));
-    const char *text = (const char *)F.text.p;
-    char last = '\n';
-    auto t0 = clk::now();
-    if (int rc = arrival.arrive((char *)F.text.p, textCap, &last, &F.arriveKernelMs)) return rc;
-    F.uploadMs = ms(t0) - F.arriveKernelMs;
-    uint64_t nNl = 0;
-    if (nBytes) {
-        HIPCHK(hipEventRecord(F.ev[0], s));
-        fqgpu::countNewlines(text, nBytes, (uint32_t *)F.counts.p, s);
-        HIPCHK(hipEventRecord(F.ev[1], s));
-        samgpu::scanStarts((const uint32_t *)F.counts.p, nTiles, (uint64_t *)F.sums.p, (uint64_t *)F.tileStart.p, s);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(F.ev[2], s));
-        evUsed[0] = true;
-        HIPCHK(hipMemcpyAsync(&nNl, (const uint64_t *)F.tileStart.p + nTiles, 8, hipMemcpyDeviceToHost, s));
-        if (int rc = waitLane(a, a->lane[0])) return rc;
-    }
-    // records are the line quadruples; a last line without its newline counts
-    const uint64_t nLines = nNl + (nBytes && last != '\n' ? 1 : 0), n = nLines / 4;
-    if (n > 0xffffffffull) { snapgpu::setError("fastq_upload: batch too large"); return SNAPGPU_EINVAL; }
-    // 2. newline positions, the records' lengths and clips, the scans of base and id lengths
-    uint64_t total = 0, idTotal = 0;
-    fqgpu::Records R{};
-    fqgpu::Totals hTot{};
-    if (n) {
-        const uint64_t needRec[7] = {nNl * 8 + 16, n * 20 + 16, (n + 1) * 8, (n + 1) * 8, samgpu::scanTiles(n) * 8 + 16,
-                                     samgpu::scanTiles(n) * 8 + 16, sizeof(fqgpu::Totals)};
-        snapgpu_aligner::ExBuf *bufRec[7] = {&F.nl, &F.rec, &F.baseStart, &F.idStart, &F.sums, &F.sums2, &F.tot};
-        need = 0;
-        for (int k = 0; k < 7; k++) need += growBytes(*bufRec[k], needRec[k]);
-        if (int rc = fqFits(need, "the line and record arrays")) return rc;
-        for (int k = 0; k < 7; k++) HIPCHK(fqEnsure(a, *bufRec[k], needRec[k]));
-        uint32_t *rec = (uint32_t *)F.rec.p;
-        R = fqgpu::Records{rec, rec + n, rec + 2 * n, rec + 3 * n, rec + 4 * n};
-        auto *tot = (fqgpu::Totals *)F.tot.p;
-        HIPCHK(hipEventRecord(F.ev[3], s));
-        HIPCHK(hipMemsetAsync(&tot->firstBad, 0xff, 8, s));
-        HIPCHK(hipMemsetAsync(&tot->baseBytes, 0, 16, s));   // and the two maxima behind it
-        fqgpu::lineStarts(text, nBytes, (const uint64_t *)F.tileStart.p, (uint64_t *)F.nl.p, nNl, s);
-        HIPCHK(hipEventRecord(F.ev[4], s));
-        fqgpu::records(text, nBytes, (const uint64_t *)F.nl.p, nNl, n, clipping, R, tot, s);
-        HIPCHK(hipEventRecord(F.ev[5], s));
-        samgpu::scanStarts(R.baseLen, n, (uint64_t *)F.sums.p, (uint64_t *)F.baseStart.p, s);
-        samgpu::scanStarts(R.idLen, n, (uint64_t *)F.sums2.p, (uint64_t *)F.idStart.p, s);
-        fqgpu::limits(R.baseLen, R.idLen, n, tot, s);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(F.ev[6], s));
-        evUsed[1] = true;
-        HIPCHK(hipMemcpyAsync(&hTot, tot, sizeof hTot, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipMemcpyAsync(&total, (const uint64_t *)F.baseStart.p + n, 8, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipMemcpyAsync(&idTotal, (const uint64_t *)F.idStart.p + n, 8, hipMemcpyDeviceToHost, s));
-        if (int rc = waitLane(a, a->lane[0])) return rc;
-        if (hTot.firstBad < n) {
-            snapgpu::setError(std::string("FASTQ record without '@' header in ") + name);
-            return SNAPGPU_EFORMAT;
-        }
-        if (hTot.baseBytes != total) {
-            char msg[160];
-            snprintf(msg, sizeof msg, "fastq_upload: the record pass counted %llu base bytes, the scan placed %llu",
-                     (unsigned long long)hTot.baseBytes, (unsigned long long)total);
-            snapgpu::setError(msg);
-            return SNAPGPU_EDEVICE;
-        }
-    }
-    // 3. the resident batch (snapgpu_reads_upload's buffers) and the copy pass into it
-    const uint64_t dBytes[7] = {total + 64, total + 64, (n + 1) * 8, (n + 1) * 4, (n + 1) * sizeof(snapgpu_result_t),
-                                3 * (n + 1) * sizeof(uint32_t), (n + 8) * SEEDS_PER_READ * sizeof(SeedRec)};
-    // what the SAM / BAM calls take from the batch itself: the packed ids, the four per-record arrays
-    // in one allocation, and (at most the last read's unclipped bases and qualities) the tail
-    auto al16 = [](uint64_t x) { return (x + 15) & ~15ull; };
-    const uint64_t oIdLen = al16(n * 8), oFront = al16(oIdLen + n * 4), oFull = al16(oFront + n * 4),
-                   metaBytes = al16(oFull + n * 4) + 16;
-    need = idTotal + 16 + metaBytes + 2ull * hTot.maxBaseLen;
-    for (uint64_t b : dBytes) need += b;
-    if (int rc = fqFits(need, "the resident batch")) return rc;
-    d = new snapgpu_device_reads_t();
-    d->owner = a;
-    d->n = n;
-    d->device = a->device;
-    d->hasIds = true;
-    d->clipping = clipping;
-    d->total = total;
-    d->idTotal = idTotal;
-    d->maxUnclipped = hTot.maxBaseLen;
-    d->maxIdLen = hTot.maxIdLen;
-    HIPCHK(hipMalloc(&d->dIds, idTotal + 16));
-    HIPCHK(hipMalloc(&d->dMeta, metaBytes));
-    d->dIdStart = (const uint64_t *)d->dMeta;
-    d->dIdLen = (const uint32_t *)(d->dMeta + oIdLen);
-    d->dFront = (const uint32_t *)(d->dMeta + oFront);
-    d->dUnclipped = (const uint32_t *)(d->dMeta + oFull);
-    HIPCHK(hipMemsetAsync(d->dIds + idTotal, 0, 16, s));
-    HIPCHK(hipMalloc(&d->dBases, dBytes[0]));
-    HIPCHK(hipMalloc(&d->dQuals, dBytes[1]));
-    HIPCHK(hipMalloc(&d->dOffsets, dBytes[2]));
-    HIPCHK(hipMalloc(&d->dLengths, dBytes[3]));
-    HIPCHK(hipMalloc(&d->dOut, dBytes[4]));
-    HIPCHK(hipMalloc(&d->dDefer, dBytes[5]));   // pass-1 / pass-2 defers, arena overflows
-    HIPCHK(hipMalloc(&d->dSeeds, dBytes[6]));
-    if (n) {
-        HIPCHK(hipEventRecord(F.ev[7], s));
-        fqgpu::pack(text, nBytes, (const uint64_t *)F.nl.p, nNl, n, R, (const uint64_t *)F.baseStart.p,
-                    (const uint64_t *)F.idStart.p, d->dBases, d->dQuals, d->dIds, d->dOffsets, d->dLengths, s);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(F.ev[8], s));
-        evUsed[2] = true;
-        // the batch's own copies of what the next upload overwrites in the parser's buffers
-        HIPCHK(hipMemcpyAsync(d->dMeta, F.idStart.p, n * 8, hipMemcpyDeviceToDevice, s));
-        HIPCHK(hipMemcpyAsync(d->dMeta + oIdLen, R.idLen, n * 4, hipMemcpyDeviceToDevice, s));
-        HIPCHK(hipMemcpyAsync(d->dMeta + oFront, R.front, n * 4, hipMemcpyDeviceToDevice, s));
-        HIPCHK(hipMemcpyAsync(d->dMeta + oFull, R.baseLen, n * 4, hipMemcpyDeviceToDevice, s));
-        if (int rc = waitLane(a, a->lane[0])) return rc;
-    }
-    // 4. offsets and lengths always come back (the extent hash is a sequential chain); the batch on request
-    t0 = clk::now();
-    std::vector<uint64_t> tmpOff;
-    std::vector<uint32_t> tmpLen;
-    uint64_t *hOff;
-    uint32_t *hLen;
-    if (hostBatch) {
-        r = snapgpu::allocReads(n, total, false, /*zero=*/false);
-        r->ids = new char[idTotal + 1]();
-        r->idOffsets = new uint64_t[n + 1]();
-        r->idLengths = new uint32_t[n + 1]();
-        if (clipping) {
-            r->frontClipped = new uint32_t[n + 1]();
-            r->unclippedLength = new uint32_t[n + 1]();
-        }
-        r->clipping = clipping;
-        r->nUploads = 1;
-        hOff = r->offsets;
-        hLen = r->lengths;
-        if (total) {
-            HIPCHK(hipMemcpyAsync(r->bases, d->dBases, total, hipMemcpyDeviceToHost, cs));
-            HIPCHK(hipMemcpyAsync(r->quals, d->dQuals, total, hipMemcpyDeviceToHost, cs));
-        }
-        memset(r->bases + total, 0, 64);   // the batch's zero slack
-        memset(r->quals + total, 0, 64);
-        if (idTotal) HIPCHK(hipMemcpyAsync(r->ids, d->dIds, idTotal, hipMemcpyDeviceToHost, cs));
-        if (n) {
-            HIPCHK(hipMemcpyAsync(r->idOffsets, d->dIdStart, n * 8, hipMemcpyDeviceToHost, cs));
-            HIPCHK(hipMemcpyAsync(r->idLengths, d->dIdLen, n * 4, hipMemcpyDeviceToHost, cs));
-            if (clipping) {
-                HIPCHK(hipMemcpyAsync(r->frontClipped, d->dFront, n * 4, hipMemcpyDeviceToHost, cs));
-                HIPCHK(hipMemcpyAsync(r->unclippedLength, d->dUnclipped, n * 4, hipMemcpyDeviceToHost, cs));
-            }
-        }
-    } else {
-        tmpOff.resize(n + 1);
-        tmpLen.resize(n + 1);
-        hOff = tmpOff.data();
-        hLen = tmpLen.data();
-    }
-    if (n) {
-        HIPCHK(hipMemcpyAsync(hOff, d->dOffsets, n * 8, hipMemcpyDeviceToHost, cs));
-        HIPCHK(hipMemcpyAsync(hLen, d->dLengths, n * 4, hipMemcpyDeviceToHost, cs));
-    }
-    HIPCHK(hipStreamSynchronize(cs));
-    uint64_t bytes = 0;
-    for (uint64_t i = 0; i < n; i++) {   // as snapgpu_reads_upload
-        const uint64_t endb = hOff[i] + hLen[i];
-        if (endb > bytes) bytes = endb;
-        if (hLen[i] > d->maxLen) d->maxLen = hLen[i];
-        d->extentHash = extentMix(d->extentHash, hOff[i], hLen[i]);
-    }
-    if (bytes > total) { snapgpu::setError("fastq_upload: a clipped read ends past the batch"); return SNAPGPU_EDEVICE; }
-    d->bytes = bytes;
-    // the SAM / BAM lines print the unclipped SEQ and QUAL: what the zeroing takes stays in the tail
-    if (const uint64_t tail = total - bytes) {
-        if (tail > hTot.maxBaseLen) { snapgpu::setError("fastq_upload: the tail is longer than the longest read"); return SNAPGPU_EDEVICE; }
-        HIPCHK(hipMalloc(&d->dTail, 2 * tail));
-        HIPCHK(hipMemcpyAsync(d->dTail, d->dBases + bytes, tail, hipMemcpyDeviceToDevice, cs));
-        HIPCHK(hipMemcpyAsync(d->dTail + tail, d->dQuals + bytes, tail, hipMemcpyDeviceToDevice, cs));
-    }
-    // zero from the largest clipped end on, as an upload of the clipped batch leaves it
-    HIPCHK(hipMemsetAsync(d->dBases + bytes, 0, total + 64 - bytes, cs));
-    HIPCHK(hipMemsetAsync(d->dQuals + bytes, 0, total + 64 - bytes, cs));
-    HIPCHK(hipStreamSynchronize(cs));
-    F.downloadMs = ms(t0);
-    static const int kFirst[3] = {0, 3, 7}, kCount[3] = {2, 3, 1};   // the event groups and their intervals
-    for (int k = 0, slot = 0; k < 3; slot += kCount[k], k++)
-        if (evUsed[k])
-            for (int j = 0; j < kCount[k]; j++) {
-                float f = 0;
-                HIPCHK(hipEventElapsedTime(&f, F.ev[kFirst[k] + j], F.ev[kFirst[k] + j + 1]));
-                F.passMs[slot + j] = f;
-                F.kernelMs += f;
-            }
-    F.kernelMs += F.arriveKernelMs;
-    F.ran = true;
-    return SNAPGPU_OK;
-}
-
-// the plain form's arrival: the text itself through the staging chunks
-FastqArrival fastqPlainArrival(snapgpu_aligner_t *a, uint64_t nBytes, const FastqFill &fill) {
-    FastqArrival A;
-    A.nBytes = nBytes;
-    A.arrive = [a, nBytes, &fill](char *text, uint64_t cap, char *last, double *) -> int {
-        return fastqTextUpload(a, text, cap, nBytes, fill, last);
-    };
-    return A;
-}
-
-// The BGZF form's arrival: the compressed stream goes up and bgzf_inflate_kernel writes the text
-// where the parser reads it; its last byte comes back.
-FastqArrival fastqBgzfArrival(snapgpu_aligner_t *a, const char *in, uint64_t n, const std::vector<Member> &members,
-                              uint64_t textBytes) {
-    FastqArrival A;
-    A.nBytes = textBytes;
-    A.extraNeed = inflateGrowBytes(a, n, members.size());
-    A.arrive = [a, in, n, &members, textBytes](char *text, uint64_t cap, char *last, double *kernelMs) -> int {
-        HIPCHK(hipMemsetAsync(text + textBytes, 0, cap - textBytes, a->stream()));
-        const int rc = inflateOnDevice(a, "fastq_upload_bgzf", in, n, members, text);
-        *kernelMs = a->inf.kernelMs;
-        if (rc) return rc;
-        if (textBytes) HIPCHK(hipMemcpy(last, text + textBytes - 1, 1, hipMemcpyDeviceToHost));
-        return (int)SNAPGPU_OK;
-    };
-    return A;
-}
-
-int fastqUpload(snapgpu_aligner_t *a, const FastqArrival &arrival, const char *name, int clipping,
-                uint32_t flags, snapgpu_device_reads_t **dOut, snapgpu_reads_t **readsOut) {
-    if (dOut) *dOut = nullptr;
-    if (readsOut) *readsOut = nullptr;
-    const bool hostBatch = flags & SNAPGPU_FASTQ_HOST_BATCH;
-    if (!a || !dOut || !name || (hostBatch && !readsOut) || clipping < 0 || clipping > 3 ||
-        (flags & ~SNAPGPU_FASTQ_HOST_BATCH)) {
-        snapgpu::setError("fastq_upload: bad argument");
-        return SNAPGPU_EINVAL;
-    }
-    if (a->failed) { snapgpu::setError("aligner failed earlier (device timeout)"); return SNAPGPU_EDEVICE; }
-    HIPCHK(hipSetDevice(a->device));
-    snapgpu_device_reads_t *d = nullptr;
-    snapgpu_reads_t *r = nullptr;
-    const int rc = fastqRun(a, arrival, name, clipping, hostBatch, d, r);
-    if (rc != SNAPGPU_OK) {
-        snapgpu_device_reads_free(d);
-        snapgpu_reads_free(r);
-        return rc;
-    }
-    *dOut = d;
-    if (hostBatch) *readsOut = r;
-    return SNAPGPU_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int snapgpu_fastq_upload(snapgpu_aligner_t *a, const char *text, uint64_t nBytes, const char *name, int clipping,
-                         uint32_t flags, snapgpu_device_reads_t **dOut, snapgpu_reads_t **readsOut) {
-    if (!text && nBytes) {
-        if (dOut) *dOut = nullptr;
-        if (readsOut) *readsOut = nullptr;
-        snapgpu::setError("fastq_upload: bad argument");
-        return SNAPGPU_EINVAL;
-    }
-    const FastqFill fill = [text](char *dst, uint64_t off, uint64_t m) {
-        fastqParallel(m, [=](uint64_t b, uint64_t e) { memcpy(dst + b, text + off + b, e - b); });
-        return true;
-    };
-    return fastqUpload(a, fastqPlainArrival(a, nBytes, fill), name, clipping, flags, dOut, readsOut);
-}
-
-int snapgpu_fastq_upload_file(snapgpu_aligner_t *a, const char *path, int clipping, uint32_t flags,
-                              snapgpu_device_reads_t **dOut, snapgpu_reads_t **readsOut) {
-    if (dOut) *dOut = nullptr;
-    if (readsOut) *readsOut = nullptr;
-    if (!path) { snapgpu::setError("fastq_upload: bad argument"); return SNAPGPU_EINVAL; }
-    const int fd = open(path, O_RDONLY);
-    if (fd < 0) { snapgpu::setError(std::string("cannot open ") + path); return SNAPGPU_EIO; }
-    struct stat sb;
-    if (fstat(fd, &sb) != 0) { close(fd); snapgpu::setError(std::string("cannot stat ") + path); return SNAPGPU_EIO; }
-    // the file goes straight into the staging chunks: one host pass over its bytes
-    const FastqFill fill = [fd, path](char *dst, uint64_t off, uint64_t m) {
-        std::atomic<bool> ok{true};
-        fastqParallel(m, [&, dst, off](uint64_t b, uint64_t e) {
-            while (b < e) {
-                const ssize_t got = pread(fd, dst + b, e - b, (off_t)(off + b));
-                if (got <= 0) { ok = false; return; }
-                b += (uint64_t)got;
-            }
-        });
-        if (!ok) snapgpu::setError(std::string("cannot read ") + path);
-        return ok.load();
-    };
-    const int rc = fastqUpload(a, fastqPlainArrival(a, (uint64_t)sb.st_size, fill), path, clipping, flags, dOut, readsOut);
-    close(fd);
-    return rc;
-}
-
-int snapgpu_fastq_upload_bgzf(snapgpu_aligner_t *a, const char *data, uint64_t nBytes, const char *name, int clipping,
-                              uint32_t flags, snapgpu_device_reads_t **dOut, snapgpu_reads_t **readsOut) {
-    if (dOut) *dOut = nullptr;
-    if (readsOut) *readsOut = nullptr;
-    if (!a || (!data && nBytes) || !name) {
-        snapgpu::setError("fastq_upload_bgzf: bad argument");
-        return SNAPGPU_EINVAL;
-    }
-    std::vector<Member> members;
-    uint64_t textBytes = 0;
-    if (int rc = snapgpu::bgzfWalk("fastq_upload_bgzf", data, nBytes, members, &textBytes)) return rc;
-    return fastqUpload(a, fastqBgzfArrival(a, data, nBytes, members, textBytes), name, clipping, flags, dOut, readsOut);
-}
-
-int snapgpu_fastq_upload_bgzf_file(snapgpu_aligner_t *a, const char *path, int clipping, uint32_t flags,
-                                   snapgpu_device_reads_t **dOut, snapgpu_reads_t **readsOut) {
-    if (dOut) *dOut = nullptr;
-    if (readsOut) *readsOut = nullptr;
-    if (!path) { snapgpu::setError("fastq_upload_bgzf: bad argument"); return SNAPGPU_EINVAL; }
-    const int fd = open(path, O_RDONLY);
-    if (fd < 0) { snapgpu::setError(std::string("cannot open ") + path); return SNAPGPU_EIO; }
-    struct stat sb;
-    if (fstat(fd, &sb) != 0) { close(fd); snapgpu::setError(std::string("cannot stat ") + path); return SNAPGPU_EIO; }
-    // the member walk hops through the whole stream, so the compressed file is read first
-    const uint64_t size = (uint64_t)sb.st_size;
-    std::unique_ptr<char[]> data(new char[size ? size : 1]);
-    std::atomic<bool> ok{true};
-    char *dst = data.get();
-    fastqParallel(size, [&ok, fd, dst](uint64_t b, uint64_t e) {
-        while (b < e) {
-            const ssize_t got = pread(fd, dst + b, e - b, (off_t)b);
-            if (got <= 0) { ok = false; return; }
-            b += (uint64_t)got;
-        }
-    });
-    close(fd);
-    if (!ok) { snapgpu::setError(std::string("cannot read ") + path); return SNAPGPU_EIO; }
-    return snapgpu_fastq_upload_bgzf(a, data.get(), size, path, clipping, flags, dOut, readsOut);
-}
-
-int snapgpu_bgzf_inflate_gpu(snapgpu_aligner_t *a, const char *in, uint64_t n, char *out, uint64_t cap, uint64_t *used) {
-    if (!a || (!in && n) || !used) { snapgpu::setError("bgzf_inflate_gpu: null argument"); return SNAPGPU_EINVAL; }
-    *used = 0;
-    if (a->failed) { snapgpu::setError("aligner failed earlier (device timeout)"); return SNAPGPU_EDEVICE; }
-    std::vector<Member> members;
-    uint64_t total = 0;
-    if (int rc = snapgpu::bgzfWalk("bgzf_inflate_gpu", in, n, members, &total)) return rc;
-    *used = total;
-    if (total > cap || (!out && total)) { snapgpu::setError("bgzf_inflate_gpu: output buffer too small"); return SNAPGPU_EINVAL; }
-    HIPCHK(hipSetDevice(a->device));
-    auto &I = a->inf;
-    if (int rc = fqFits(inflateGrowBytes(a, n, members.size()) + growBytes(I.out, total + 64), "the stream and its output")) return rc;
-    HIPCHK(fqEnsure(a, I.out, total + 64));
-    if (int rc = inflateOnDevice(a, "bgzf_inflate_gpu", in, n, members, (char *)I.out.p)) return rc;
-    const auto t0 = std::chrono::steady_clock::now();
-    if (total)
-        if (int rc = textDownload(a, (const char *)I.out.p, total, out)) return rc;
-    I.downloadMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    return SNAPGPU_OK;
-}
-
-int snapgpu_bgzf_inflate_last_ms(snapgpu_aligner_t *a, double *uploadMs, double *kernelMs, double *downloadMs) {
-    if (!a || !uploadMs || !kernelMs || !downloadMs) return SNAPGPU_EINVAL;
-    if (!a->inf.ran) { snapgpu::setError("bgzf_inflate_last_ms: no device inflate on this aligner"); return SNAPGPU_EINVAL; }
-    *uploadMs = a->inf.uploadMs;
-    *kernelMs = a->inf.kernelMs;
-    *downloadMs = a->inf.downloadMs;
-    return SNAPGPU_OK;
-}
-
-int snapgpu_bgzf_inflate_waves(snapgpu_aligner_t *a) {
-    if (!a) { snapgpu::setError("bgzf_inflate_waves: null argument"); return SNAPGPU_EINVAL; }
-    if (a->failed) { snapgpu::setError("aligner failed earlier (device timeout)"); return SNAPGPU_EDEVICE; }
-    if (int rc = inflateWaves(a)) return rc;
-    return a->inf.waves;
-}
-
-int snapgpu_fastq_last_ms(snapgpu_aligner_t *a, double *uploadMs, double *kernelMs, double *downloadMs) {
-    if (!a || !uploadMs || !kernelMs || !downloadMs) return SNAPGPU_EINVAL;
-    if (!a->fq.ran) { snapgpu::setError("fastq_last_ms: no device FASTQ parse on this aligner"); return SNAPGPU_EINVAL; }
-    *uploadMs = a->fq.uploadMs;
-    *kernelMs = a->fq.kernelMs;
-    *downloadMs = a->fq.downloadMs;
-    return SNAPGPU_OK;
-}
-
-uint32_t snapgpu_fastq_tile_bytes(void) { return fqgpu::kTileBytes; }
-
-// ms[0 .. 6): newline count, its scan, line starts, record pass, the two length scans, copy pass of the
-// last device FASTQ parse (tools/fastq_parse_time.py)
-int snapgpu_internal_fastq_pass_ms(snapgpu_aligner_t *a, double *ms) {
-    if (!a || !ms || !a->fq.ran) return SNAPGPU_EINVAL;
-    for (int k = 0; k < 6; k++) ms[k] = a->fq.passMs[k];
-    return SNAPGPU_OK;
-}
-
-int snapgpu_device_reads_peek(snapgpu_aligner_t *a, snapgpu_device_reads_t *d, uint64_t *n, uint64_t *bytes,
-                              uint32_t *maxLen, uint64_t *extentHash, uint64_t *offsets, uint32_t *lengths,
-                              char *bases, char *quals) {
-    if (!a || !d || d->owner != a) { snapgpu::setError("device_reads_peek: bad argument"); return SNAPGPU_EINVAL; }
-    if (a->failed) { snapgpu::setError("aligner failed earlier (device timeout)"); return SNAPGPU_EDEVICE; }
-    HIPCHK(hipSetDevice(a->device));
-    if (n) *n = d->n;
-    if (bytes) *bytes = d->bytes;
-    if (maxLen) *maxLen = d->maxLen;
-    if (extentHash) *extentHash = d->extentHash;
-    if (offsets && d->n) HIPCHK(hipMemcpy(offsets, d->dOffsets, d->n * 8, hipMemcpyDeviceToHost));
-    if (lengths && d->n) HIPCHK(hipMemcpy(lengths, d->dLengths, d->n * 4, hipMemcpyDeviceToHost));
-    if (bases) HIPCHK(hipMemcpy(bases, d->dBases, d->bytes + 64, hipMemcpyDeviceToHost));
-    if (quals) HIPCHK(hipMemcpy(quals, d->dQuals, d->bytes + 64, hipMemcpyDeviceToHost));
-    return SNAPGPU_OK;
-}
-
-int snapgpu_device_reads_ids_download(snapgpu_aligner_t *a, snapgpu_device_reads_t *d, char *ids, uint64_t cap,
-                                      uint64_t *used, uint64_t *idOffsets, uint32_t *idLengths, uint32_t *frontClipped,
-                                      uint32_t *unclippedLength) {
-    if (!a || !d || !used || d->owner != a) { snapgpu::setError("device_reads_ids_download: bad argument"); return SNAPGPU_EINVAL; }
-    *used = 0;
-    if (a->failed) { snapgpu::setError("aligner failed earlier (device timeout)"); return SNAPGPU_EDEVICE; }
-    if (!d->hasIds) {
-        snapgpu::setError("device_reads_ids_download: the resident batch holds no ids of its own (only snapgpu_fastq_upload leaves them)");
-        return SNAPGPU_EINVAL;
-    }
-    *used = d->idTotal;
-    if (d->idTotal > cap || (!ids && d->idTotal)) {
-        snapgpu::setError("device_reads_ids_download: output buffer too small");
-        return SNAPGPU_EINVAL;
-    }
-    HIPCHK(hipSetDevice(a->device));
-    if (d->idTotal) HIPCHK(hipMemcpy(ids, d->dIds, d->idTotal, hipMemcpyDeviceToHost));
-    if (d->n) {
-        if (idOffsets) HIPCHK(hipMemcpy(idOffsets, d->dIdStart, d->n * 8, hipMemcpyDeviceToHost));
-        if (idLengths) HIPCHK(hipMemcpy(idLengths, d->dIdLen, d->n * 4, hipMemcpyDeviceToHost));
-        if (d->clipping) {
-            if (frontClipped) HIPCHK(hipMemcpy(frontClipped, d->dFront, d->n * 4, hipMemcpyDeviceToHost));
-            if (unclippedLength) HIPCHK(hipMemcpy(unclippedLength, d->dUnclipped, d->n * 4, hipMemcpyDeviceToHost));
-        }
-    }
-    return SNAPGPU_OK;
-}
-
-// ms[0 .. 3): the compress pass, the scan, the gather pass with the check, of the last device BGZF
-// call (tools/bgzf_gpu_time.py)
-int snapgpu_internal_bgzf_pass_ms(snapgpu_aligner_t *a, double *ms) {
-    if (!a || !ms || !a->bgzfLast || a->failed) return SNAPGPU_EINVAL;
-    HIPCHK(hipSetDevice(a->device));
-    BgzfState &S = *a->bgzfLast;
-    for (int k = 0; k < 3; k++) {
-        float f = 0;
-        if (S.maxBlocks) {
-            HIPCHK(hipEventSynchronize(S.ev[k + 1]));
-            HIPCHK(hipEventElapsedTime(&f, S.ev[k], S.ev[k + 1]));
-        }
-        ms[k] = f;
-    }
-    return SNAPGPU_OK;
-}
-
-int snapgpu_sam_last_ms(snapgpu_aligner_t *a, double *kernelMs, double *downloadMs) {
-    if (!a || !kernelMs || !downloadMs) return SNAPGPU_EINVAL;
-    if (!a->samLast) { snapgpu::setError("sam_last_ms: no device SAM call on this aligner"); return SNAPGPU_EINVAL; }
-    if (a->failed) { snapgpu::setError("aligner failed earlier (device timeout)"); return SNAPGPU_EDEVICE; }
-    HIPCHK(hipSetDevice(a->device));
-    SamState &S = *a->samLast;
-    float f = 0;
-    if (S.n) {
-        HIPCHK(hipEventSynchronize(S.ev[1]));
-        HIPCHK(hipEventElapsedTime(&f, S.ev[0], S.ev[1]));
-    }
-    *kernelMs = f;
-    *downloadMs = S.downloadMs;
-    return SNAPGPU_OK;
-}
-
-int snapgpu_sam_pass_ms(snapgpu_aligner_t *a, double *lengthMs, double *scanMs, double *writeMs) {
-    if (!a || !lengthMs || !scanMs || !writeMs) return SNAPGPU_EINVAL;
-    if (!a->samLast) { snapgpu::setError("sam_pass_ms: no device SAM call on this aligner"); return SNAPGPU_EINVAL; }
-    if (a->failed) { snapgpu::setError("aligner failed earlier (device timeout)"); return SNAPGPU_EDEVICE; }
-    HIPCHK(hipSetDevice(a->device));
-    SamState &S = *a->samLast;
-    float f[3] = {0, 0, 0};
-    if (S.n) {
-        HIPCHK(hipEventSynchronize(S.ev[1]));
-        HIPCHK(hipEventElapsedTime(&f[0], S.ev[0], S.ev[2]));
-        HIPCHK(hipEventElapsedTime(&f[1], S.sorted ? S.ev[4] : S.ev[2], S.ev[3]));   // the sort step is not the scan's
-        HIPCHK(hipEventElapsedTime(&f[2], S.ev[3], S.ev[1]));
-    }
-    *lengthMs = f[0];
-    *scanMs = f[1];
-    *writeMs = f[2];
-    return SNAPGPU_OK;
-}
-
-int snapgpu_sam_sort_ms(snapgpu_aligner_t *a, double *sortMs) {
-    if (!a || !sortMs) return SNAPGPU_EINVAL;
-    if (!a->samLast) { snapgpu::setError("sam_sort_ms: no device SAM call on this aligner"); return SNAPGPU_EINVAL; }
-    if (a->failed) { snapgpu::setError("aligner failed earlier (device timeout)"); return SNAPGPU_EDEVICE; }
-    HIPCHK(hipSetDevice(a->device));
-    SamState &S = *a->samLast;
-    float f = 0;
-    if (S.n && S.sorted) {
-        HIPCHK(hipEventSynchronize(S.ev[1]));
-        HIPCHK(hipEventElapsedTime(&f, S.ev[2], S.ev[4]));
-    }
-    *sortMs = f;
-    return SNAPGPU_OK;
-}
-
 int snapgpu_cigar_batch(snapgpu_aligner_t *a, const snapgpu_reads_t *reads, const uint32_t *locations,
                         const uint8_t *directions, int useM, int32_t *editDistance, uint32_t *nOps, uint32_t *ops) {
     if (!a || !reads || !locations || !directions || !editDistance || !nOps || !ops) return SNAPGPU_EINVAL;
@@ -5229,18 +3168,8 @@ static int cigarPinned(snapgpu_aligner_t *a, const char *const base[2], const ui
     const uint64_t oOff = 0, oLen = al8(oOff + (n + 1) * 8), oLoc = al8(oLen + (n + 1) * 4), oDir = al8(oLoc + (n + 1) * 4),
                    oBases = al8(oDir + n + 1), inBytes = al8(oBases + total + 64);
     const uint64_t rEd = 0, rN = al8((n + 1) * 4), rOps = al8(rN + (n + 1) * 4), outBytes = rOps + (n + 1) * CIG_MAX_OPS * 4;
-    auto ensure = [a](snapgpu_aligner::ExBuf &b, uint64_t bytes) -> hipError_t {
-        if (bytes <= b.cap) return hipSuccess;
-        devFree(a, b.p);
-        b.p = nullptr;
-        b.cap = 0;
-        const uint64_t want = bytes + bytes / 4 + 256;
-        hipError_t e = hipMalloc(&b.p, want);
-        if (e == hipSuccess) b.cap = want;
-        return e;
-    };
-    HIPCHK(ensure(a->cgIn, inBytes));
-    HIPCHK(ensure(a->cgOut, outBytes));
+    HIPCHK(devGrow(a, a->cgIn, inBytes));
+    HIPCHK(devGrow(a, a->cgOut, outBytes));
     auto pinned = [](void *&p, uint64_t &cap, uint64_t bytes) -> hipError_t {
         if (bytes <= cap) return hipSuccess;
         hostPinnedFree(p);
@@ -5437,16 +3366,8 @@ int snapgpu_copy_peak(snapgpu_aligner_t *a, uint64_t bytes, double *ms) {
 int snapgpu_internal_devbuf(snapgpu_aligner_t *a, int slot, uint64_t bytes, void **p) {
     if (!a || slot < 0 || slot >= 8 || !p) return SNAPGPU_EINVAL;
     if (a->failed) return SNAPGPU_EDEVICE;
-    auto &b = a->aux[slot];
-    if (bytes > b.cap) {
-        devFree(a, b.p);
-        b.p = nullptr;
-        b.cap = 0;
-        const uint64_t want = bytes + bytes / 4 + 256;
-        if (hipMalloc(&b.p, want) != hipSuccess) return SNAPGPU_ENOMEM;
-        b.cap = want;
-    }
-    *p = b.p;
+    if (devGrow(a, a->aux[slot], bytes) != hipSuccess) return SNAPGPU_ENOMEM;
+    *p = a->aux[slot].p;
     return SNAPGPU_OK;
 }
 hipStream_t snapgpu_internal_stream(snapgpu_aligner_t *a) { return a->sideStream; }   // charseeds.hip

@@ -1,4 +1,4 @@
-// bai.h -- the device BAI builder's kernels (bai.hip) as aligner.hip launches them.
+// bai.h -- the device BAI builder's kernels (bai.hip) as output_chain.hip launches them.
 #pragma once
 #include "bai_index.h"
 

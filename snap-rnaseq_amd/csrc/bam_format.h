@@ -1,4 +1,4 @@
-// bam_format.h -- the device BAM encoder's kernels (bam_format.hip) as aligner.hip launches them.
+// bam_format.h -- the device BAM encoder's kernels (bam_format.hip) as output_chain.hip launches them.
 #pragma once
 #include "bam_line.h"
 #include "sam_format.h"

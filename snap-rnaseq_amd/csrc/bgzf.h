@@ -1,4 +1,4 @@
-// bgzf.h -- the device BGZF compressor's kernels (bgzf.hip) as aligner.hip launches them.
+// bgzf.h -- the device BGZF compressor's kernels (bgzf.hip) as output_chain.hip launches them.
 #pragma once
 #include "bgzf_block.h"
 

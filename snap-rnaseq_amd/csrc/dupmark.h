@@ -1,4 +1,4 @@
-// dupmark.h -- the device duplicate marking's kernels (dupmark.hip) as aligner.hip launches them.
+// dupmark.h -- the device duplicate marking's kernels (dupmark.hip) as output_chain.hip launches them.
 #pragma once
 #include "dupmark_rule.h"
 

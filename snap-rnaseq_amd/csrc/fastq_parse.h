@@ -1,4 +1,4 @@
-// fastq_parse.h -- the device FASTQ parser's kernels (fastq_parse.hip) as aligner.hip launches them.
+// fastq_parse.h -- the device FASTQ parser's kernels (fastq_parse.hip) as fastq_upload.hip launches them.
 #pragma once
 #include "fastq_record.h"
 

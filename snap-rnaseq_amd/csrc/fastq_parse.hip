@@ -1,6 +1,6 @@
 // fastq_parse.hip -- FASTQ text in device memory to a resident read batch (gfx950, wave64):
 //   1. fastq_count_kernel    '\n' bytes per tile of kTileBytes (SWAR compare, popcount, reduction)
-//   2. samgpu::scanStarts    the tiles' first newline ranks (aligner.hip queues it)
+//   2. samgpu::scanStarts    the tiles' first newline ranks (fastq_upload.hip queues it)
 //   3. fastq_lines_kernel    each tile rescans and stores its newline positions at their ranks
 //   4. fastq_record_kernel   fastq_record.h per record, a wave per record: trimmed line bounds, the
 //                            three lengths, Read::clip, the first record without '@' header (an

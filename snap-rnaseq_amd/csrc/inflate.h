@@ -1,4 +1,4 @@
-// inflate.h -- the device BGZF inflater's kernel (inflate.hip) as aligner.hip launches it.
+// inflate.h -- the device BGZF inflater's kernel (inflate.hip) as fastq_upload.hip launches it.
 #pragma once
 #include "inflate_block.h"
 

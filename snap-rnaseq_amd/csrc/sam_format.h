@@ -1,4 +1,4 @@
-// sam_format.h -- the device SAM formatter's kernels (sam_format.hip) as aligner.hip launches them.
+// sam_format.h -- the device SAM formatter's kernels (sam_format.hip) as output_chain.hip launches them.
 #pragma once
 #include "sam_line.h"
 

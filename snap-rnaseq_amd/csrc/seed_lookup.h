@@ -26,14 +26,8 @@
 
 namespace sgk {
 
-// 16 bytes per (read, seed k of the sequence, k < SEEDS_PER_READ)
-struct SeedRec {
-    uint32_t meta;      // bit31 valid, [7:0] offset, bit8 found, bit9 comp, bit10 palindrome, [30:16] probes
-    uint32_t v1, v2;    // slot values (GenomeIndex.cpp:1004-1010 swaps them when comp)
-    uint32_t cnt;       // overflow counts, u16 each, saturated: [15:0] value1 side, [31:16] value2 side
-};
-constexpr int SEEDS_PER_READ = 16;   // = lanes per read in seed_lookup_kernel: 4 reads per wave
-constexpr int LOOKUP_WAVES = 4;      // waves per seed_lookup_kernel block (16 reads)
+// SeedRec and SEEDS_PER_READ: align_device.h (the hosts that only size the record array need no kernel)
+constexpr int LOOKUP_WAVES = 4;     // waves per seed_lookup_kernel block (16 reads)
 
 // bits [p, p+len) of a 128-bit value (len <= 32)
 __device__ __forceinline__ uint32_t win128(uint64_t lo, uint64_t hi, int p, int len) {
