@@ -23,7 +23,8 @@
 //   samheader <indexDir> <sorted 0|1> <version> [args...]
 //          -> SAMFormat::writeHeader (SAM.cpp:700-800) for a FASTQ input (no input header),
 //             default read group, command line = args
-//   paired <indexDir> <reads0.fq> <reads1.fq> [maxHits maxK numSeeds extra minSpacing maxSpacing maxBigHits]
+//   paired <indexDir> <reads0.fq> <reads1.fq> [maxHits maxK numSeeds extra minSpacing maxSpacing maxBigHits
+//          [seedCoverage]]   (seedCoverage: used when numSeeds is 0; omitted = 0, as before)
 //          -> per pair: the IntersectingPairedEndAligner result alone, then the
 //             ChimericPairedEndAligner result, constructed as PairedAligner.cpp:462-482
 //             (paired defaults AlignerOptions.cpp:73-77: maxHits 16000, maxK 15, 8 seeds)
@@ -253,16 +254,19 @@ static int mode_paired(int argc, char **argv) {
     unsigned minSpacing = argc > 9 ? atoi(argv[9]) : 50;
     unsigned maxSpacing = argc > 10 ? atoi(argv[10]) : 1000;
     unsigned maxBigHits = argc > 11 ? atoi(argv[11]) : DEFAULT_INTERSECTING_ALIGNER_MAX_HITS;
+    // used when numSeeds is 0: seeds per pair = max(len0, len1) * seedCoverage / seedLen (:150-155), and
+    // the pool reservation is sized from it as the constructor sizes the pools (:51-57)
+    const double seedCoverage = argc > 12 ? atof(argv[12]) : 0;
     const unsigned pool = DEFAULT_MAX_CANDIDATE_POOL_SIZE;
     initializeLVProbabilitiesToPhredPlus33();
     GenomeIndex *idx = GenomeIndex::loadFromDirectory(argv[2]);
     if (!idx) { fprintf(stderr, "cannot load index %s\n", argv[2]); return 1; }
     const int maxReadSize = MAX_READ_LENGTH;
     BigAllocator *al = new BigAllocator(IntersectingPairedEndAligner::getBigAllocatorReservation(
-        idx, maxBigHits, maxReadSize, idx->getSeedLength(), numSeeds, 0, maxK, extra, pool));
-    IntersectingPairedEndAligner *ia = new IntersectingPairedEndAligner(idx, maxReadSize, maxHits, maxK, numSeeds, 0,
+        idx, maxBigHits, maxReadSize, idx->getSeedLength(), numSeeds, seedCoverage, maxK, extra, pool));
+    IntersectingPairedEndAligner *ia = new IntersectingPairedEndAligner(idx, maxReadSize, maxHits, maxK, numSeeds, seedCoverage,
                                                                        minSpacing, maxSpacing, maxBigHits, extra, pool, al);
-    ChimericPairedEndAligner *ca = new ChimericPairedEndAligner(idx, maxReadSize, maxHits, maxK, numSeeds, 0, minSpacing,
+    ChimericPairedEndAligner *ca = new ChimericPairedEndAligner(idx, maxReadSize, maxHits, maxK, numSeeds, seedCoverage, minSpacing,
                                                                maxSpacing, false, extra, ia);
     std::ifstream in0(argv[3]), in1(argv[4]);
     std::string id[2], bases[2], plus[2], quals[2];

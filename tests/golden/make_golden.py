@@ -23,6 +23,8 @@ TSV/JSON expected outputs.
     python3 tests/golden/make_golden.py --only-single-bench # digest + CPU rate of the reference on bench.py's single-end leg
     python3 tests/golden/make_golden.py --only-rna-bam   # `snap-rna paired ... -o out.bam` records (both RNA sets)
     python3 tests/golden/make_golden.py --only-rna-fs    # `snap-rna paired ... -fs` SAM records (2 x <=101 set)
+    python3 tests/golden/make_golden.py --only-paired-edges # paired runs on long / unequal mates, repeats, seeds 16 / 25
+    python3 tests/golden/make_golden.py --only-verylong  # single-end reads of 257..500 bases (align_kernel<512>)
 """
 import hashlib
 import json
@@ -1304,8 +1306,379 @@ def rna_fs_fixtures(work):
         json.dump({"block": RNA_BLOCK, "starts": starts, "records_differing_from_plain": plain_differs}, dst)
 
 
+EDGE_LENGTHS = (49, 50, 64, 128, 129, 192, 193, 256, 257, 320, 384, 448, 499, 500)
+_COMP = str.maketrans("ACGTN", "TGCAN")
+
+
+def _rc(x):
+    return x.translate(_COMP)[::-1]
+
+
+def _fasta_seqs(fa):
+    """contig name -> upper-cased sequence (IUPAC bytes kept, as FASTA.cpp:104-116 keeps them)."""
+    seqs, name = {}, None
+    for line in open(fa):
+        line = line.strip()
+        if line.startswith(">"):
+            name = line[1:].split()[0]
+            seqs[name] = []
+        else:
+            seqs[name].append(line.upper())
+    return {k: "".join(v) for k, v in seqs.items()}
+
+
+def _keep_gz(name, text):
+    """A fixture kept gzipped (tests/golden/<name>.gz; golden_common.golden_path unpacks it for the tests);
+    mtime 0: reproducible bytes."""
+    import gzip
+    with open(os.path.join(HERE, name + ".gz"), "wb") as f:
+        f.write(gzip.compress(text.encode(), compresslevel=9, mtime=0))
+
+
+def _write_pairs(work, stem, pairs, tag):
+    """<stem>_{1,2}.fq in `work` for the reference, gzipped into tests/golden."""
+    for k in (0, 1):
+        text = "".join(f"@{tag}{i}/{k + 1}\n{p[2 * k]}\n+\n{p[2 * k + 1]}\n" for i, p in enumerate(pairs))
+        with open(os.path.join(work, f"{stem}_{k + 1}.fq"), "w") as f:
+            f.write(text)
+        _keep_gz(f"{stem}_{k + 1}.fq", text)
+
+
+def _edge_mutate(s, rng):
+    """Substitutions and indels that scale with the length (scores span 0..maxK at every length); the
+    length is kept (an insertion drops the tail, a deletion appends random bases), so a 500-base mate
+    stays within the reference's MAX_READ_LENGTH."""
+    L, scale = len(s), 1 + len(s) // 128
+    s = list(s)
+    for _ in range(rng.choice([0, 0, 0, 1, 1, 2, 3, 5]) * scale):
+        s[rng.randrange(L)] = rng.choice("ACGT")
+    for _ in range(scale):
+        if rng.random() < 0.06 and L > 20:
+            j = rng.randrange(5, L - 5)
+            s = s[:j] + s[j + rng.randrange(1, 4):] if rng.random() < 0.5 else s[:j] + list("TGA"[:rng.randrange(1, 4)]) + s[j:]
+    s = s[:L] + [rng.choice("ACGT") for _ in range(L - len(s))]
+    return "".join(s)
+
+
+def paired_edge_long_reads(seqs, rng, n_pairs=360):
+    """The `long` pairs: paired_reads' mix (proper, overlapping, past maxSpacing, chimeric, one or both
+    mates random, N-rich, same-orientation) with each mate's length drawn on its own from EDGE_LENGTHS,
+    plus pairs laid over one of the genome's IUPAC bytes (forward strand, so the read carries the same
+    byte) and pairs within 500 bases of a contig's start or end.  -> (pairs, counts)."""
+    names = list(seqs)
+    iupac = [(c, i) for c in names for i, ch in enumerate(seqs[c]) if ch not in "ACGTN"]
+    counts = dict(end_lo=0, end_hi=0)
+
+    def rand_seq(L):
+        return "".join(rng.choice("ACGT") for _ in range(L))
+
+    def frag_at(c, pos, L0, L1, ins, flip):
+        f = seqs[c][pos:pos + ins]
+        assert len(f) == ins >= max(L0, L1)
+        if flip:
+            f = _rc(f)
+        return f[:L0], _rc(f[len(f) - L1:])
+
+    def frag_pair(L0, L1, ins):
+        c = rng.choice(names)
+        ins = max(ins, L0, L1)
+        return frag_at(c, rng.randrange(0, len(seqs[c]) - ins), L0, L1, ins, rng.random() < 0.5)
+
+    pairs = []
+    for i in range(n_pairs):
+        u = rng.random()
+        L0, L1 = rng.choice(EDGE_LENGTHS), rng.choice(EDGE_LENGTHS)
+        M = max(L0, L1)
+        if u < 0.44:
+            a, b = frag_pair(L0, L1, M + rng.randrange(0, 550))
+        elif u < 0.49:
+            a, b = frag_pair(L0, L1, M + rng.randrange(0, 40))               # mates overlap: within minSpacing
+        elif u < 0.53:
+            a, b = frag_pair(L0, L1, M + rng.randrange(1100, 4000))          # beyond maxSpacing
+        elif u < 0.60:
+            a, _ = frag_pair(L0, L1, M + 300)                                # chimeric
+            _, b = frag_pair(L0, L1, M + 300)
+        elif u < 0.65:
+            a, b = frag_pair(L0, L1, M + 300)
+            if rng.random() < 0.5:
+                a = rand_seq(L0)
+            else:
+                b = rand_seq(L1)
+        elif u < 0.70:
+            a, b = rand_seq(L0), rand_seq(L1)
+        elif u < 0.74:
+            a, b = frag_pair(L0, L1, M + 300)
+            a = "".join("N" if rng.random() < 0.08 else ch for ch in a)      # N-rich (> maxK Ns once long enough)
+        elif u < 0.78:
+            a, b = frag_pair(L0, L1, M + 300)
+            b = _rc(b)                                                       # same orientation
+        elif u < 0.90:   # over an IUPAC byte of the genome; half of them with both mates of 50..256 bases
+            if rng.random() < 0.5:
+                L0, L1 = (rng.choice([x for x in EDGE_LENGTHS if 50 <= x <= 256]) for _ in range(2))
+                M = max(L0, L1)
+            c, at = rng.choice(iupac)
+            ins = M + rng.randrange(0, 400)
+            pos = min(max(0, at - rng.randrange(0, L0)), len(seqs[c]) - ins)
+            a, b = frag_at(c, pos, L0, L1, ins, False)
+        else:            # within 500 bases of a contig's start / end
+            c = rng.choice(names)
+            ins = M + rng.randrange(0, 400)
+            lo = rng.random() < 0.5
+            pos = rng.randrange(0, 400) if lo else len(seqs[c]) - ins - rng.randrange(0, 400)
+            counts["end_lo" if lo else "end_hi"] += 1
+            a, b = frag_at(c, pos, L0, L1, ins, rng.random() < 0.5)
+        if rng.random() < 0.5:
+            a, b = b, a
+        a, b = _edge_mutate(a, rng), _edge_mutate(b, rng)
+        if rng.random() < 0.05:
+            a = a.lower()
+        qa, qb = ["I"] * len(a), ["I"] * len(b)
+        if rng.random() < 0.1:
+            qa = [rng.choice("#+5?I") for _ in a]
+        pairs.append((a, "".join(qa), b, "".join(qb)))
+    return pairs, counts
+
+
+def _edge_long_asserts(pairs, counts):
+    """The length classes and edge counts the `long` set promises, from the FASTQ text alone."""
+    L = [(len(a), len(b)) for a, _, b, _ in pairs]
+    mx = [max(x) for x in L]
+    assert sum(1 for m in mx if m <= 128) >= 20 and sum(1 for m in mx if 129 <= m <= 256) >= 20
+    assert sum(1 for m in mx if m >= 257) >= 20
+    assert sum(1 for x in L if min(x) <= 128 and max(x) > 256) >= 20
+    assert sum(1 for x in L if 500 in x) >= 10 and sum(1 for x in L if 49 in x) >= 10
+    assert sum(1 for x in L if x[0] != x[1] and min(x) >= 50) >= 200
+    assert sum(1 for x in L if max(x) < 50) >= 1                  # both mates short: written by no pass
+    other = lambda s: bool(set(s.upper()) - set("ACGTN"))
+    n_iupac = sum(1 for a, _, b, _ in pairs if other(a) or other(b))
+    assert n_iupac >= 15, n_iupac
+    # the routing rule for IUPAC pairs needs some with both mates of 50..256 bases
+    assert sum(1 for a, _, b, _ in pairs if (other(a) or other(b)) and 50 <= min(len(a), len(b)) and
+               max(len(a), len(b)) <= 256) >= 5
+    assert counts["end_lo"] >= 5 and counts["end_hi"] >= 5, counts
+
+
+def _ref_paired(idx, fq0, fq1, p):
+    args = [str(p[k]) for k in ("maxHits", "maxK", "numSeeds", "extra", "minSpacing", "maxSpacing", "maxBigHits")]
+    if "seedCoverage" in p:
+        args.append(repr(p["seedCoverage"]))
+    return run([HARNESS, "paired", idx, fq0, fq1] + args)
+
+
+def tandem_genome_and_pairs(rng):
+    """tandem.fa: one contig of random sequence holding one array of 300 copies of a 20-base unit, each
+    copy with 0..2 substitutions; 100-base mates inside the array, across its borders and in the flanks.
+    -> (sequence, pairs, per pair the larger count of a mate's first seed, either strand, within 3000
+    bases of the other mate)."""
+    flank, n_copies = 40000, 300
+    unit = "".join(rng.choice("ACGT") for _ in range(20))
+    copies = []
+    for _ in range(n_copies):
+        c = list(unit)
+        for _ in range(rng.choice([0, 0, 0, 0, 1, 2])):
+            j = rng.randrange(20)
+            c[j] = rng.choice([x for x in "ACGT" if x != c[j]])
+        copies.append("".join(c))
+    g = "".join(rng.choice("ACGT") for _ in range(flank)) + "".join(copies) + \
+        "".join(rng.choice("ACGT") for _ in range(flank))
+    A, B = flank, flank + 20 * n_copies
+
+    def count(seed, lo, hi):
+        w, n = g[max(0, lo):hi], 0
+        for s in {seed, _rc(seed)}:
+            at = w.find(s)
+            while at >= 0:
+                n += 1
+                at = w.find(s, at + 1)
+        return n
+
+    pairs, seen = [], []
+    for i in range(80):
+        if i < 40:      # both mates inside the array
+            ins = rng.randrange(150, 2900)
+            pos = rng.randrange(A, B - ins)
+        elif i < 68:    # one mate inside, one in a flank (up to maxSpacing away)
+            ins = rng.randrange(250, 2900)
+            pos = rng.randrange(A - ins + 100, A - 100 + 1) if i % 2 else rng.randrange(B - ins + 100, B - 100 + 1)
+        else:           # both in a flank
+            ins = rng.randrange(150, 700)
+            pos = rng.randrange(1000, A - 3000) if i % 2 else rng.randrange(B + 3000, len(g) - 1000)
+        f = g[pos:pos + ins]
+        flip = rng.random() < 0.5
+        pa, pb = (pos, pos + ins - 100)
+        a, b = f[:100], _rc(f[-100:])
+        if flip:
+            a, b, pa, pb = b, a, pb, pa
+        # the first seed of each mate as the genome holds it (the reads are mutated afterwards)
+        seen.append(max(count(a[:20], pb - 3000, pb + 3100), count(b[:20], pa - 3000, pa + 3100)))
+        mut = []
+        for s in (a, b):
+            s = list(s)
+            for _ in range(rng.choice([0, 0, 1, 2, 3])):
+                s[rng.randrange(20, 100)] = rng.choice("ACGT")
+            mut.append("".join(s))
+        pairs.append((mut[0], "I" * 100, mut[1], "I" * 100))
+    return g, pairs, seen
+
+
+def repeat_pairs(seqs, rng, n_pairs=120):
+    """Pairs of 100-base mates on repeat.fa (contigs: a 5,000-base random head, then 600 copies of a
+    150-base element 20..60 bases apart): both mates inside copies, or one inside a copy and one in the
+    head; inserts of 150..700."""
+    erng = random.Random(77)                                   # the element multihit_alias_fixtures drew
+    elem = "".join(erng.choice("ACGT") for _ in range(150))
+    starts = {}
+    for c, g in seqs.items():
+        st = []
+        for key, off in ((elem[:40], 0), (_rc(elem)[-40:], 110)):   # substitutions sit at 40, 75, 110 only
+            at = g.find(key)
+            while at >= 0:
+                st.append(at - off)
+                at = g.find(key, at + 1)
+        starts[c] = sorted(x for x in st if x >= 5000)
+        assert len(starts[c]) == 600, (c, len(starts[c]))
+    pairs = []
+    for i in range(n_pairs):
+        c = rng.choice(list(seqs))
+        g, st = seqs[c], starts[c]
+        if i % 3 < 2:   # both mates inside copies
+            while True:
+                j = rng.randrange(len(st))
+                k = rng.randrange(j, min(len(st), j + 4))
+                s, e = st[j] + rng.randrange(0, 50), st[k] + rng.randrange(100, 151)
+                if 150 <= e - s <= 700:
+                    break
+        else:           # one mate in the random head, its mate inside one of the first copies
+            while True:
+                e = st[rng.randrange(0, 3)] + rng.randrange(100, 151)
+                s = e - rng.randrange(150, 701)
+                if s + 100 <= 5000:
+                    break
+        f = g[s:e]
+        a, b = f[:100], _rc(f[-100:])
+        if rng.random() < 0.5:
+            a, b = b, a
+        mut = []
+        for x in (a, b):
+            x = list(x)
+            for _ in range(rng.choice([0, 0, 1, 2, 4])):
+                x[rng.randrange(100)] = rng.choice("ACGT")
+            mut.append("".join(x))
+        pairs.append((mut[0], "I" * 100, mut[1], "I" * 100))
+    return pairs
+
+
+def paired_edge_fixtures(work):
+    """The PAIRED_EDGE_SETS of golden_common.py (tests/test_paired_edges.py): reads of 257..500 bases
+    and mates of different lengths (`long`), more than 64 mates inside one spacing window (`tandem`),
+    pairs on the 1,800-copy repeat genome (`repeat`), seed lengths 16 and 25, and the seedCoverage seed
+    count (`coverage`), each through `ref_harness paired`.  Every promise the sets make (length classes,
+    IUPAC and contig-end pairs, outcome mix, seed occurrence counts, maxBigHits biting) is asserted here."""
+    from golden_common import PAIRED_EDGE_SETS, PAIRED_EDGE_FIRST, PAIRED_EDGE_MAXLEN
+    # --- the new inputs (kept gzipped: the `long` mates alone are 375 KB of text)
+    small = _fasta_seqs(os.path.join(HERE, "small.fa"))
+    pairs, counts = paired_edge_long_reads(small, random.Random(257))
+    _edge_long_asserts(pairs, counts)
+    _write_pairs(work, "paired_edge_long", pairs, "el")
+    # coverage: the long pairs with both mates <= 256 bases: at seedCoverage 2.0 none asks for more seeds
+    # than the reference's MAX_MAX_SEEDS (30, IntersectingPairedEndAligner.h:93: its lookup arrays)
+    cov = [p for p in pairs if max(len(p[0]), len(p[2])) <= PAIRED_EDGE_MAXLEN["coverage"]]
+    cp = PAIRED_EDGE_SETS["coverage"][3]
+    assert all(int(max(len(p[0]), len(p[2])) * cp["seedCoverage"] / 20) <= 30 for p in cov) and len(cov) >= 100
+    g, tp, seen = tandem_genome_and_pairs(random.Random(307))
+    fasta = ">tandem0\n" + "".join(g[i:i + 70] + "\n" for i in range(0, len(g), 70))
+    assert len(fasta) < 100_000
+    with open(os.path.join(work, "tandem.fa"), "w") as f:
+        f.write(fasta)
+    _keep_gz("tandem.fa", fasta)
+    # the scan for the lowest best-possible score walks the mates 64 per step: > 128 mates in one window
+    # make it three steps, 65..128 two
+    assert sum(1 for x in seen if x > 128) >= 20 and sum(1 for x in seen if 65 <= x <= 128) >= 10, sorted(seen)
+    _write_pairs(work, "paired_edge_tandem", tp, "et")
+    _write_pairs(work, "paired_edge_repeat", repeat_pairs(_fasta_seqs(os.path.join(HERE, "repeat.fa")), random.Random(1801)), "er")
+    # --- the reference's rows
+    idx_of, rows = {}, {}
+    for name, (fa, seed_len, stem, p) in PAIRED_EDGE_SETS.items():
+        key = (fa, seed_len)
+        if key not in idx_of:
+            idx_of[key] = os.path.join(work, f"eidx_{fa}_{seed_len}")
+            shutil.rmtree(idx_of[key], ignore_errors=True)
+            # the dense repeats need the larger overflow space (as multihit_alias_fixtures)
+            run([SNAP, "index", os.path.join(work if fa == "tandem.fa" else HERE, fa), idx_of[key], "-s", str(seed_len)] +
+                (["-O1000"] if fa != "small.fa" else []))
+        # the pairs of the set: all of <stem>_{1,2}.fq, its first pairs, or its pairs of bounded mate length
+        recs = [open(os.path.join(work if stem.startswith("paired_edge") else HERE, f"{stem}_{k}.fq")).read().splitlines()
+                for k in (1, 2)]
+        n = len(recs[0]) // 4
+        take = [i for i in range(min(n, PAIRED_EDGE_FIRST.get(name, n)))
+                if max(len(recs[0][4 * i + 1]), len(recs[1][4 * i + 1])) <= PAIRED_EDGE_MAXLEN.get(name, 500)]
+        if name == "coverage":
+            assert len(take) == len(cov)
+        fq = [os.path.join(work, f"set_{k}.fq") for k in (1, 2)]
+        for k in range(2):
+            with open(fq[k], "w") as f:
+                f.write("".join("\n".join(recs[k][4 * i:4 * i + 4]) + "\n" for i in take))
+        out = _ref_paired(idx_of[key], fq[0], fq[1], p)
+        rows[name] = out.splitlines()
+        # a pair the reference cannot complete (a soft exit) ends its output early
+        assert len(rows[name]) == len(take), f"{name}: the reference wrote {len(rows[name])} rows for {len(take)} pairs"
+        _keep_gz(f"expected_paired_edge_{name}.tsv", out)
+    chim = [r.split("\t")[12:25] for r in rows["long_default"]]
+    together = sum(1 for c in chim if c[10] == "1")
+    fallback = sum(1 for c in chim if c[10] == "0" and c[0] != "0")
+    untouched = sum(1 for c in chim if c[0] == "0" and c[1] == "0" and c[2] == str(0xFFFFFFFF))
+    assert together >= 100 and fallback >= 20 and untouched >= 10, (together, fallback, untouched)
+    differ = sum(1 for a, b in zip(rows["repeat_default"], rows["repeat_wide"]) if a != b)
+    assert differ >= 20, differ                                  # maxBigHits 64 biting
+    print("long/default: together", together, "fallback", fallback, "untouched", untouched,
+          "| repeat: wide differs from default on", differ, "pairs | tandem first-seed counts", sorted(seen))
+
+
+def verylong_fixtures(work):
+    """Single-end reads of 257..500 bases (align_kernel<512>, byte compares) on the small genome, built
+    as long_fixtures builds its reads: fixed lengths and a mixed-length tail, some lower-case, some with
+    N bases, with the reference's AlignRead outputs for three parameter sets."""
+    from golden_common import VERYLONG_SETS
+    fa = os.path.join(HERE, "small.fa")
+    g = snapgpu.Genome.from_fasta(fa, 500)
+    rd = []
+    for rl, cnt, seed in ((257, 30, 141), (300, 50, 142), (320, 30, 143), (384, 30, 144), (448, 30, 145),
+                          (499, 30, 146), (500, 40, 147)):
+        syn = snapgpu.Reads.synthetic(g, cnt, seed=seed, read_length=rl, random_read_fraction=0.02)
+        rd += [tuple(x.decode() for x in syn.get(i)) for i in range(syn.n)]
+    rng = random.Random(148)
+    syn = snapgpu.Reads.synthetic(g, 60, seed=149, read_length=500, random_read_fraction=0.02)
+    for i in range(syn.n):   # mixed lengths 257..500, some lower-case and N bases
+        b, q = (x.decode() for x in syn.get(i))
+        L = rng.randrange(257, 501)
+        b, q = list(b[:L]), q[:L]
+        for _ in range(rng.randrange(0, 3)):
+            b[rng.randrange(L)] = "N"
+        b = "".join(b)
+        if rng.random() < 0.1:
+            b = b.lower()
+        rd.append((b, q))
+    fq = os.path.join(work, "small_verylong_reads.fq")
+    write_fastq(fq, rd)
+    _keep_gz("small_verylong_reads.fq", open(fq).read())
+    idxdir = os.path.join(work, "small_idx_verylong")
+    ref_index(fa, idxdir)
+    for name in VERYLONG_SETS:
+        _keep_gz(f"expected_small_verylong_{name}.tsv", ref_align(idxdir, fq, PARAM_SETS[name]))
+
+
 def main():
     work = tempfile.mkdtemp(prefix="golden_")
+    if "--only-paired-edges" in sys.argv:
+        paired_edge_fixtures(work)
+        shutil.rmtree(work, ignore_errors=True)
+        print("paired edge fixtures written to", HERE)
+        return
+    if "--only-verylong" in sys.argv:
+        verylong_fixtures(work)
+        shutil.rmtree(work, ignore_errors=True)
+        print("257..500-base read fixtures written to", HERE)
+        return
     if "--only-bam" in sys.argv:
         bam_fixtures(work)
         shutil.rmtree(work, ignore_errors=True)

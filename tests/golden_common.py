@@ -59,5 +59,56 @@ PAIRED_RUNS = {
 }
 
 
+# Paired edge sets (tests/test_paired_edges.py, make_golden.py --only-paired-edges): name -> (genome
+# FASTA, seed length, FASTQ stem, paired parameters).  The pairs are <stem>_1.fq / <stem>_2.fq; the
+# reference's rows (`ref_harness paired`) are expected_paired_edge_<name>.tsv; the new files are kept
+# gzipped (golden_path below).  A "seedCoverage" in the
+# parameters goes with numSeeds 0 (seeds per pair = max(len0, len1) * seedCoverage / seedLen).
+_TANDEM = dict(PAIRED_RUNS["default"], maxSpacing=3000)
+_COVERAGE = dict(PAIRED_RUNS["default"], numSeeds=0, seedCoverage=2.0)
+PAIRED_EDGE_SETS = {
+    "long_default": ("small.fa", 20, "paired_edge_long", PAIRED_RUNS["default"]),
+    "long_wide": ("small.fa", 20, "paired_edge_long", PAIRED_RUNS["wide"]),
+    "tandem": ("tandem.fa", 20, "paired_edge_tandem", _TANDEM),
+    "repeat_default": ("repeat.fa", 20, "paired_edge_repeat", PAIRED_RUNS["default"]),
+    "repeat_wide": ("repeat.fa", 20, "paired_edge_repeat", PAIRED_RUNS["wide"]),
+    "seed16": ("small.fa", 16, "paired", PAIRED_RUNS["default"]),
+    "seed25": ("small.fa", 25, "paired", PAIRED_RUNS["default"]),
+    "coverage": ("small.fa", 20, "paired_edge_long", _COVERAGE),
+}
+# sets that take only the first pairs of their FASTQ files, or only the pairs with both mates of at most
+# this many bases (coverage: so that no pair asks for more than the reference's 30 seeds); the others take all
+PAIRED_EDGE_FIRST = {"seed16": 600, "seed25": 600}
+PAIRED_EDGE_MAXLEN = {"coverage": 256}
+
+# Single-end reads of 257..500 bases (tests/test_long_reads.py, make_golden.py --only-verylong):
+# small_verylong_reads.fq on small.fa, expected_small_verylong_<set>.tsv from `ref_harness align`.
+VERYLONG_SETS = ("default", "k20", "s4")
+
+_unpacked = None
+
+
+def golden_path(name):
+    """Path of the fixture tests/golden/<name>; one kept gzipped (<name>.gz) is unpacked once into a
+    directory that lasts as long as the process."""
+    import atexit
+    import gzip
+    import os
+    import shutil
+    import tempfile
+    global _unpacked
+    g = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+    if os.path.exists(os.path.join(g, name)):
+        return os.path.join(g, name)
+    if _unpacked is None:
+        _unpacked = tempfile.mkdtemp(prefix="golden_")
+        atexit.register(shutil.rmtree, _unpacked, ignore_errors=True)
+    out = os.path.join(_unpacked, name)
+    if not os.path.exists(out):
+        with open(out, "wb") as f:
+            f.write(gzip.decompress(open(os.path.join(g, name + ".gz"), "rb").read()))
+    return out
+
+
 def digest(text):
     return hashlib.sha256(text.encode()).hexdigest()

@@ -4,7 +4,9 @@ Fixtures (tests/golden/make_golden.py --only-long, from the reference built in o
 * small_long_reads.fq -- synthetic 150 / 250 / 129 / 256 bp reads and mixed lengths 129..256
   (some lower-case, some N bases) on tests/golden/small.fa, with the reference's AlignRead
   outputs for three parameter sets (expected_small_long_{default,k20,s4}.tsv);
-* lv_long_{fwd,rev}.tsv -- LandauVishkin<+-1> calls with patterns of 128..253 bases.
+* lv_long_{fwd,rev}.tsv -- LandauVishkin<+-1> calls with patterns of 128..253 bases;
+* small_verylong_reads.fq (--only-verylong) -- reads of 257..500 bases (align_kernel<512>, the byte-compare
+  pass) with the reference's outputs for the same three sets (expected_small_verylong_*.tsv).
 CPU tests pin the oracle to them; GPU tests run the product path (every read goes through
 pass 2, none reaches the byte-compare pass 3) and the 256-bit lv_group unit kernel."""
 import os
@@ -13,8 +15,8 @@ import numpy as np
 import pytest
 
 import snapgpu
-from golden_common import PARAM_SETS, params_to_aligner_kwargs
-from oracle_ffi import canonical_tsv, oracle_align, oracle_lv
+from golden_common import PARAM_SETS, VERYLONG_SETS, golden_path, params_to_aligner_kwargs
+from oracle_ffi import assert_no_corrupt_reads, canonical_tsv, oracle_align, oracle_lv
 
 G = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 SETS = ("default", "k20", "s4")
@@ -72,7 +74,46 @@ def test_oracle_lv_matches_reference_long_patterns(direction, fn):
             assert np.float64(gp).view(np.uint64) == np.float64(float.fromhex(prob)).view(np.uint64)
 
 
+# Reads of 257..500 bases (MAX_READ_LENGTH): small_verylong_reads.fq with the reference's AlignRead outputs
+# (make_golden.py --only-verylong).  Above 256 bases neither the restatement nor align_kernel<512> was pinned
+# to the reference before (test_front_stage.py compares 300-base reads with the restatement only).
+@pytest.fixture(scope="module")
+def verylong_reads():
+    return snapgpu.Reads.from_fastq(golden_path("small_verylong_reads.fq"))
+
+
+def test_verylong_fixture_shape(verylong_reads):
+    L = verylong_reads.lengths()
+    assert L.min() == 257 and L.max() == 500 and verylong_reads.n <= 300
+    for rl in (257, 300, 320, 384, 448, 499, 500):
+        assert (L == rl).sum() >= 30, rl
+    assert len(set(L.tolist())) > 40   # the mixed-length tail
+
+
+@pytest.mark.parametrize("name", VERYLONG_SETS)
+def test_oracle_matches_reference_verylong_reads(small_index, verylong_reads, name):
+    """The single-end side of 257..500 bases: the restatement equals the reference's rows."""
+    res = oracle_align(small_index, verylong_reads, _params(name), n_threads=4)
+    bad = _diff(canonical_tsv(res), open(golden_path(f"expected_small_verylong_{name}.tsv")).read())
+    assert not bad, f"{len(bad)} differ, first: {bad[:3]}"
+
+
 # ------------------------------------------------------------------------- GPU
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", VERYLONG_SETS)
+def test_gpu_verylong_reads_match_reference(gpu_available, small_index, verylong_reads, name):
+    """align_kernel<512> (byte compares) on reads of 257..500 bases equals the reference's rows; every read
+    leaves passes 1 and 2 and is a byte-path read."""
+    al = snapgpu.BaseAligner(small_index, **params_to_aligner_kwargs(PARAM_SETS[name]))
+    res = al.AlignReads(verylong_reads)
+    t = al.timing()
+    n = verylong_reads.n
+    assert t["nByteReads"] == n and t["nSpilled"] == n, t
+    assert_no_corrupt_reads(res)
+    bad = _diff(canonical_tsv(res), open(golden_path(f"expected_small_verylong_{name}.tsv")).read())
+    assert not bad, f"{len(bad)} differ, first: {bad[:3]}"
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", SETS)
 def test_gpu_long_reads_match_reference(gpu_available, small_index, long_reads, name):
