@@ -473,6 +473,10 @@ typedef struct snapgpu_grids {
     uint32_t perCUSimple, gridSimple;
     uint32_t perCUCigar, gridCigar;
     uint32_t lds128, ldsUnit, ldsPerCU, reserved;
+    /* registers a lane of seed_lookup_kernel (pass 0) and of the 128-base align kernel is allocated
+     * (hipFuncGetAttributes::numRegs rounded up to the allocation unit of 8): pass 0 runs beside the
+     * resident align kernel only while 5 * vgpr128 + vgprLookup <= 512, the SIMD's register file */
+    uint32_t vgprLookup, vgpr128;
 } snapgpu_grids_t;
 int snapgpu_aligner_debug_grids(snapgpu_aligner_t *a, snapgpu_grids_t *g);
 /* SHA-256 of the sources this library was built from (snapgpu/_srcsha.py: csrc, this header, the

@@ -3068,6 +3068,9 @@ int snapgpu_aligner_debug_grids(snapgpu_aligner_t *a, snapgpu_grids_t *g) {
     g->ldsUnit = (uint32_t)LDS_ALLOC_UNIT;
     g->ldsPerCU = (uint32_t)prop.maxSharedMemoryPerMultiProcessor;
     g->reserved = 0;
+    g->vgpr128 = ((uint32_t)fa.numRegs + 7u) & ~7u;
+    HIPCHK(hipFuncGetAttributes(&fa, (const void *)seed_lookup_kernel));
+    g->vgprLookup = ((uint32_t)fa.numRegs + 7u) & ~7u;
     return SNAPGPU_OK;
 }
 

@@ -27,7 +27,12 @@
 namespace sgk {
 
 // SeedRec and SEEDS_PER_READ: align_device.h (the hosts that only size the record array need no kernel)
-constexpr int LOOKUP_WAVES = 4;     // waves per seed_lookup_kernel block (16 reads)
+// One wave per seed_lookup_kernel block (4 reads), at no more than 32 VGPRs: beside five resident
+// align_kernel<128> waves at 96 VGPRs a SIMD has 512 - 5 * 96 = 32 registers and three wave slots
+// left, so pass 0 of the next chunk runs beside the body of the persistent kernel instead of waiting
+// for its tail, and a one-wave workgroup needs one free slot, not four on one CU (DESIGN.md
+// section 5, round 22; tools/gpu/coresident.hip).
+constexpr int LOOKUP_WAVES = 1;
 
 // bits [p, p+len) of a 128-bit value (len <= 32)
 __device__ __forceinline__ uint32_t win128(uint64_t lo, uint64_t hi, int p, int len) {
@@ -51,12 +56,13 @@ __device__ __forceinline__ uint64_t spread2(uint32_t x32) {
 // stats[4*slot + 0..2] += seeds looked up, hash entries probed, overflow counts read (roofline
 // bytes); slot = block % 256
 __global__ __launch_bounds__(64 * LOOKUP_WAVES) void seed_lookup_kernel(KArgs A, SeedRec *out, unsigned long long *stats) {
+    static_assert(LOOKUP_WAVES == 1, "wrapT is shared through wave_sync(): one wave per block");
     // the wrap table (GetWrappedNextSeedToTest order) in LDS: the walk below reads it per lane
     __shared__ uint32_t wrapT[32];
     if (threadIdx.x < 32) wrapT[threadIdx.x] = A.tab->wrap[threadIdx.x];
-    __syncthreads();
+    wave_sync();
     const int lane = lane_id();
-    const uint32_t r = (blockIdx.x * LOOKUP_WAVES + threadIdx.x / 64) * 4 + (lane >> 4);
+    const uint32_t r = blockIdx.x * 4 + (lane >> 4);
     const int k = lane & 15;
     const int sub = k & 7;          // lanes k < 8 load the read, 16 bases each
     const bool have = r < A.nReads;
@@ -64,7 +70,8 @@ __global__ __launch_bounds__(64 * LOOKUP_WAVES) void seed_lookup_kernel(KArgs A,
     const uint64_t off = have ? A.offsets[r] : 0;
     const int L = (int)A.seedLen;
     // 16 bases per lane (read buffer carries >= 64 bytes of slack past the last read)
-    uint64_t chunk = 0;   // [15:0] bit0 of the seed code, [31:16] bit1, [47:32] not-ACGT / past the end
+    uint32_t chunk = 0;   // [15:0] bit0 of the seed code, [31:16] bit1
+    uint32_t chunkIv = 0; // [15:0] not-ACGT / past the end
     bool bad = false;     // a base of the read (position < n) that is not ACGT
     {
         const uint64_t b0 = off + 16 * (uint64_t)sub;
@@ -98,62 +105,47 @@ __global__ __launch_bounds__(64 * LOOKUP_WAVES) void seed_lookup_kernel(KArgs A,
                 iv |= (inv ? 1u : 0u) << bit;
             }
         }
-        chunk = (uint64_t)p0 | ((uint64_t)p1 << 16) | ((uint64_t)iv << 32);
+        chunk = p0 | (p1 << 16);
+        chunkIv = iv;
+        // both words are final here: without this the compiler sinks the planes' arithmetic below the
+        // walk of the non-ACGT reads and carries the 16 unpacked bytes across it (5 VGPRs more)
+        asm volatile("" : "+v"(chunk), "+v"(chunkIv));
     }
     SeedRec rec = {0u, 0u, 0u, 0u};
     uint32_t weight = 0;   // a long read's seed: its hit count (0: popular or not found)
-    uint32_t nSeed = 0, nProbe = 0, nOvfRead = 0;
+    uint32_t nProbe = 0, nOvfRead = 0;
     const int grp = lane & ~15;
     const uint64_t badMask = ballot(bad);
     const bool can = have && (int)n >= L;
     const bool lng = n > 128;   // records: the first-round seeds inside positions 0..127 only
     const int firstRound = 128 / L;   // of a long read: offsets 0, L, .., (firstRound - 1) L (all-ACGT prefix)
     int my = -1;             // offset of this lane's seed k of the sequence (-1: none)
-    uint32_t w0 = 0, w1 = 0;   // code bits 0 and 1 of the seed's positions my .. my + L - 1
-    if (badMask == 0) {
-        // every read of the wave is all ACGT: its sequence of seed offsets depends on its length
-        // alone (a table entry), and a seed's bits come from the three chunks it can span
-        if (can && !lng) {
+    // an all-ACGT read's sequence of seed offsets depends on its length alone (a table entry)
+    const bool clean = ((badMask >> grp) & 0xffffull) == 0;
+    if (can && clean) {
+        if (lng) my = k < firstRound ? k * L : -1;
+        else {
             const uint32_t t = A.tab->seedSeq[n][k];
             my = t == 0xffu ? -1 : (int)t;
-        } else if (can) my = k < firstRound ? k * L : -1;
-        const int c0 = my > 0 ? my >> 4 : 0;
-        const uint32_t a = (uint32_t)shfl_idx((int)(uint32_t)chunk, grp + c0);
-        const uint32_t b = (uint32_t)shfl_idx((int)(uint32_t)chunk, grp + (c0 + 1 < 8 ? c0 + 1 : 7));
-        const uint32_t c = (uint32_t)shfl_idx((int)(uint32_t)chunk, grp + (c0 + 2 < 8 ? c0 + 2 : 7));
-        const uint64_t q0 = (uint64_t)(a & 0xffffu) | ((uint64_t)(b & 0xffffu) << 16) | ((uint64_t)(c & 0xffffu) << 32);
-        const uint64_t q1 = (uint64_t)(a >> 16) | ((uint64_t)(b >> 16) << 16) | ((uint64_t)(c >> 16) << 32);
-        const int sh = my > 0 ? my - 16 * c0 : 0;
-        const uint32_t M = (uint32_t)((1ull << L) - 1);
-        w0 = (uint32_t)(q0 >> sh) & M;
-        w1 = (uint32_t)(q1 >> sh) & M;
-    } else {
-        // the read's full 128-position planes in every lane of its group
-        uint64_t P0[2] = {0, 0}, P1[2] = {0, 0}, IV[2] = {0, 0};
+        }
+    }
+    if (badMask != 0) {
+        // a read of the wave has a non-ACGT base: its 128-position not-ACGT plane in every lane of its
+        // group (the planes of the code bits stay in the chunks; the seed's bits are fetched below)
+        uint64_t IV[2] = {0, 0};
 #pragma unroll
         for (int j = 0; j < 8; j++) {
-            const int src = grp + j;
-            const uint32_t lo = (uint32_t)shfl_idx((int)(uint32_t)chunk, src);
-            const uint32_t hi = (uint32_t)shfl_idx((int)(uint32_t)(chunk >> 32), src);
-            const int wd = j >> 2, s = 16 * (j & 3);
-            P0[wd] |= (uint64_t)(lo & 0xffff) << s;
-            P1[wd] |= (uint64_t)(lo >> 16) << s;
-            IV[wd] |= (uint64_t)(hi & 0xffff) << s;
+            const uint32_t hi = (uint32_t)shfl_idx((int)chunkIv, grp + j);
+            IV[j >> 2] |= (uint64_t)(hi & 0xffff) << (16 * (j & 3));
         }
-        const bool clean = ((badMask >> grp) & 0xffffull) == 0;
-        if (can) {
+        if (can && !clean) {
             // offset of the k-th seed of the sequence (BaseAligner.cpp:686-746), simulated with the
             // read's seedUsed bits: rounds 0, seedLen, ... then the wrap table's starts
             const int nPossible = (lng ? 128 : (int)n) - L + 1;
             uint64_t u0 = 0, u1 = 0;   // seedUsed, positions 0..127
             int p = 0, wrap = 0, idx = 0;
-            if (clean && lng) my = k < firstRound ? k * L : -1;
-            else if (clean) {
-                const uint32_t t = A.tab->seedSeq[n][k];
-                my = t == 0xffu ? -1 : (int)t;
-            }
 #pragma nounroll
-            for (int guard = 0; !clean && guard < 4 * 128; guard++) {   // each step marks, wraps or ends
+            for (int guard = 0; guard < 4 * 128; guard++) {   // each step marks, wraps or ends
                 if (p >= nPossible) {
                     if (lng || ++wrap >= L) break;               // wrapCount == seedLen: the read is scored
                     p = (int)wrapT[wrap];
@@ -167,8 +159,21 @@ __global__ __launch_bounds__(64 * LOOKUP_WAVES) void seed_lookup_kernel(KArgs A,
                 idx++;
                 p += L;
             }
-            if (my >= 0) { w0 = win128(P0[0], P0[1], my, L); w1 = win128(P1[0], P1[1], my, L); }
         }
+    }
+    uint32_t w0, w1;   // code bits 0 and 1 of the seed's positions my .. my + L - 1
+    {
+        // from the three chunks the seed can span (every lane of the wave takes part)
+        const int c0 = my > 0 ? my >> 4 : 0;
+        const uint32_t a = (uint32_t)shfl_idx((int)chunk, grp + c0);
+        const uint32_t b = (uint32_t)shfl_idx((int)chunk, grp + (c0 + 1 < 8 ? c0 + 1 : 7));
+        const uint32_t c = (uint32_t)shfl_idx((int)chunk, grp + (c0 + 2 < 8 ? c0 + 2 : 7));
+        const uint64_t q0 = (uint64_t)(a & 0xffffu) | ((uint64_t)(b & 0xffffu) << 16) | ((uint64_t)(c & 0xffffu) << 32);
+        const uint64_t q1 = (uint64_t)(a >> 16) | ((uint64_t)(b >> 16) << 16) | ((uint64_t)(c >> 16) << 32);
+        const int sh = my > 0 ? my - 16 * c0 : 0;
+        const uint32_t M = (uint32_t)((1ull << L) - 1);
+        w0 = (uint32_t)(q0 >> sh) & M;
+        w1 = (uint32_t)(q1 >> sh) & M;
     }
     {
         const uint32_t M = (uint32_t)((1ull << L) - 1);
@@ -177,6 +182,7 @@ __global__ __launch_bounds__(64 * LOOKUP_WAVES) void seed_lookup_kernel(KArgs A,
         const uint64_t f = (spread2(r1) << 1) | spread2(r0);
         const uint64_t rcv = (spread2(~w1 & M) << 1) | spread2(~w0 & M);
         const bool comp = (int64_t)f > (int64_t)rcv;
+        const bool pal = f == rcv;   // its own reverse complement (the two 64-bit codes are not kept across the lookup)
         const uint64_t canon = comp ? rcv : f;
         const uint32_t table = (uint32_t)(canon >> 32);
         const uint32_t key = (uint32_t)canon;
@@ -189,12 +195,11 @@ __global__ __launch_bounds__(64 * LOOKUP_WAVES) void seed_lookup_kernel(KArgs A,
             auto side = [&](uint32_t v, uint32_t c) -> uint32_t {
                 return v == UNUSED_SIDE ? 0u : v < A.nBases ? 1u : c >= BK_CSAT ? 0xffffu : c;
             };
-            const uint32_t h = side(v1, c1) + (f != rcv ? side(v2, c2) : 0u);
+            const uint32_t h = side(v1, c1) + (!pal ? side(v2, c2) : 0u);
             weight = h <= A.maxHits ? h : 0u;
         }
         if (my >= 0) {
             uint32_t cnt = 0;
-            nSeed = 1;
             nProbe = probes;
             if (found) {   // overflow list lengths (GenomeIndex.cpp:1013-1086), from the entry
                 const uint32_t c1 = aux & BK_CSAT, c2 = (aux >> 15) & BK_CSAT;
@@ -202,45 +207,49 @@ __global__ __launch_bounds__(64 * LOOKUP_WAVES) void seed_lookup_kernel(KArgs A,
                 const uint32_t nf = comp ? c2 : c1, nr = comp ? c1 : c2;
                 uint32_t cf = 0, cr = 0;
                 if (vf >= A.nBases && vf != UNUSED_SIDE) { cf = bucket_count(A, nf, vf); nOvfRead += nf >= BK_CSAT; }
-                if (f != rcv && vr >= A.nBases && vr != UNUSED_SIDE) { cr = bucket_count(A, nr, vr); nOvfRead += nr >= BK_CSAT; }
+                if (!pal && vr >= A.nBases && vr != UNUSED_SIDE) { cr = bucket_count(A, nr, vr); nOvfRead += nr >= BK_CSAT; }
                 cnt = (cf < 0xffffu ? cf : 0xffffu) | ((cr < 0xffffu ? cr : 0xffffu) << 16);
             }
             rec.meta = 0x80000000u | (uint32_t)my | (found ? 0x100u : 0u) | (comp ? 0x200u : 0u) |
-                       (f == rcv ? 0x400u : 0u) | ((probes < 0x7fffu ? probes : 0x7fffu) << 16);
+                       (pal ? 0x400u : 0u) | ((probes < 0x7fffu ? probes : 0x7fffu) << 16);
             rec.v1 = v1;
             rec.v2 = v2;
             rec.cnt = cnt;
         }
     }
-    if (have) out[(uint64_t)r * SEEDS_PER_READ + k] = rec;
+    // (lane, read and seed index derived again here: carried from the top they are three VGPRs that live
+    // across the whole kernel)
+    const int laneE = lane_id();
+    const uint32_t rE = blockIdx.x * 4 + (laneE >> 4);
+    if (rE < A.nReads) out[(uint64_t)rE * SEEDS_PER_READ + (laneE & 15)] = rec;
     // route the wave's long reads (lane 16j speaks for read j) onto pass 2's list, or with their
     // weight class onto the order list
     if (A.longCount) {
         const bool isLong = have && lng;
-        const uint64_t ml = ballot(k == 0 && isLong);
+        const uint64_t ml = ballot((laneE & 15) == 0 && isLong);
         if (ml) {
             uint32_t w = weight;   // the read's summed weight, in every lane of its 16
 #pragma unroll
             for (int s = 8; s >= 1; s >>= 1) w += (uint32_t)__shfl_xor((int)w, s, 64);
             uint32_t bl = 0;
-            if (lane == 0) {
+            if (laneE == 0) {
                 bl = atomicAdd(A.deferCount, (uint32_t)__popcll(ml));
                 atomicAdd(A.longCount, (uint32_t)__popcll(ml));
             }
             bl = (uint32_t)readlane((int)bl, 0);
-            const uint32_t at = bl + (uint32_t)__popcll(ml & ((1ull << lane) - 1));
-            if (k == 0 && isLong) {
-                if (A.orderTmp) A.orderTmp[at] = r | (order_class(w) << ORDER_CLASS_SHIFT);
-                else A.deferList[at] = r;
+            const uint32_t at = bl + (uint32_t)__popcll(ml & ((1ull << laneE) - 1));
+            if ((laneE & 15) == 0 && isLong) {
+                if (A.orderTmp) A.orderTmp[at] = rE | (order_class(w) << ORDER_CLASS_SHIFT);
+                else A.deferList[at] = rE;
             }
         }
     }
     if (stats) {
-        const uint32_t seeds = (uint32_t)__popcll(ballot(nSeed != 0));
+        const uint32_t seeds = (uint32_t)__popcll(ballot(my >= 0));
         const uint32_t ovf = (uint32_t)__popcll(ballot(nOvfRead >= 1)) + (uint32_t)__popcll(ballot(nOvfRead >= 2));
         const uint32_t probes = sum_reduce32(nProbe);
-        if (lane == 0) {   // 256 slot groups: no single-address atomic hot spot
-            unsigned long long *st = stats + 4 * ((blockIdx.x * LOOKUP_WAVES + threadIdx.x / 64) & 255);
+        if (laneE == 0) {   // 256 slot groups: no single-address atomic hot spot
+            unsigned long long *st = stats + 4 * (blockIdx.x & 255);
             atomicAdd(st + 0, (unsigned long long)seeds);
             atomicAdd(st + 1, (unsigned long long)probes);
             atomicAdd(st + 2, (unsigned long long)ovf);

@@ -237,7 +237,8 @@ assert C.sizeof(Result) == 64, C.sizeof(Result)
 class Grids(C.Structure):   # snapgpu_grids_t
     _fields_ = [(f, C.c_uint32) for f in (
         "computeUnits", "shortRows", "perCU128", "grid128", "perCU256", "grid256", "perCU512", "grid512",
-        "perCUSimple", "gridSimple", "perCUCigar", "gridCigar", "lds128", "ldsUnit", "ldsPerCU", "reserved")]
+        "perCUSimple", "gridSimple", "perCUCigar", "gridCigar", "lds128", "ldsUnit", "ldsPerCU", "reserved",
+        "vgprLookup", "vgpr128")]
 
 
 class BucketInfo(C.Structure):   # snapgpu_bucket_info_t
