@@ -1068,6 +1068,65 @@ snapgpu_aligner_t *snapgpu_paired_aligner_single(snapgpu_paired_aligner_t *pa);
  * SNAPGPU_PAIRED_GRID caps every grid. */
 int snapgpu_paired_aligner_debug_grids(const snapgpu_paired_aligner_t *pa, uint32_t out[8]);
 
+/* ------------------------------------------------------------ SAM text of read pairs
+ * The two lines of every pair as the paired writer prints them (SimpleReadWriter::writePair,
+ * ReadWriter.cpp:133-217, over SAMFormat::writeRead with a mate, SAM.cpp:914-973), without
+ * transcriptome CIGARs.  With locs[e] = location[e], or invalid where status[e] is SNAPGPU_NOT_FOUND,
+ * the end written first is end 1 when locs[0] > locs[1] and end 0 otherwise; output record 2q + w is
+ * the w-th written end of pair q (FLAG 0x40 for w = 0, 0x80 for w = 1).  "/1" and "/2" are dropped
+ * from the two ids as writePair does; the batches' own ids and clip state (snapgpu_reads_clip) are
+ * used.  The CIGAR arrays have 2n rows: row 2q + e is end e of pair q (editDistance -1 = "*"), as
+ * snapgpu_cigar_batch gives them for locs[e] and direction[e].  Size contract as snapgpu_sam_format.
+ * SNAPGPU_EINVAL for batches that differ in n or carry no ids, for a read whose unclipped length
+ * exceeds 1024 bases, and for nOps > SNAPGPU_CIGAR_MAX_OPS.  Runs the product path's line writer on the
+ * host threads. */
+int snapgpu_sam_format_pairs(const snapgpu_index_t *idx, const snapgpu_reads_t *reads0, const snapgpu_reads_t *reads1,
+                             const snapgpu_pair_result_t *results, const int32_t *editDistance, const uint32_t *nOps,
+                             const uint32_t *ops, const char *readGroup, char *out, uint64_t cap, uint64_t *used);
+/* The byte length of each of the 2n lines snapgpu_sam_format_pairs prints (lineLengths: 2n entries). */
+int snapgpu_sam_pair_line_lengths(const snapgpu_index_t *idx, const snapgpu_reads_t *reads0,
+                                  const snapgpu_reads_t *reads1, const snapgpu_pair_result_t *results,
+                                  const int32_t *editDistance, const uint32_t *nOps, const uint32_t *ops,
+                                  const char *readGroup, uint32_t *lineLengths);
+/* The same text made on the device from the pair batch the last snapgpu_paired_align_batch /
+ * snapgpu_paired_intersect_batch left resident (both ends' bases and qualities stay in device
+ * memory until the next of those calls, which makes the CIGARs and the text below stale).
+ *
+ * snapgpu_paired_cigar_resident: uploads the caller's final pair records (after the chimeric
+ * fallback; 64 bytes per pair) and queues the CIGAR kernel for both ends at locs[e] and
+ * direction[e] over the resident bases; the reads are not uploaded again.  useM: 'M' for '=' and 'X'.
+ * `results` must hold one record for every pair of the resident batch (the call takes no count).  A read
+ * over 512 bases would get edit distance -1 and CIGAR "*" here, where snapgpu_cigar_batch refuses it;
+ * the pair kernels refuse such reads before a batch is resident.
+ * snapgpu_paired_cigar_download waits and reads back the 2n rows (ops: 2n * SNAPGPU_CIGAR_MAX_OPS).
+ *
+ * snapgpu_paired_sam_resident: uploads the batches' ids and clip state and queues the formatter
+ * over the 2n records with the uploaded records and the CIGAR rows on the device.  SNAPGPU_EINVAL
+ * with no batch resident, with no snapgpu_paired_cigar_resident behind it, and for batches that
+ * differ from the resident one in n, totalBytes or lengths.  snapgpu_paired_sam_download waits and
+ * copies the text out (size contract as snapgpu_sam_format; SNAPGPU_EDEVICE if a line does not end
+ * where the length pass placed it).  snapgpu_paired_sam_last_ms: the CIGAR pass and the formatter's
+ * kernels between HIP events, and the download's wall time, of the last calls.
+ *
+ * Everything is queued on the paired aligner's stream: the next align call's copies wait for it. */
+/* Pairs of the resident batch, 0 when there is none: the records snapgpu_paired_cigar_resident reads, half the
+ * rows snapgpu_paired_cigar_download writes. */
+uint64_t snapgpu_paired_resident_pairs(const snapgpu_paired_aligner_t *pa);
+int snapgpu_paired_cigar_resident(snapgpu_paired_aligner_t *pa, const snapgpu_pair_result_t *results, int useM);
+int snapgpu_paired_cigar_download(snapgpu_paired_aligner_t *pa, int32_t *editDistance, uint32_t *nOps, uint32_t *ops);
+int snapgpu_paired_sam_resident(snapgpu_paired_aligner_t *pa, const snapgpu_reads_t *reads0,
+                                const snapgpu_reads_t *reads1, const char *readGroup);
+int snapgpu_paired_sam_download(snapgpu_paired_aligner_t *pa, char *out, uint64_t cap, uint64_t *used);
+int snapgpu_paired_sam_last_ms(snapgpu_paired_aligner_t *pa, double *cigarMs, double *kernelMs, double *downloadMs);
+/* The batch form: snapgpu_sam_format_pairs's arguments (idx: the paired aligner's index, or NULL)
+ * uploaded, formatted by the same kernels and downloaded.  Byte-identical to snapgpu_sam_format_pairs.
+ * It leaves the resident batch and its CIGAR rows alone; a resident text has to be made again. */
+int snapgpu_sam_format_pairs_gpu(snapgpu_paired_aligner_t *pa, const snapgpu_index_t *idx,
+                                 const snapgpu_reads_t *reads0, const snapgpu_reads_t *reads1,
+                                 const snapgpu_pair_result_t *results, const int32_t *editDistance,
+                                 const uint32_t *nOps, const uint32_t *ops, const char *readGroup, char *out,
+                                 uint64_t cap, uint64_t *used);
+
 /* ------------------------------------------- RNA seed census
  * BaseAligner::CharacterizeSeeds (BaseAligner.cpp:206-508) on the GPU: the seeds of AlignRead's
  * order until numSeeds directions applied (or the wrap runs out), every hit of a side that is

@@ -3086,6 +3086,29 @@ static int cigar_kernel_launch(snapgpu_aligner_t *a, const CigarArgs &C, uint64_
     return SNAPGPU_OK;
 }
 
+int snapgpu_internal_cigar_device(snapgpu_aligner_t *a, hipStream_t st, const char *dBases, const uint64_t *dOffsets, const uint32_t *dLengths,
+                uint64_t n, const uint32_t *dLocations, const uint8_t *dDirections, int useM, int32_t *dEd, uint32_t *dNOps,
+                uint32_t *dOps) {
+    if (a->failed) { snapgpu::setError("aligner failed earlier (device timeout)"); return SNAPGPU_EDEVICE; }
+    if (n > 0xffffffffull) { snapgpu::setError("batch too large"); return SNAPGPU_EINVAL; }
+    if (int rc = cigar_grid(a)) return rc;
+    CigarArgs C;
+    memset(&C, 0, sizeof(C));
+    const snapgpu_index_t *idx = a->idx;
+    C.genome = a->dGenome; C.pieces = a->dPieces; C.nPieces = (int32_t)idx->genome->pieceOffsets.size();
+    C.nBases = idx->genome->nBases; C.padding = idx->genome->chromosomePadding;
+    C.bases = dBases; C.offsets = dOffsets; C.lengths = dLengths; C.nReads = (uint32_t)n;
+    C.locations = dLocations; C.directions = dDirections;
+    C.useM = useM ? 1 : 0;
+    C.outEd = dEd; C.outNOps = dNOps; C.outOps = dOps;
+    int grid = a->cigarGrid;
+    if ((uint64_t)grid > n) grid = (int)n;
+    if (grid == 0) return SNAPGPU_OK;
+    hipLaunchKernelGGL(cigar_kernel, dim3(grid), dim3(64), 0, st, C);
+    HIPCHK(hipGetLastError());
+    return SNAPGPU_OK;
+}
+
 static int cigar_launch(snapgpu_aligner_t *a, snapgpu_device_reads_t *d, CigarArgs C) {
     if (d->maxLen > (uint32_t)CIG_MAXLEN) { snapgpu::setError("cigar: read longer than 512 bases"); return SNAPGPU_EINVAL; }
     if (d->n > 0xffffffffull) { snapgpu::setError("batch too large"); return SNAPGPU_EINVAL; }

@@ -2,8 +2,9 @@
 // behind snapgpu_aligner_t and snapgpu_device_reads_t, the grow-only device buffer, the base of the
 // output chain's stage states, and the host helpers every entry point uses.  Included by aligner.hip
 // (the align kernels, the pass scheduler, create / free), output_chain.hip (SAM, BAM, duplicate
-// marking, BGZF, BAI) and fastq_upload.hip (FASTQ parse, BGZF inflate); everything else goes
-// through the snapgpu_internal_* accessors (internal.h).
+// marking, BGZF, BAI), fastq_upload.hip (FASTQ parse, BGZF inflate) and paired_output.hip (the paired
+// aligner's CIGARs and SAM text); everything else goes through the snapgpu_internal_* accessors
+// (internal.h).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -374,6 +375,12 @@ int waitEvent(snapgpu_aligner_t *a, hipEvent_t ev);
 int waitLane(snapgpu_aligner_t *a, ExecLane &L);
 // running hash of a batch's (offset, length) pairs
 uint64_t extentMix(uint64_t h, uint64_t off, uint32_t len);
+// cigar_kernel over n reads that are in device memory already (read r = dBases[dOffsets[r] .. +
+// dLengths[r]), at explicit locations and directions, into device rows, queued on st (the caller's
+// stream and timing; a's genome upload and CIGAR grid).  Reads over 512 bases get edit distance -1.
+extern "C" int snapgpu_internal_cigar_device(snapgpu_aligner_t *a, hipStream_t st, const char *dBases, const uint64_t *dOffsets, const uint32_t *dLengths,
+                uint64_t n, const uint32_t *dLocations, const uint8_t *dDirections, int useM, int32_t *dEd, uint32_t *dNOps,
+                uint32_t *dOps);
 
 // ---- defined in output_chain.hip
 // S's buffers and events back to the runtime (neither once the aligner has failed).

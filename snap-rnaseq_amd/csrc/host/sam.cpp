@@ -7,6 +7,7 @@
 // are formatted in parallel chunks and concatenated in read order.
 #include "internal.h"
 #include "sam_line.h"
+#include "sam_pair_line.h"
 #include "fastq_record.h"
 
 #include <algorithm>
@@ -629,5 +630,218 @@ extern "C" int snapgpu_sam_sort_records(const snapgpu_index_t *idx, const char *
     if (cap < n) return SNAPGPU_EINVAL;
     const std::string sorted = samSortRecords(*idx->genome, std::vector<std::string>{std::string(in, n)});
     memcpy(out, sorted.data(), sorted.size());
+    return SNAPGPU_OK;
+}
+
+// ------------------------------------------------------------------ pair batches (sam_pair_line.h)
+namespace {
+
+struct HostPairLines {
+    samline::PairArgs A;
+    std::vector<uint32_t> nameOff;
+    std::string names;
+};
+
+// The pair formatters' input check and their arguments as sam_pair_line.h takes them: the batches'
+// own ids and clip state, 2n CIGAR rows.
+int hostPairArgs(HostPairLines &H, const char *who, const snapgpu_index_t *idx, const snapgpu_reads_t *reads0,
+                 const snapgpu_reads_t *reads1, const snapgpu_pair_result_t *results, const int32_t *editDistance,
+                 const uint32_t *nOps, const uint32_t *ops, const char *readGroup) {
+    if (!idx || !idx->genome || !reads0 || !reads1) {
+        setError(std::string(who) + ": null argument");
+        return SNAPGPU_EINVAL;
+    }
+    if (reads0->n != reads1->n) {
+        setError(std::string(who) + ": the two read batches differ in length");
+        return SNAPGPU_EINVAL;
+    }
+    const uint64_t n = reads0->n;
+    if (n && (!results || !editDistance || !nOps || !ops)) {
+        setError(std::string(who) + ": null argument");
+        return SNAPGPU_EINVAL;
+    }
+    const snapgpu_reads_t *R[2] = {reads0, reads1};
+    const Genome &g = *idx->genome;
+    samPieceNames(g, H.nameOff, H.names);
+    samline::PairArgs &A = H.A;
+    memset(&A, 0, sizeof(A));
+    for (int e = 0; e < 2; e++) {
+        if (n && (!R[e]->ids || !R[e]->idOffsets || !R[e]->idLengths)) {
+            setError(std::string(who) + ": a read batch carries no ids");
+            return SNAPGPU_EINVAL;
+        }
+        const uint32_t *front = nullptr, *unclipped = nullptr;
+        if (int rc = samCheckClips(R[e], nullptr, &front, &unclipped)) return rc;
+        A.bases[e] = R[e]->bases; A.quals[e] = R[e]->quals;
+        A.offsets[e] = R[e]->offsets; A.lengths[e] = R[e]->lengths;
+        A.front[e] = front; A.unclipped[e] = unclipped;
+        A.ids[e] = R[e]->ids; A.idOffsets[e] = R[e]->idOffsets; A.idLengths[e] = R[e]->idLengths;
+    }
+    for (uint64_t i = 0; i < 2 * n; i++)
+        if (nOps[i] > SNAPGPU_CIGAR_MAX_OPS) {
+            setError("sam_format: nOps > SNAPGPU_CIGAR_MAX_OPS, read longer than 1024 bases or bad clip arrays");
+            return SNAPGPU_EINVAL;
+        }
+    A.res = results;
+    A.ed = editDistance; A.nOps = nOps; A.ops = ops;
+    A.rowPair = 2; A.rowEnd = 1;
+    A.pieceOffsets = g.pieceOffsets.data();
+    A.pieceNameOff = H.nameOff.data();
+    A.pieceNames = H.names.data();
+    A.nPieces = (int32_t)g.pieceOffsets.size();
+    A.rgLen = readGroup ? (uint32_t)strlen(readGroup) : 0u;
+    A.rg = readGroup;
+    return SNAPGPU_OK;
+}
+
+// f(t, a, b) for thread t's records [a, b) of 2n, whole pairs each
+template <class F>
+void pairThreads(uint64_t nPairs, F f) {
+    unsigned nt = std::min(hostThreads(16), 64u);
+    if (nPairs < 4096) nt = 1;
+    std::vector<std::thread> th;
+    for (unsigned t = 1; t < nt; t++) th.emplace_back([=] { f(t, 2 * (nPairs * t / nt), 2 * (nPairs * (t + 1) / nt)); });
+    f(0u, (uint64_t)0, 2 * (nPairs / nt));
+    for (auto &x : th) x.join();
+}
+
+}  // namespace
+
+// sam_pair_line.h's length of the 2n lines, on the host (what the device length pass computes)
+extern "C" int snapgpu_sam_pair_line_lengths(const snapgpu_index_t *idx, const snapgpu_reads_t *reads0,
+                                             const snapgpu_reads_t *reads1, const snapgpu_pair_result_t *results,
+                                             const int32_t *editDistance, const uint32_t *nOps, const uint32_t *ops,
+                                             const char *readGroup, uint32_t *lineLengths) {
+    HostPairLines H;
+    if (int rc = hostPairArgs(H, "sam_pair_line_lengths", idx, reads0, reads1, results, editDistance, nOps, ops, readGroup))
+        return rc;
+    if (!lineLengths && reads0->n) {
+        setError("sam_pair_line_lengths: null argument");
+        return SNAPGPU_EINVAL;
+    }
+    const samline::PairArgs &A = H.A;
+    pairThreads(reads0->n, [&A, lineLengths](unsigned, uint64_t a, uint64_t b) {
+        const samline::Serial g{nullptr};
+        for (uint64_t j = a; j < b; j++) lineLengths[j] = samline::pairLineLength(A, samline::pairFields(A, j, g));
+    });
+    return SNAPGPU_OK;
+}
+
+// The two lines of pair q through samAppendLine with SamLine::hasMate, filled as host/rna_paired.cpp's
+// record loop fills it (without transcriptome CIGARs).
+static void appendPair(std::string &o, const Genome &gg, const samline::PairArgs &A, uint64_t q) {
+    const snapgpu_pair_result_t &r = A.res[q];
+    uint32_t idLen[2] = {A.idLengths[0][q], A.idLengths[1][q]};
+    const char *id[2] = {A.ids[0] + A.idOffsets[0][q], A.ids[1] + A.idOffsets[1][q]};
+    if (idLen[0] == idLen[1] && idLen[0] > 2 && id[0][idLen[0] - 2] == '/' && id[1][idLen[0] - 2] == '/') {
+        const char c0 = id[0][idLen[0] - 1], c1 = id[1][idLen[1] - 1];
+        if ((c0 == '1' || c0 == '2') && (c0 == '1' || c1 == '2') && c0 != c1) { idLen[0] -= 2; idLen[1] -= 2; }
+    }
+    uint32_t locs[2];
+    for (int k = 0; k < 2; k++) locs[k] = r.status[k] != SNAPGPU_NOT_FOUND ? r.location[k] : kInvalidLocation;
+    const int first = locs[0] > locs[1], second = 1 - first;
+    for (int w = 0; w < 2; w++) {
+        const int k = w == 0 ? first : second, m = 1 - k;
+        SamLine L;
+        L.id = id[k];
+        L.idLen = A.idLengths[k][q];
+        L.qnameLen = idLen[k];
+        L.front = A.front[k] ? A.front[k][q] : 0u;
+        L.clippedLen = A.lengths[k][q];
+        L.fullLen = A.unclipped[k] ? A.unclipped[k][q] : L.clippedLen;
+        L.bases = A.bases[k] + A.offsets[k][q] - L.front;
+        L.quals = A.quals[k] + A.offsets[k][q] - L.front;
+        L.rg = A.rg;
+        L.result = r.status[k];
+        L.loc = locs[k];
+        L.dir = r.direction[k];
+        L.mapq = r.mapq[k];
+        L.ed = A.ed[2 * q + k];
+        L.ops = A.ops + (2 * q + k) * SNAPGPU_CIGAR_MAX_OPS;
+        L.nOps = A.nOps[2 * q + k];
+        L.hasMate = true;
+        L.firstInPair = w == 0;
+        L.mateLoc = locs[m];
+        L.mateDir = r.direction[m];
+        L.mateFront = A.front[m] ? A.front[m][q] : 0u;
+        L.mateClippedLen = A.lengths[m][q];
+        L.mateFullLen = A.unclipped[m] ? A.unclipped[m][q] : L.mateClippedLen;
+        samAppendLine(o, gg, L);
+    }
+}
+
+// The product path's line writer on the host threads: each formats its share of the pairs into a
+// part, and copies its part out (as snapgpu_sam_format_clipped does for reads without mate).
+extern "C" int snapgpu_sam_format_pairs(const snapgpu_index_t *idx, const snapgpu_reads_t *reads0,
+                                        const snapgpu_reads_t *reads1, const snapgpu_pair_result_t *results,
+                                        const int32_t *editDistance, const uint32_t *nOps, const uint32_t *ops,
+                                        const char *readGroup, char *out, uint64_t cap, uint64_t *used) {
+    if (!used) {
+        setError("sam_format_pairs: null argument");
+        return SNAPGPU_EINVAL;
+    }
+    *used = 0;
+    HostPairLines H;
+    if (int rc = hostPairArgs(H, "sam_format_pairs", idx, reads0, reads1, results, editDistance, nOps, ops, readGroup))
+        return rc;
+    const samline::PairArgs &A = H.A;
+    const Genome &gg = *idx->genome;
+    const uint64_t n = reads0->n;
+    std::vector<std::string> parts(64);
+    pairThreads(n, [&](unsigned t, uint64_t a, uint64_t b) {
+        std::string o;   // a local string, swapped in at the end (the parts' headers share cache lines)
+        o.reserve((b - a) * 320);
+        for (uint64_t q = a / 2; q < b / 2; q++) appendPair(o, gg, A, q);
+        parts[t].swap(o);
+    });
+    std::vector<uint64_t> at(parts.size() + 1, 0);
+    for (size_t t = 0; t < parts.size(); t++) at[t + 1] = at[t] + parts[t].size();
+    const uint64_t total = at.back();
+    *used = total;
+    if (total > cap || (!out && total)) {
+        setError("sam_format_pairs: output buffer too small");
+        return SNAPGPU_EINVAL;
+    }
+    pairThreads(n, [&](unsigned t, uint64_t, uint64_t) {
+        if (!parts[t].empty()) memcpy(out + at[t], parts[t].data(), parts[t].size());
+        std::string().swap(parts[t]);
+    });
+    return SNAPGPU_OK;
+}
+
+// sam_pair_line.h's writer on one host thread (the code the device write pass runs per wave), for
+// tests that need no GPU.  Same size contract.
+extern "C" int snapgpu_internal_sam_pair_line_write(const snapgpu_index_t *idx, const snapgpu_reads_t *reads0,
+                                                    const snapgpu_reads_t *reads1, const snapgpu_pair_result_t *results,
+                                                    const int32_t *editDistance, const uint32_t *nOps,
+                                                    const uint32_t *ops, const char *readGroup, char *out, uint64_t cap,
+                                                    uint64_t *used) {
+    if (!used) return SNAPGPU_EINVAL;
+    *used = 0;
+    HostPairLines H;
+    if (int rc = hostPairArgs(H, "sam_pair_line_write", idx, reads0, reads1, results, editDistance, nOps, ops, readGroup))
+        return rc;
+    const samline::PairArgs &A = H.A;
+    const uint64_t recs = 2 * reads0->n;
+    const samline::Serial none{nullptr};
+    std::vector<uint32_t> len(recs + 1);
+    std::vector<samline::Scans> scans(recs + 1);   // what the length pass scanned, for the write pass (as on the device)
+    uint64_t total = 0;
+    for (uint64_t j = 0; j < recs; j++) {
+        const samline::PairFields P = samline::pairFields(A, j, none);
+        total += len[j] = samline::pairLineLength(A, P);
+        scans[j] = samline::Scans{P.F.qlen, (uint16_t)P.F.seqLen, (uint16_t)P.F.qualLen};
+    }
+    *used = total;
+    if (total > cap || (!out && total)) {
+        setError("sam_pair_line_write: output buffer too small");
+        return SNAPGPU_EINVAL;
+    }
+    const samline::Serial g{out};
+    uint64_t at = 0;
+    for (uint64_t j = 0; j < recs; j++) {
+        samline::pairWrite(A, j, samline::pairFields(A, j, g, &scans[j]), at, g);
+        at += len[j];
+    }
     return SNAPGPU_OK;
 }

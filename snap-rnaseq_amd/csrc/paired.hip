@@ -35,6 +35,7 @@
 #include "bucket_table.h"
 #include "order_long.h"
 #include "internal.h"
+#include "paired_state.h"
 #include "resident_grid.h"
 
 int snapgpu_internal_index_args(const snapgpu_aligner_t *a, sgk::KArgs *A, int *device);
@@ -915,37 +916,7 @@ hipError_t ensurePairedTables(int device) {   // this translation unit's g_tab (
     return e;
 }
 
-struct PassPool {
-    char *pool = nullptr;
-    uint64_t stride = 0;
-    int grid = 0;
-    uint32_t candCap = 0, mateCap = 0, anchorCap = 0;
-};
-
 }  // namespace
-
-struct snapgpu_paired_aligner {
-    int device = 0;
-    snapgpu_paired_params_t p{};
-    snapgpu_aligner_t *single = nullptr;   // the chimeric fallback's BaseAligner; owns the index upload
-    KArgs X{};
-    hipStream_t stream = nullptr;
-    PassPool pass[3];                      // [0] passes 1 and 1b, [1] pass 3 (the reference's pools), [2] pass 2
-    int grid256 = 0;                       // pass 1b (<256>) grid: at most pass[0].grid (its pools)
-    int computeUnits = 0, perCU[3] = {};   // resident workgroups per CU of paired_kernel<128> / <256> / <512>: the grids' source
-    uint32_t refPool = 0, maxSeedsCmd = 0;
-    uint32_t *dCounter = nullptr;          // [0] pass 1 queue, [1] pass 3 queue, [2] pass-1 defer count,
-                                           // [3] pass 2 queue, [4] pass-2 defer count, [5] pass 1b queue,
-                                           // [6] pass-1b defer count
-    uint32_t *dDefer = nullptr, *dDefer2 = nullptr;
-    uint32_t *dOrder = nullptr, *dOrderW = nullptr;   // long pairs before / after pair_weight_kernel
-    bool orderLong = true;                 // pass 1b longest-first (SNAPGPU_ORDER_LONG=0: input order)
-    snapgpu_pair_result_t *dOut = nullptr;
-    char *dB[2] = {}, *dQ[2] = {};
-    uint64_t *dO[2] = {};
-    uint32_t *dL[2] = {};
-    uint64_t capPairs = 0, capBytes[2] = {0, 0};
-};
 
 static void pfree(void *p) { if (p) (void)hipFree(p); }
 
@@ -999,6 +970,7 @@ static int runIntersect(snapgpu_paired_aligner_t *pa, const snapgpu_reads_t *r0,
     const snapgpu_reads_t *R[2] = {r0, r1};
     const uint64_t n = r0->n;
     uint64_t bytes[2] = {r0->totalBytes, r1->totalBytes};
+    pairedOutputStale(pa);   // the reads the earlier batch's CIGARs and text were made from go
     int rc = ensurePairCapacity(pa, n, bytes);
     if (rc) return rc;
     hipStream_t s = pa->stream;
@@ -1120,6 +1092,8 @@ static int runIntersect(snapgpu_paired_aligner_t *pa, const snapgpu_reads_t *r0,
                                   : "paired: scoring candidate pool exhausted (the reference exits; raise maxCandidatePoolSize)");
             return SNAPGPU_EINVAL;
         }
+    pa->residentN = n;   // both ends' reads stay in dB / dQ / dO / dL for paired_output.hip
+    pa->residentBytes[0] = bytes[0]; pa->residentBytes[1] = bytes[1];
     return SNAPGPU_OK;
 }
 
@@ -1229,6 +1203,7 @@ void snapgpu_paired_aligner_free(snapgpu_paired_aligner_t *pa) {
     } else {
         (void)hipSetDevice(pa->device);
         if (pa->stream) (void)hipStreamSynchronize(pa->stream);
+        pairedOutputFree(pa);
         pfree(pa->dCounter); pfree(pa->dDefer); pfree(pa->dDefer2); pfree(pa->dOrder); pfree(pa->dOrderW); pfree(pa->dOut);
         for (int r = 0; r < 2; r++) { pfree(pa->dB[r]); pfree(pa->dQ[r]); pfree(pa->dO[r]); pfree(pa->dL[r]); }
         for (auto &pp : pa->pass) pfree(pp.pool);

@@ -774,6 +774,62 @@ class PairedAligner:
         names = ("computeUnits", "perCU128", "grid128", "perCU256", "grid256", "perCU512", "grid512", "gridPools")
         return dict(zip(names, (int(v) for v in out)))
 
+    # the resident pair batch: what the last align() / intersect() left in HBM
+    def resident_pairs(self):
+        """Pairs of the batch the aligner's last intersecting run left resident (0: none)."""
+        return int(lib().snapgpu_paired_resident_pairs(self._h))
+
+    def run_cigars(self, results, useM=False):
+        """CIGARs of both ends of the resident batch at the locations and directions of `results`
+        (the caller's final records of that batch), over the bases already in HBM (asynchronous)."""
+        res = np.ascontiguousarray(results, dtype=PAIR_RESULT_DTYPE)
+        n = self.resident_pairs()
+        if n and res.shape != (n,):   # the C call takes no count: it reads one record per resident pair
+            raise ValueError(f"results has shape {res.shape} for the {n} pairs of the resident batch")
+        _check(lib().snapgpu_paired_cigar_resident(self._h, res.ctypes.data if n else None, int(useM)),
+               "paired_cigar_resident")
+
+    def cigars(self):
+        """The 2n rows run_cigars() wrote (waits): row 2q + e is end e of pair q."""
+        c = Cigars.empty(2 * self.resident_pairs())   # the C call writes two rows per resident pair
+        _check(lib().snapgpu_paired_cigar_download(self._h, c.editDistance.ctypes.data, c.nOps.ctypes.data,
+                                                   c.ops.ctypes.data), "paired_cigar_download")
+        return c
+
+    def run_sam(self, reads0, reads1, read_group="FASTQ"):
+        """SAM lines of the resident batch, its uploaded records and the CIGARs run_cigars() left in
+        HBM, formatted on the GPU (asynchronous).  reads0 / reads1: the batches that were aligned
+        (their ids and clip state are uploaded, their bases are not)."""
+        rg = None if read_group is None else (read_group.encode() if isinstance(read_group, str) else bytes(read_group))
+        _check(lib().snapgpu_paired_sam_resident(self._h, reads0._p, reads1._p, rg), "paired_sam_resident")
+
+    def sam(self, timing=None):
+        """The text run_sam() wrote -> bytes (waits).  timing: a dict that receives "done", the
+        time.perf_counter() at which the text was in host memory."""
+        used = C.c_uint64()
+        fn = lib().snapgpu_paired_sam_download
+        rc = fn(self._h, None, 0, C.byref(used))
+        if rc != 0 and used.value == 0:
+            _check(rc, "paired_sam_download")
+        buf = np.empty(max(1, used.value), dtype=np.uint8)
+        _check(fn(self._h, buf.ctypes.data, used.value, C.byref(used)), "paired_sam_download")
+        if timing is not None:
+            timing["done"] = time.perf_counter()
+        return buf[:used.value].tobytes()
+
+    def sam_format(self, reads0, reads1, results, cigars, read_group="FASTQ"):
+        """The module-level sam_format_pairs on the GPU (snapgpu_sam_format_pairs_gpu: uploads reads,
+        records and CIGARs, runs the resident path's kernels, downloads the text) -> bytes."""
+        args, keep, cap = _pair_inputs(self.index, reads0, reads1, results, cigars, read_group)
+        return _sized_call(lambda *a: lib().snapgpu_sam_format_pairs_gpu(self._h, *a), args, cap, "sam_format_pairs_gpu")
+
+    def sam_ms(self):
+        """(CIGAR kernel ms, formatter kernel ms, download ms) of the last resident calls
+        (snapgpu_paired_sam_last_ms)."""
+        v = [C.c_double() for _ in range(3)]
+        _check(lib().snapgpu_paired_sam_last_ms(self._h, *[C.byref(x) for x in v]), "paired_sam_last_ms")
+        return tuple(x.value for x in v)
+
     def __del__(self):
         if getattr(self, "_h", None):
             lib().snapgpu_paired_aligner_free(self._h)
@@ -1175,6 +1231,92 @@ def sam_line_lengths(index, reads, ids, results, cigars, read_group="FASTQ", cli
     out = np.zeros(max(1, reads.n), dtype=np.uint32)
     _check(lib().snapgpu_sam_line_lengths(index._h, *args, out.ctypes.data), "sam_line_lengths")
     return out[:reads.n]
+
+
+def _pair_inputs(index, reads0, reads1, results, cigars, read_group):
+    """The argument list the pair formatters take up to the read group (and what keeps it alive)."""
+    n = reads0.n
+    if reads1.n != n:
+        raise ValueError("the two read batches differ in length")
+    res = np.ascontiguousarray(results, dtype=PAIR_RESULT_DTYPE)
+    if res.shape != (n,) or len(cigars.editDistance) != 2 * n:
+        raise ValueError("results / cigars do not have one entry per pair / two rows per pair")
+    ed = np.ascontiguousarray(cigars.editDistance, dtype=np.int32)
+    nops = np.ascontiguousarray(cigars.nOps, dtype=np.uint32)
+    ops = np.ascontiguousarray(cigars.ops, dtype=np.uint32)
+    rg = None if read_group is None else (read_group.encode() if isinstance(read_group, str) else bytes(read_group))
+    keep = (res, ed, nops, ops, rg)
+    ptr = lambda a: a.ctypes.data if a.size else None
+    args = [index._h, reads0._p, reads1._p, ptr(res), ptr(ed), ptr(nops), ptr(ops), rg]
+    ids = sum(int(np.ctypeslib.as_array(r._p.contents.idLengths, shape=(n,)).sum())
+              for r in (reads0, reads1) if n and r._p.contents.idLengths)
+    cap = ids + 2 * int(reads0._p.contents.totalBytes + reads1._p.contents.totalBytes) + 2 * n * 512
+    return args, keep, cap
+
+
+def _sized_call(fn, args, cap, what):
+    """fn(*args, out, cap, &used) under the formatters' size contract -> bytes."""
+    used = C.c_uint64()
+    buf = np.empty(max(1, cap), dtype=np.uint8)
+    rc = fn(*args, buf.ctypes.data, cap, C.byref(used))
+    if rc != 0 and used.value > cap:
+        cap = used.value
+        buf = np.empty(cap, dtype=np.uint8)
+        rc = fn(*args, buf.ctypes.data, cap, C.byref(used))
+    _check(rc, what)
+    return buf[:used.value].tobytes()
+
+
+def sam_format_pairs(index, reads0, reads1, results, cigars, read_group="FASTQ", timing=None):
+    """The two SAM lines of every pair (snapgpu_sam_format_pairs: SimpleReadWriter::writePair over
+    SAMFormat::writeRead with a mate) -> bytes.  results: PAIR_RESULT_DTYPE records; cigars: 2n rows,
+    row 2q + e for end e of pair q; the batches' own ids and clip state are used.  timing: a dict
+    that receives the seconds spent in the C formatter ("format_s")."""
+    args, keep, cap = _pair_inputs(index, reads0, reads1, results, cigars, read_group)
+    t0 = time.perf_counter()
+    text = _sized_call(lib().snapgpu_sam_format_pairs, args, cap, "sam_format_pairs")
+    if timing is not None:
+        timing["format_s"] = time.perf_counter() - t0
+    return text
+
+
+def sam_pair_line_lengths(index, reads0, reads1, results, cigars, read_group="FASTQ"):
+    """Byte length of each of the 2n lines sam_format_pairs prints (the host side of the device
+    formatter's length pass; needs no GPU) -> np.uint32 array."""
+    args, keep, _ = _pair_inputs(index, reads0, reads1, results, cigars, read_group)
+    out = np.zeros(max(1, 2 * reads0.n), dtype=np.uint32)
+    _check(lib().snapgpu_sam_pair_line_lengths(*args, out.ctypes.data), "sam_pair_line_lengths")
+    return out[:2 * reads0.n]
+
+
+def _sam_pair_line_write(index, reads0, reads1, results, cigars, read_group="FASTQ"):
+    """The same lines through csrc/sam_pair_line.h's writer on one host thread, the code the device
+    write pass runs per wave (test accessor; needs no GPU)."""
+    args, keep, cap = _pair_inputs(index, reads0, reads1, results, cigars, read_group)
+    fn = lib().snapgpu_internal_sam_pair_line_write
+    fn.restype = C.c_int
+    fn.argtypes = _ffi._PAIR_LINES + [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+    return _sized_call(fn, args, cap, "sam_pair_line_write")
+
+
+def _pair_cigar_inputs(results):
+    """(locations, directions) of the 2n CIGAR rows of pair records, row 2q + e: location[e], or
+    invalid where status[e] is NotFound, and direction[e] (BaseAligner.Cigars' arguments)."""
+    res = np.ascontiguousarray(results, dtype=PAIR_RESULT_DTYPE)
+    loc = np.where(res["status"] != NotFound, res["location"], 0xFFFFFFFF).astype(np.uint32).reshape(-1)
+    return np.ascontiguousarray(loc), np.ascontiguousarray(res["direction"].reshape(-1), dtype=np.uint8)
+
+
+def _pair_cigars(aligner, reads0, reads1, results, useM=False):
+    """The 2n CIGAR rows of pair records through the existing batch call (BaseAligner.Cigars on each
+    end's batch at _pair_cigar_inputs' locations and directions), row 2q + e -> Cigars."""
+    loc, dr = _pair_cigar_inputs(results)
+    n = reads0.n
+    c = Cigars.empty(2 * n)
+    for e, r in enumerate((reads0, reads1)):
+        k = aligner.Cigars(r, loc[e::2], dr[e::2], useM=useM)
+        c.editDistance[e::2], c.nOps[e::2], c.ops[e::2] = k.editDistance, k.nOps, k.ops
+    return c
 
 
 def sam_sort_keys(index, results):

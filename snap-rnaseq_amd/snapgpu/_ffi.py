@@ -477,6 +477,22 @@ _PROTOS += [
     ("snapgpu_seed_runs_free", None, [C.POINTER(SeedRuns)]),
 ]
 
+# SAM text of read pairs: (index, reads0, reads1, results, editDistance, nOps, ops, readGroup), then the output
+_PAIR_LINES = [C.c_void_p, C.POINTER(Reads), C.POINTER(Reads), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p]
+_PROTOS += [
+    ("snapgpu_sam_format_pairs", C.c_int, _PAIR_LINES + [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
+    ("snapgpu_sam_pair_line_lengths", C.c_int, _PAIR_LINES + [C.c_void_p]),
+    ("snapgpu_paired_resident_pairs", C.c_uint64, [C.c_void_p]),
+    ("snapgpu_paired_cigar_resident", C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
+    ("snapgpu_paired_cigar_download", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("snapgpu_paired_sam_resident", C.c_int, [C.c_void_p, C.POINTER(Reads), C.POINTER(Reads), C.c_char_p]),
+    ("snapgpu_paired_sam_download", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
+    ("snapgpu_paired_sam_last_ms", C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                             C.POINTER(C.c_double)]),
+    ("snapgpu_sam_format_pairs_gpu", C.c_int, [C.c_void_p] + _PAIR_LINES + [C.c_void_p, C.c_uint64,
+                                                                            C.POINTER(C.c_uint64)]),
+]
+
 CIGAR_MAX_OPS = 64   # SNAPGPU_CIGAR_MAX_OPS
 
 EXPORTED_SYMBOLS = [p[0] for p in _PROTOS]
