@@ -10,6 +10,7 @@
 
 #include <atomic>
 #include <chrono>
+#include <cstring>
 #include <initializer_list>
 #include <string>
 #include <vector>
@@ -149,10 +150,35 @@ struct SamState : StageState {
     bool cachedDevForm = false;   // ... laid out for a call without a host batch (reads == NULL): no ids, no clip arrays
     uint64_t n = 0, textBound = 0;
     // ev: before the length pass, after the check; after the length pass, after the scan; after the sort step
-    explicit SamState(Stage stage = kStageSam)
-        : StageState(stage, 5, {&aux, &len, &scans, &start, &sums, &text, &bad, &bases, &quals, &res, &ed, &nOps, &ops,
-                                &key, &keySorted, &iota, &order, &slotLen, &sortTemp}) {}
+    // (a state built on this one may ask for more events and say what they are recorded around)
+    explicit SamState(Stage stage = kStageSam, int nEv = 5)
+        : StageState(stage, nEv, {&aux, &len, &scans, &start, &sums, &text, &bad, &bases, &quals, &res, &ed, &nOps, &ops,
+                                  &key, &keySorted, &iota, &order, &slotLen, &sortTemp}) {}
 };
+
+// One packed upload of small host arrays (SamState::aux): 16-byte aligned pieces, each piece's
+// offset known when it is added, the bytes copied later or not at all.
+struct AuxPack {
+    struct Piece { const void *p; uint64_t at, bytes; };
+    std::vector<Piece> pieces;
+    uint64_t end = 0;   // 16-byte aligned
+    // `bytes` at p (null: zeros) -> their offset in the upload
+    uint64_t add(const void *p, uint64_t bytes) {
+        pieces.push_back({p, end, bytes});
+        end = (end + bytes + 15) & ~15ull;
+        return pieces.back().at;
+    }
+    uint64_t bytes() const { return end + 16; }   // with 16 bytes of zeros behind the last piece
+    void copyTo(std::vector<char> &h) const {
+        h.assign(bytes(), 0);
+        for (const Piece &c : pieces)
+            if (c.p && c.bytes) memcpy(h.data() + c.at, c.p, c.bytes);
+    }
+};
+
+// What the download of a text stage says: the message of a failed check, a printf format over (bad,
+// records, bytes, bound), and the call's name in "<call>: output buffer too small".
+struct StageWords { const char *checkFmt, *call; };
 
 // Device BAM encoder (bam_format.hip) state: the SAM formatter's buffers (its own copies: a batch's
 // SAM and BAM calls do not disturb each other) and the NM carry's.
@@ -385,6 +411,18 @@ extern "C" int snapgpu_internal_cigar_device(snapgpu_aligner_t *a, hipStream_t s
 // ---- defined in output_chain.hip
 // S's buffers and events back to the runtime (neither once the aligner has failed).
 void stageFree(const snapgpu_aligner_t *a, StageState &S);
+// S's nEv events, created by the stage's first launch.
+int stageEvents(StageState &S);
+// The text stage's buffers for n records (0 < n < 2^32) and S.textBound bytes of text, grown, into
+// *B (no mid events).
+int textBuffers(const snapgpu_aligner_t *a, SamState &S, uint64_t n, samgpu::Buffers *B);
+// What follows a text stage's kernels (S.ev[1] recorded behind them, S.n records): wait for them,
+// fetch start[n] and bad and compare them with S.textBound (SNAPGPU_EDEVICE, in W's words), *used =
+// the bytes, then copy them to out[0 .. cap) (textDownload; SNAPGPU_EINVAL when they do not fit).
+// checked(S, arg), if given, runs once the check has passed (the BAM stage's carry-out).
+// S.downloadMs = the wall ms after the wait.  S.n == 0: nothing to do.
+int textFinish(snapgpu_aligner_t *a, SamState &S, const StageWords &W, char *out, uint64_t cap, uint64_t *used,
+               int (*checked)(SamState &, void *) = nullptr, void *arg = nullptr);
 // `total` bytes at device address `text` to the caller's (pageable) buffer, in chunks through two
 // pinned staging buffers: chunk k + 1 crosses PCIe while host threads copy chunk k out.
 int textDownload(snapgpu_aligner_t *a, const char *text, uint64_t total, char *out);

@@ -1,7 +1,7 @@
 // bam_format.hip -- BAM records of single-end alignments, encoded in HBM.
 //
 // The passes of sam_format.hip over n records whose reads, records and CIGAR ops are device resident,
-// with bam_line.h in place of sam_line.h:
+// with bam_line.h as the line rule:
 //   length  one wave per record computes its exact size and its own NM value, or "none" for a record
 //           without CIGAR ops (and, for sorted output, its sort key);
 //   carry   an inclusive "last defined value" scan of the NM values over input order, seeded with the
@@ -10,54 +10,40 @@
 //   scan    samgpu::scanStarts over the sizes (over output slots after samgpu::sortStep when sorted);
 //   write   one workgroup per kRecsPerGroup consecutive slots, one contiguous byte range: each wave
 //           composes its records in an LDS window of that range (the lead lane writes the fixed part,
-//           the CIGAR ops and the NM value, lanes copy id and QUAL bytes, lane k packs SEQ byte k),
-//           then the workgroup flushes the window with 16-byte lane-contiguous stores (the range's
-//           unaligned head and tail bytewise).  Nothing is stored outside [start[first], start[end)).
+//           the CIGAR ops and the NM value, lanes copy id and QUAL bytes, lane k packs SEQ byte k)
+//           and the workgroup flushes the window with 16-byte stores (staged_write.h).
 // A last kernel counts the records whose block_size is not the size the scan gave them.
+// The length and write kernels are line_passes.h's, instantiated for BamRule below; the NM carry
+// passes and the block_size check are this file's own.
 #include "bam_format.h"
+
+#include "line_passes.h"
 
 namespace bamgpu {
 
-using bamline::Fields;
 using bamline::kNoNm;
-using samgpu::kRecsPerGroup;
 using samgpu::kScanTile;
-using samgpu::kTileBytes;
 using samgpu::Wave;
 using samline::Args;
 
 namespace {
 
-template <bool Sorted>
-struct KeyOut {};
-template <>
-struct KeyOut<true> {
-    uint32_t *key;   // [n] out: bamline::sortKey per record
-};
-template <bool Sorted>
-struct SlotOrder {
-    __device__ uint64_t record(uint64_t j) const { return j; }
-};
-template <>
-struct SlotOrder<true> {
-    const uint32_t *order;   // [n] output slot -> record
-    __device__ uint64_t record(uint64_t j) const { return order[j]; }
-};
-
-template <bool Sorted>
-__global__ __launch_bounds__(256) void bam_length_kernel(Args A, uint64_t n, uint32_t *__restrict__ len,
-                                                         int32_t *__restrict__ nm, KeyOut<Sorted> K) {
-    const Wave g{nullptr, 0, 0, threadIdx.x & 63u};
-    const uint64_t waves = (uint64_t)gridDim.x * 4u;
-    for (uint64_t r = (uint64_t)blockIdx.x * 4u + threadIdx.x / 64u; r < n; r += waves) {
+// The BAM record rule (bam_line.h); its side is the record's own NM after the length pass, the NM
+// it carries after the carry passes.  The sort key needs nothing beside the arguments.
+struct BamRule {
+    using Fields = bamline::Fields;
+    using Side = int32_t;
+    struct SortTables {};
+    Args A;
+    __device__ Fields fields(uint64_t r, const Wave &g) const { return bamline::fields(A, r, g); }
+    __device__ uint32_t length(const Fields &F) const { return bamline::recordLength(A, F); }
+    __device__ Side side(const Fields &F) const { return F.nmOwn; }
+    __device__ uint32_t sortKey(const SortTables &, const Fields &F) const { return bamline::sortKey(A, F); }
+    __device__ void write(uint64_t r, uint64_t s, const Side *nm, const Wave &g) const {
         const Fields F = bamline::fields(A, r, g);
-        if (g.lane == 0) {
-            len[r] = bamline::recordLength(A, F);
-            nm[r] = F.nmOwn;
-            if constexpr (Sorted) K.key[r] = bamline::sortKey(A, F);
-        }
+        bamline::write(A, r, F, nm[r], s, g);
     }
-}
+};
 
 constexpr uint32_t kPerThread = kScanTile / 256;
 
@@ -126,46 +112,6 @@ __global__ __launch_bounds__(256) void bam_nm_apply_kernel(int32_t *__restrict__
     }
 }
 
-// Sorted: start[] is over output slots and slot j holds record O.order[j] (nm[] stays per record),
-// else slot j holds record j.
-template <bool Sorted>
-__global__ __launch_bounds__(256) void bam_write_kernel(Args A, uint64_t n, const uint64_t *__restrict__ start,
-                                                        const int32_t *__restrict__ nm, char *__restrict__ out,
-                                                        uint64_t cap, SlotOrder<Sorted> O) {
-    __shared__ uint4 tile[kTileBytes / 16];
-    char *lds = reinterpret_cast<char *>(tile);
-    const uint64_t first = (uint64_t)blockIdx.x * kRecsPerGroup;
-    const uint64_t end = first + kRecsPerGroup < n ? first + kRecsPerGroup : n;
-    const uint64_t r0 = start[first], r1 = start[end];
-    if (r1 > cap) return;   // the host's bound on the output was too small: bam_check_kernel reports it
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x / 64u;
-    // windows are 16-byte aligned in the output, so an LDS chunk is a 16-byte aligned store
-    for (uint64_t w0 = r0 & ~15ull; w0 < r1; w0 += kTileBytes) {
-        const uint64_t w1 = w0 + kTileBytes < r1 ? w0 + kTileBytes : r1;
-        const Wave g{lds, w0, w1, lane};
-        for (uint64_t j = first + wave; j < end; j += 4) {
-            const uint64_t s = start[j], e = start[j + 1];
-            if (e <= w0 || s >= w1) continue;
-            const uint64_t r = O.record(j);
-            if (Sorted && r >= n) continue;   // not a record (never): the slot is empty, the check reports it
-            const Fields F = bamline::fields(A, r, g);
-            bamline::write(A, r, F, nm[r], s, g);
-        }
-        __syncthreads();
-        const uint32_t chunks = (uint32_t)((w1 - w0 + 15) / 16);
-        for (uint32_t c = threadIdx.x; c < chunks; c += 256) {
-            const uint64_t a = w0 + 16ull * c;
-            if (a >= r0 && a + 16 <= r1) {
-                *reinterpret_cast<uint4 *>(out + a) = tile[c];
-            } else {
-                const uint64_t lo = a > r0 ? a : r0, hi = a + 16 < r1 ? a + 16 : r1;
-                for (uint64_t b = lo; b < hi; b++) out[b] = lds[b - w0];
-            }
-        }
-        __syncthreads();
-    }
-}
-
 // block_size of slot i must be its scanned size - 4, at its scanned start
 __global__ __launch_bounds__(256) void bam_check_kernel(const uint64_t *__restrict__ start, uint64_t n,
                                                         const char *__restrict__ out, uint64_t cap, uint32_t *bad) {
@@ -185,15 +131,14 @@ __global__ __launch_bounds__(256) void bam_check_kernel(const uint64_t *__restri
 
 hipError_t launch(const Args &A, uint64_t n, int32_t nmCarryIn, const Buffers &B, hipStream_t st,
                   const samgpu::SortBuffers *S) {
-    hipError_t e = hipMemsetAsync(B.bad, 0, sizeof(uint32_t), st);
+    using samgpu::KeyOut;
+    using samgpu::SlotOrder;
+    const BamRule R{A};
+    hipError_t e = S ? samgpu::lengthPass(R, n, B.len, B.nm, B.bad, st, KeyOut<true, BamRule>{{}, S->key})
+                     : samgpu::lengthPass(R, n, B.len, B.nm, B.bad, st, KeyOut<false, BamRule>{});
     if (e != hipSuccess) return e;
-    const uint64_t nTiles = samgpu::scanTiles(n), nGroups = (n + kRecsPerGroup - 1) / kRecsPerGroup;
-    const uint64_t lenBlocks = (n + 3) / 4 < 65536 ? (n + 3) / 4 : 65536;
-    const dim3 perItem((unsigned)((n + 255) / 256)), tiles((unsigned)nTiles);
-    if (S) hipLaunchKernelGGL(bam_length_kernel<true>, dim3((unsigned)lenBlocks), dim3(256), 0, st, A, n, B.len, B.nm,
-                              KeyOut<true>{S->key});
-    else hipLaunchKernelGGL(bam_length_kernel<false>, dim3((unsigned)lenBlocks), dim3(256), 0, st, A, n, B.len, B.nm,
-                            KeyOut<false>{});
+    const uint64_t nTiles = samgpu::scanTiles(n);
+    const dim3 tiles((unsigned)nTiles);
     hipLaunchKernelGGL(bam_nm_tile_last_kernel, tiles, dim3(256), 0, st, B.nm, n, B.nmTiles);
     hipLaunchKernelGGL(bam_nm_tiles_kernel, dim3(1), dim3(256), 0, st, B.nmTiles, nTiles, nmCarryIn);
     hipLaunchKernelGGL(bam_nm_apply_kernel, tiles, dim3(256), 0, st, B.nm, n, B.nmTiles);
@@ -203,11 +148,9 @@ hipError_t launch(const Args &A, uint64_t n, int32_t nmCarryIn, const Buffers &B
         len = S->slotLen;
     }
     samgpu::scanStarts(len, n, B.sums, B.start, st);
-    if (S) hipLaunchKernelGGL(bam_write_kernel<true>, dim3((unsigned)nGroups), dim3(256), 0, st, A, n, B.start, B.nm, B.out,
-                              B.outCap, SlotOrder<true>{S->order});
-    else hipLaunchKernelGGL(bam_write_kernel<false>, dim3((unsigned)nGroups), dim3(256), 0, st, A, n, B.start, B.nm, B.out,
-                            B.outCap, SlotOrder<false>{});
-    hipLaunchKernelGGL(bam_check_kernel, perItem, dim3(256), 0, st, B.start, n, B.out, B.outCap, B.bad);
+    if (S) samgpu::writePass(R, n, B.start, B.nm, B.out, B.outCap, st, SlotOrder<true>{S->order});
+    else samgpu::writePass(R, n, B.start, B.nm, B.out, B.outCap, st, SlotOrder<false>{});
+    hipLaunchKernelGGL(bam_check_kernel, samgpu::perItem(n), dim3(256), 0, st, B.start, n, B.out, B.outCap, B.bad);
     return hipGetLastError();
 }
 

@@ -9,10 +9,12 @@
 //                            reduction, then one atomicMax each per wave)
 //   5. samgpu::scanStarts    64-bit starts of the records' bases and ids
 //   6. fastq_pack_kernel     ids, bases and qualities to their places, staged through LDS so that
-//                            the stores are whole 16-byte chunks
+//                            the stores are whole 16-byte chunks (staged_write.h, once per output)
 // All byte offsets are 64-bit.  The text buffer is fqgpu::textCapacity(nBytes) long and zero from
 // nBytes on, so the newline passes load whole 64-byte lane spans without a tail case.
 #include "fastq_parse.h"
+
+#include "staged_write.h"
 
 namespace fqgpu {
 namespace {
@@ -154,20 +156,18 @@ __global__ __launch_bounds__(256) void fastq_limits_kernel(const uint32_t *__res
 }
 
 // One output of the copy pass over the group's records [first, end): record j's piece is src[j]'s
-// first `valid` bytes, then 0x00, start[j + 1] - start[j] bytes in all, at out + start[j].  Windows
-// of kStageBytes of the output, 16-byte aligned, are filled in LDS by a wave per record and stored
-// as whole uint4 chunks (bytes at the group's two ragged ends singly: the neighbours own the rest).
+// first `valid` bytes, then 0x00, start[j + 1] - start[j] bytes in all, at out + start[j], staged
+// through windows of kStageBytes in LDS and stored as whole uint4 chunks (staged_write.h).
 template <class Src>
 __device__ void packStream(char *__restrict__ out, const uint64_t *__restrict__ start, uint64_t first, uint64_t end,
                            uint4 *tile, Src src) {
     char *lds = reinterpret_cast<char *>(tile);
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x / 64u;
-    const uint64_t r0 = start[first], r1 = start[end];
-    for (uint64_t w0 = r0 & ~15ull; w0 < r1; w0 += kStageBytes) {
-        const uint64_t w1 = w0 + kStageBytes < r1 ? w0 + kStageBytes : r1;
+    for (staged::Windows<kStageBytes> W(start, first, end); W.more(); W.flush(out, tile)) {
+        const uint64_t w0 = W.w0, w1 = W.w1();
         for (uint64_t j = first + wave; j < end; j += 4) {
             const uint64_t s = start[j], e = start[j + 1];
-            if (e <= w0 || s >= w1) continue;
+            if (!W.holds(s, e)) continue;
             const char *p;
             uint32_t valid;
             src(j, p, valid);
@@ -177,18 +177,6 @@ __device__ void packStream(char *__restrict__ out, const uint64_t *__restrict__ 
                 lds[at - w0] = k < valid ? p[k] : (char)0;
             }
         }
-        __syncthreads();
-        const uint32_t chunks = (uint32_t)((w1 - w0 + 15) / 16);
-        for (uint32_t c = threadIdx.x; c < chunks; c += 256) {
-            const uint64_t a = w0 + 16ull * c;
-            if (a >= r0 && a + 16 <= r1) {
-                *reinterpret_cast<uint4 *>(out + a) = tile[c];
-            } else {
-                const uint64_t lo = a > r0 ? a : r0, hi = a + 16 < r1 ? a + 16 : r1;
-                for (uint64_t b = lo; b < hi; b++) out[b] = lds[b - w0];
-            }
-        }
-        __syncthreads();
     }
 }
 

@@ -27,7 +27,7 @@ void stageFree(const snapgpu_aligner_t *a, StageState &S) {
             if (e) { hipEventDestroy(e); e = nullptr; }
 }
 
-static int stageEvents(StageState &S) {   // created on the stage's first launch
+int stageEvents(StageState &S) {
     for (int k = 0; k < S.nEv; k++)
         if (!S.ev[k]) HIPCHK(hipEventCreate(&S.ev[k]));
     return SNAPGPU_OK;
@@ -138,33 +138,22 @@ static int samPrepare(snapgpu_aligner_t *a, SamState &S, const SamHostIn &H, boo
         }
     }
     S.textBound = bound;
-    auto al16 = [](uint64_t x) { return (x + 15) & ~15ull; };
+    AuxPack P;
     const uint64_t nIds = H.ids ? n : 0;   // the id arrays ride in aux only when they come from the host
-    const uint64_t oIdOff = 0, oIdLen = al16(oIdOff + nIds * 8), oFront = al16(oIdLen + nIds * 4),
-                   oFull = al16(oFront + (H.unclipped ? n * 4 : 0)), oOff = al16(oFull + (H.unclipped ? n * 4 : 0)),
-                   oLen = al16(oOff + (H.offsets ? n * 8 : 0)), oNameOff = al16(oLen + (H.offsets ? n * 4 : 0)),
-                   oNames = al16(oNameOff + nameOff.size() * 4), oSortBase = al16(oNames + names.size()),
-                   oSortNone = al16(oSortBase + sortBase.size() * 4), oRg = al16(oSortNone + sortNone.size()),
-                   oIds = al16(oRg + rgLen), bytes = al16(oIds + idBytes) + 16;
+    const uint64_t nClip = H.unclipped ? n : 0, nExt = H.offsets ? n : 0;
+    const uint64_t oIdOff = P.add(H.idOffsets, nIds * 8), oIdLen = P.add(H.idLengths, nIds * 4),
+                   oFront = P.add(H.front, nClip * 4), oFull = P.add(H.unclipped, nClip * 4),
+                   oOff = P.add(H.offsets, nExt * 8), oLen = P.add(H.lengths, nExt * 4),
+                   oNameOff = P.add(nameOff.data(), nameOff.size() * 4), oNames = P.add(names.data(), names.size()),
+                   oSortBase = P.add(sortBase.data(), sortBase.size() * 4), oSortNone = P.add(sortNone.data(), sortNone.size()),
+                   oRg = P.add(H.rg, rgLen), oIds = P.add(H.ids, idBytes);
     if (!skip) {
         if (S.ran && S.ev[1]) HIPCHK(hipEventSynchronize(S.ev[1]));   // an earlier call's kernels may still read aux
-        HIPCHK(devGrow(a, S.aux, bytes));
-        S.hAux.assign(bytes, 0);
-        char *h = S.hAux.data();
-        if (n) {
-            if (nIds) { memcpy(h + oIdOff, H.idOffsets, n * 8); memcpy(h + oIdLen, H.idLengths, n * 4); }
-            if (H.unclipped) { memcpy(h + oFront, H.front, n * 4); memcpy(h + oFull, H.unclipped, n * 4); }
-            if (H.offsets) { memcpy(h + oOff, H.offsets, n * 8); memcpy(h + oLen, H.lengths, n * 4); }
-        }
-        memcpy(h + oNameOff, nameOff.data(), nameOff.size() * 4);
-        memcpy(h + oNames, names.data(), names.size());
-        memcpy(h + oSortBase, sortBase.data(), sortBase.size() * 4);
-        memcpy(h + oSortNone, sortNone.data(), sortNone.size());
-        if (rgLen) memcpy(h + oRg, H.rg, rgLen);
-        if (idBytes) memcpy(h + oIds, H.ids, idBytes);
+        HIPCHK(devGrow(a, S.aux, P.bytes()));
+        P.copyTo(S.hAux);
         // on the otherwise idle copy stream, and waited for: the host copy may go, and the side
         // stream (which may still be in the CIGAR kernel) is not waited for
-        HIPCHK(hipMemcpyAsync(S.aux.p, h, bytes, hipMemcpyHostToDevice, a->copyStream));
+        HIPCHK(hipMemcpyAsync(S.aux.p, S.hAux.data(), P.bytes(), hipMemcpyHostToDevice, a->copyStream));
         HIPCHK(hipStreamSynchronize(a->copyStream));
     }
     const char *d = (const char *)S.aux.p;
@@ -196,6 +185,19 @@ static int sortBuffers(snapgpu_aligner_t *a, SamState &S, uint64_t n, samgpu::So
     return SNAPGPU_OK;
 }
 
+int textBuffers(const snapgpu_aligner_t *a, SamState &S, uint64_t n, samgpu::Buffers *B) {
+    if (n > 0xffffffffull) { snapgpu::setError("batch too large"); return SNAPGPU_EINVAL; }
+    HIPCHK(devGrow(a, S.len, n * 4));
+    HIPCHK(devGrow(a, S.scans, n * sizeof(samline::Scans)));
+    HIPCHK(devGrow(a, S.start, (n + 1) * 8));
+    HIPCHK(devGrow(a, S.sums, samgpu::scanTiles(n) * 8));
+    HIPCHK(devGrow(a, S.bad, 16));
+    HIPCHK(devGrow(a, S.text, S.textBound + 16));
+    *B = samgpu::Buffers{(uint32_t *)S.len.p, (samline::Scans *)S.scans.p, (uint64_t *)S.start.p, (uint64_t *)S.sums.p,
+                         (char *)S.text.p, S.textBound, (uint32_t *)S.bad.p, {nullptr, nullptr}};
+    return SNAPGPU_OK;
+}
+
 // Length pass, scan, write pass and check of n records on the side stream, into S's buffers;
 // sorted: in the stable order of the records' coordinate-sort keys (S.order keeps that order).
 static int samLaunch(snapgpu_aligner_t *a, SamState &S, const samline::Args &A, uint64_t n, bool sorted) {
@@ -206,15 +208,10 @@ static int samLaunch(snapgpu_aligner_t *a, SamState &S, const samline::Args &A, 
     S.sorted = sorted;
     a->last[kStageSam] = &S;
     if (n == 0) return SNAPGPU_OK;
-    if (n > 0xffffffffull) { snapgpu::setError("batch too large"); return SNAPGPU_EINVAL; }
-    HIPCHK(devGrow(a, S.len, n * 4));
-    HIPCHK(devGrow(a, S.scans, n * sizeof(samline::Scans)));
-    HIPCHK(devGrow(a, S.start, (n + 1) * 8));
-    HIPCHK(devGrow(a, S.sums, samgpu::scanTiles(n) * 8));
-    HIPCHK(devGrow(a, S.bad, 16));
-    HIPCHK(devGrow(a, S.text, S.textBound + 16));
-    const samgpu::Buffers B{(uint32_t *)S.len.p, (samline::Scans *)S.scans.p, (uint64_t *)S.start.p, (uint64_t *)S.sums.p, (char *)S.text.p,
-                            S.textBound, (uint32_t *)S.bad.p, {S.ev[2], S.ev[3]}};
+    samgpu::Buffers B;
+    if (int rc = textBuffers(a, S, n, &B)) return rc;
+    B.mid[0] = S.ev[2];
+    B.mid[1] = S.ev[3];
     samgpu::SortBuffers SB{};
     if (sorted) {
         if (int rc = sortBuffers(a, S, n, &SB)) return rc;
@@ -255,8 +252,8 @@ int textDownload(snapgpu_aligner_t *a, const char *text, uint64_t total, char *o
     return SNAPGPU_OK;
 }
 
-// Wait for S's kernels, check them, and copy the text to the caller's buffer (textDownload).
-static int samDownload(snapgpu_aligner_t *a, SamState &S, char *out, uint64_t cap, uint64_t *used) {
+int textFinish(snapgpu_aligner_t *a, SamState &S, const StageWords &W, char *out, uint64_t cap, uint64_t *used,
+               int (*checked)(SamState &, void *), void *arg) {
     *used = 0;
     S.downloadMs = 0;
     if (S.n == 0) return SNAPGPU_OK;
@@ -268,16 +265,23 @@ static int samDownload(snapgpu_aligner_t *a, SamState &S, char *out, uint64_t ca
     HIPCHK(hipMemcpy(&bad, S.bad.p, 4, hipMemcpyDeviceToHost));
     if (bad || total > S.textBound) {
         char msg[160];
-        snprintf(msg, sizeof msg, "sam: %u of %llu lines do not end where the scan placed them (text %llu bytes, bound %llu)",
-                 bad, (unsigned long long)S.n, (unsigned long long)total, (unsigned long long)S.textBound);
+        snprintf(msg, sizeof msg, W.checkFmt, bad, (unsigned long long)S.n, (unsigned long long)total,
+                 (unsigned long long)S.textBound);
         snapgpu::setError(msg);
         return SNAPGPU_EDEVICE;
     }
+    if (checked)
+        if (int rc = checked(S, arg)) return rc;
     *used = total;
-    if (total > cap || !out) { snapgpu::setError("sam_download: output buffer too small"); return SNAPGPU_EINVAL; }
+    if (total > cap || !out) { snapgpu::setError(std::string(W.call) + ": output buffer too small"); return SNAPGPU_EINVAL; }
     if (int rc = textDownload(a, (const char *)S.text.p, total, out)) return rc;
     S.downloadMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return SNAPGPU_OK;
+}
+
+static int samDownload(snapgpu_aligner_t *a, SamState &S, char *out, uint64_t cap, uint64_t *used) {
+    return textFinish(a, S, {"sam: %u of %llu lines do not end where the scan placed them (text %llu bytes, bound %llu)", "sam_download"},
+                      out, cap, used);
 }
 
 // The device BAM encoder's passes over n records on the side stream, into S's buffers (samLaunch's
@@ -311,31 +315,15 @@ static int bamLaunch(snapgpu_aligner_t *a, BamState &S, const samline::Args &A, 
     return SNAPGPU_OK;
 }
 
-// Wait for S's kernels, check them, and copy the records and the carry-out to the caller.
+// textFinish over the records, and the carry-out: the carry-in again unless the check passed.
 static int bamDownload(snapgpu_aligner_t *a, BamState &S, char *out, uint64_t cap, uint64_t *used, int32_t *nmCarryOut) {
-    *used = 0;
-    S.downloadMs = 0;
     if (nmCarryOut) *nmCarryOut = S.carryIn;
-    if (S.n == 0) return SNAPGPU_OK;
-    if (int rc = waitEvent(a, S.ev[1])) return rc;
-    const auto t0 = std::chrono::steady_clock::now();
-    uint64_t total = 0;
-    uint32_t bad = 0;
-    HIPCHK(hipMemcpy(&total, (const uint64_t *)S.start.p + S.n, 8, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(&bad, S.bad.p, 4, hipMemcpyDeviceToHost));
-    if (bad || total > S.textBound) {
-        char msg[160];
-        snprintf(msg, sizeof msg, "bam: %u of %llu records do not carry the size the scan gave them (output %llu bytes, bound %llu)",
-                 bad, (unsigned long long)S.n, (unsigned long long)total, (unsigned long long)S.textBound);
-        snapgpu::setError(msg);
-        return SNAPGPU_EDEVICE;
-    }
-    if (nmCarryOut) HIPCHK(hipMemcpy(nmCarryOut, (const int32_t *)S.nm.p + S.n - 1, 4, hipMemcpyDeviceToHost));
-    *used = total;
-    if (total > cap || !out) { snapgpu::setError("bam_download: output buffer too small"); return SNAPGPU_EINVAL; }
-    if (int rc = textDownload(a, (const char *)S.text.p, total, out)) return rc;
-    S.downloadMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    return SNAPGPU_OK;
+    auto carryOut = [](SamState &B, void *to) -> int {
+        if (to) HIPCHK(hipMemcpy(to, (const int32_t *)static_cast<BamState &>(B).nm.p + B.n - 1, 4, hipMemcpyDeviceToHost));
+        return SNAPGPU_OK;
+    };
+    return textFinish(a, S, {"bam: %u of %llu records do not carry the size the scan gave them (output %llu bytes, bound %llu)", "bam_download"},
+                      out, cap, used, carryOut, nmCarryOut);
 }
 
 // Wait for the mark passes of S and take their counts; SNAPGPU_EDEVICE unless they add up.

@@ -1,13 +1,14 @@
 // paired_output.hip -- the host side of the paired aligner's output calls behind include/snapgpu.h:
 // CIGARs of both ends of the resident pair batch (cigar_kernel over the bases the intersecting run
-// left in HBM, where they are) and the pairs' SAM text (sam_pair_format.hip), over the resident batch and in a batch
-// form.  No kernels here.  Everything is queued on the paired aligner's one stream, so the next
-// intersecting run's copies into the read buffers wait for these kernels by stream order; that run
-// marks the CIGARs and the text stale (pairedOutputStale).  Buffers are grow-only.
+// left in HBM, where they are) and the pairs' SAM text (sam_pair_format.hip), over the resident batch
+// and in a batch form.  No kernels here.  The state is the single-end text stage's (SamState) with
+// what only pairs have, and its buffer growth, packed upload, check and download are the single-end
+// chain's (aligner_state.h, output_chain.hip).  Everything is queued on the paired aligner's one
+// stream, so the next intersecting run's copies into the read buffers wait for these kernels by
+// stream order; that run marks the CIGARs and the text stale (pairedOutputStale).  Buffers are grow-only.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <chrono>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -16,26 +17,22 @@
 #include "paired_state.h"
 #include "sam_pair_format.h"
 
-struct PairedOutput {
-    // the CIGAR pass: the caller's pair records, cigar_kernel's 2n locations and directions and its
-    // 2n rows, each end's n entries a plane (entry e * n + q)
-    DevBuf res, cgLoc, cgDir, ed, nOps, ops;
-    // the SAM passes: ids, id offsets / lengths, clip arrays, piece names, read group (one packed
-    // upload; the batch form's read offsets and lengths too), then samgpu::Buffers
-    DevBuf aux, len, scans, start, sums, text, bad;
+// SamState's members as the pair uses them: res, ed, nOps, ops are the CIGAR pass's copy of the
+// caller's pair records and its 2n rows, each end's n entries a plane (entry e * n + q); aux and the
+// text passes' buffers as they are (aux: both ends' ids and clip arrays, and the batch form's read
+// offsets and lengths); n = the 2n records of the last SAM launch; ev[0..1] around the SAM passes,
+// `launched`: they were recorded.  It is nobody's a->last[]: snapgpu_paired_sam_last_ms reports it.
+struct PairedOutput : SamState {
+    static constexpr int kCigarEv = 5;   // ev[5..6] around the CIGAR pass
+    DevBuf cgLoc, cgDir;                 // cigar_kernel's 2n locations and directions, planes as the rows
     // the batch form's reads, records and CIGAR rows (the resident batch's stay as they are)
     DevBuf bBases[2], bQuals[2], bRes, bEd, bNOps, bOps;
-    hipEvent_t ev[4] = {};            // around the CIGAR pass, around the SAM passes
-    std::vector<char> hAux;           // host copy of aux (alive while its upload may be in flight)
     std::vector<uint32_t> hLen[2];    // the resident batch's lengths, fetched by the CIGAR pass
     bool cigarsValid = false;         // the rows are those of the resident batch
     bool textValid = false;           // the text is that of the resident batch and its rows
-    bool cigarTimed = false, textTimed = false;   // ev[0..1] / ev[2..3] were recorded
-    uint64_t records = 0, textBound = 0;          // of the last SAM launch
-    double downloadMs = 0;
-    std::vector<DevBuf *> bufs() {
-        return {&res, &cgLoc, &cgDir, &ed, &nOps, &ops, &aux, &len, &scans, &start, &sums, &text,
-                &bad, &bBases[0], &bBases[1], &bQuals[0], &bQuals[1], &bRes, &bEd, &bNOps, &bOps};
+    bool cigarTimed = false;          // ev[5..6] were recorded
+    PairedOutput() : SamState(kStageSam, kCigarEv + 2) {
+        bufs.insert(bufs.end(), {&cgLoc, &cgDir, &bBases[0], &bBases[1], &bQuals[0], &bQuals[1], &bRes, &bEd, &bNOps, &bOps});
     }
 };
 
@@ -47,9 +44,7 @@ void pairedOutputStale(snapgpu_paired_aligner_t *pa) {
 void pairedOutputFree(snapgpu_paired_aligner_t *pa) {
     PairedOutput *O = pa->output;
     if (!O) return;
-    for (DevBuf *b : O->bufs()) devFree(pa->single, b->p);
-    for (auto &e : O->ev)
-        if (e) (void)hipEventDestroy(e);
+    stageFree(pa->single, *O);
     delete O;
     pa->output = nullptr;
 }
@@ -65,9 +60,7 @@ int enter(const char *who, snapgpu_paired_aligner_t *pa, bool argsOk, PairedOutp
     HIPCHK(hipSetDevice(pa->device));
     if (!pa->output) pa->output = new PairedOutput();
     *O = pa->output;
-    for (auto &e : (*O)->ev)
-        if (!e) HIPCHK(hipEventCreate(&e));
-    return SNAPGPU_OK;
+    return stageEvents(**O);
 }
 
 // The formatters' check of one end's batch (ids, the 1024-base limit, its own clip state) -> the
@@ -80,17 +73,6 @@ int checkEnd(const char *who, const snapgpu_reads_t *r, const uint32_t **front, 
     *front = *unclipped = nullptr;
     return snapgpu::samCheckClips(r, nullptr, front, unclipped);
 }
-
-// 16-byte aligned pieces of one packed upload
-struct Pack {
-    std::vector<char> &h;
-    uint64_t add(const void *p, uint64_t bytes) {
-        const uint64_t at = (h.size() + 15) & ~15ull;
-        h.resize(at + bytes);
-        if (bytes && p) memcpy(h.data() + at, p, bytes);   // null: zeros
-        return at;
-    }
-};
 
 // Upload what the line rule needs beside reads, records and CIGAR rows into O.aux and point A at
 // it: per end the ids, id offsets and lengths and the clip arrays (withExtents: the read offsets and
@@ -119,10 +101,8 @@ int samPrepare(snapgpu_paired_aligner_t *pa, PairedOutput &O, const snapgpu_read
         }
     O.textBound = bound;
     // an earlier call's upload may still read hAux, its kernels aux
-    if (O.textTimed) HIPCHK(hipEventSynchronize(O.ev[3]));
-    O.hAux.clear();
-    O.hAux.reserve(idBytes[0] + idBytes[1] + n * 64 + names.size() + nameOff.size() * 4 + rgLen + 1024);
-    Pack P{O.hAux};
+    if (O.launched) HIPCHK(hipEventSynchronize(O.ev[1]));
+    AuxPack P;
     uint64_t oIdOff[2], oIdLen[2], oFront[2] = {0, 0}, oFull[2] = {0, 0}, oOff[2] = {0, 0}, oLen[2] = {0, 0}, oIds[2];
     for (int e = 0; e < 2; e++) {
         oIdOff[e] = P.add(R[e]->idOffsets, n * 8);
@@ -133,7 +113,7 @@ int samPrepare(snapgpu_paired_aligner_t *pa, PairedOutput &O, const snapgpu_read
     }
     const uint64_t oNameOff = P.add(nameOff.data(), nameOff.size() * 4), oNames = P.add(names.data(), names.size()),
                    oRg = P.add(rg, rgLen);
-    P.add(nullptr, 16);
+    P.copyTo(O.hAux);
     HIPCHK(devGrow(a, O.aux, O.hAux.size()));
     HIPCHK(hipMemcpyAsync(O.aux.p, O.hAux.data(), O.hAux.size(), hipMemcpyHostToDevice, pa->stream));
     const char *d = (const char *)O.aux.p;
@@ -156,49 +136,21 @@ int samPrepare(snapgpu_paired_aligner_t *pa, PairedOutput &O, const snapgpu_read
 
 // Length pass, scan, write pass and check of the 2n records of n > 0 pairs on the aligner's stream.
 int samLaunch(snapgpu_paired_aligner_t *pa, PairedOutput &O, const samline::PairArgs &A, uint64_t n) {
-    snapgpu_aligner_t *a = pa->single;
-    const uint64_t recs = 2 * n;
-    if (recs > 0xffffffffull) { snapgpu::setError("batch too large"); return SNAPGPU_EINVAL; }
-    HIPCHK(devGrow(a, O.len, recs * 4));
-    HIPCHK(devGrow(a, O.scans, recs * sizeof(samline::Scans)));
-    HIPCHK(devGrow(a, O.start, (recs + 1) * 8));
-    HIPCHK(devGrow(a, O.sums, samgpu::scanTiles(recs) * 8));
-    HIPCHK(devGrow(a, O.bad, 16));
-    HIPCHK(devGrow(a, O.text, O.textBound + 16));
-    const samgpu::Buffers B{(uint32_t *)O.len.p, (samline::Scans *)O.scans.p, (uint64_t *)O.start.p, (uint64_t *)O.sums.p,
-                            (char *)O.text.p, O.textBound, (uint32_t *)O.bad.p, {nullptr, nullptr}};
-    HIPCHK(hipEventRecord(O.ev[2], pa->stream));
-    HIPCHK(sampairgpu::launch(A, recs, B, pa->stream));
-    HIPCHK(hipEventRecord(O.ev[3], pa->stream));
-    O.records = recs;
-    O.textTimed = true;
+    samgpu::Buffers B;
+    if (int rc = textBuffers(pa->single, O, 2 * n, &B)) return rc;
+    O.n = 2 * n;
+    HIPCHK(hipEventRecord(O.ev[0], pa->stream));
+    HIPCHK(sampairgpu::launch(A, 2 * n, B, pa->stream));
+    HIPCHK(hipEventRecord(O.ev[1], pa->stream));
+    O.launched = true;
     return SNAPGPU_OK;
 }
 
-// Wait for the SAM passes, check them, and copy the text to the caller's buffer.
+// Wait for the SAM passes, check them, and copy the text to the caller's buffer: the text is
+// complete, so the single-end aligner's pinned staging (and its idle side stream) carry it.
 int samDownload(snapgpu_paired_aligner_t *pa, PairedOutput &O, char *out, uint64_t cap, uint64_t *used) {
-    snapgpu_aligner_t *a = pa->single;
-    *used = 0;
-    O.downloadMs = 0;
-    if (int rc = waitEvent(a, O.ev[3])) return rc;
-    const auto t0 = std::chrono::steady_clock::now();
-    uint64_t total = 0;
-    uint32_t bad = 0;
-    HIPCHK(hipMemcpy(&total, (const uint64_t *)O.start.p + O.records, 8, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(&bad, O.bad.p, 4, hipMemcpyDeviceToHost));
-    if (bad || total > O.textBound) {
-        char msg[160];
-        snprintf(msg, sizeof msg, "paired sam: %u of %llu lines do not end where the scan placed them (text %llu bytes, bound %llu)",
-                 bad, (unsigned long long)O.records, (unsigned long long)total, (unsigned long long)O.textBound);
-        snapgpu::setError(msg);
-        return SNAPGPU_EDEVICE;
-    }
-    *used = total;
-    if (total > cap || (!out && total)) { snapgpu::setError("paired_sam_download: output buffer too small"); return SNAPGPU_EINVAL; }
-    // the text is complete: the single-end aligner's pinned staging (and its idle side stream) carry it
-    if (int rc = textDownload(a, (const char *)O.text.p, total, out)) return rc;
-    O.downloadMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    return SNAPGPU_OK;
+    return textFinish(pa->single, O, {"paired sam: %u of %llu lines do not end where the scan placed them (text %llu bytes, bound %llu)",
+                                      "paired_sam_download"}, out, cap, used);
 }
 
 }  // namespace
@@ -234,7 +186,7 @@ int snapgpu_paired_cigar_resident(snapgpu_paired_aligner_t *pa, const snapgpu_pa
     }
     HIPCHK(hipMemcpyAsync(O.res.p, results, n * sizeof(snapgpu_pair_result_t), hipMemcpyHostToDevice, st));
     HIPCHK(hipStreamSynchronize(st));
-    HIPCHK(hipEventRecord(O.ev[0], st));
+    HIPCHK(hipEventRecord(O.ev[O.kCigarEv], st));
     // one cigar_kernel launch per end, over that end's resident reads where they are; end e's
     // locations, directions and rows are entries e * n + q (the line rule reads them there)
     sampairgpu::cigarInputs((const snapgpu_pair_result_t *)O.res.p, n, (uint32_t *)O.cgLoc.p, (uint8_t *)O.cgDir.p, st);
@@ -245,7 +197,7 @@ int snapgpu_paired_cigar_resident(snapgpu_paired_aligner_t *pa, const snapgpu_pa
                                                    (uint32_t *)O.nOps.p + e * n,
                                                    (uint32_t *)O.ops.p + e * n * SNAPGPU_CIGAR_MAX_OPS))
             return rc;
-    HIPCHK(hipEventRecord(O.ev[1], st));
+    HIPCHK(hipEventRecord(O.ev[O.kCigarEv + 1], st));
     O.cigarsValid = O.cigarTimed = true;
     return SNAPGPU_OK;
 }
@@ -257,7 +209,7 @@ int snapgpu_paired_cigar_download(snapgpu_paired_aligner_t *pa, int32_t *editDis
         snapgpu::setError("paired_cigar_download: no snapgpu_paired_cigar_resident on the resident batch");
         return SNAPGPU_EINVAL;
     }
-    if (int rc = waitEvent(pa->single, O->ev[1])) return rc;
+    if (int rc = waitEvent(pa->single, O->ev[O->kCigarEv + 1])) return rc;
     // the device keeps each end's rows as a plane; the caller gets row 2q + e
     const uint64_t n = pa->residentN, recs = 2 * n;
     std::vector<uint32_t> h(recs * SNAPGPU_CIGAR_MAX_OPS);
@@ -327,12 +279,12 @@ int snapgpu_paired_sam_last_ms(snapgpu_paired_aligner_t *pa, double *cigarMs, do
     if (int rc = enter("paired_sam_last_ms", pa, cigarMs && kernelMs && downloadMs, &O)) return rc;
     float c = 0, k = 0;
     if (O->cigarTimed) {
-        HIPCHK(hipEventSynchronize(O->ev[1]));
-        HIPCHK(hipEventElapsedTime(&c, O->ev[0], O->ev[1]));
+        HIPCHK(hipEventSynchronize(O->ev[O->kCigarEv + 1]));
+        HIPCHK(hipEventElapsedTime(&c, O->ev[O->kCigarEv], O->ev[O->kCigarEv + 1]));
     }
-    if (O->textTimed) {
-        HIPCHK(hipEventSynchronize(O->ev[3]));
-        HIPCHK(hipEventElapsedTime(&k, O->ev[2], O->ev[3]));
+    if (O->launched) {
+        HIPCHK(hipEventSynchronize(O->ev[1]));
+        HIPCHK(hipEventElapsedTime(&k, O->ev[0], O->ev[1]));
     }
     *cigarMs = c;
     *kernelMs = k;

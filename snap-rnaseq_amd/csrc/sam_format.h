@@ -70,13 +70,16 @@ struct Wave {
     __device__ bool lead() const { return lane == 0; }
 };
 
-// The pieces of launch() that the BAM encoder (bam_format.hip) runs as well, queued on st.
+// The pieces of launch() that the paired SAM formatter (sam_pair_format.hip) and the BAM encoder
+// (bam_format.hip) run as well, queued on st.
 // sortStep: order fill, the stable radix sort of (S.key, record index) into S.order, and the gather
 // S.slotLen[j] = len[S.order[j]]; S.keys is not read (the caller's length pass stored S.key).
 // scanStarts: the exclusive 64-bit scan of n lengths into start[0 .. n], start[n] = their sum
 // (sums: scanTiles(n) entries of scratch).
+// checkLineEnds: *bad += the slots i < n that do not end in '\n' at start[i + 1] - 1, inside cap.
 hipError_t sortStep(const SortBuffers &S, const uint32_t *len, uint64_t n, hipStream_t st);
 void scanStarts(const uint32_t *len, uint64_t n, uint64_t *sums, uint64_t *start, hipStream_t st);
+void checkLineEnds(const uint64_t *start, uint64_t n, const char *out, uint64_t cap, uint32_t *bad, hipStream_t st);
 
 // Bytes of temporary storage the radix sort of n (key, record) pairs on st asks for.  A size query
 // on the host: nothing is launched and nothing is waited for.

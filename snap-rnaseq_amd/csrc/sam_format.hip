@@ -3,18 +3,20 @@
 // Three passes over n records whose reads, records and CIGAR ops are device resident:
 //   length  one wave per record computes the exact byte length of its line (sam_line.h);
 //   scan    exclusive scan of the lengths into 64-bit line starts, start[n] = bytes of text;
-//   write   one workgroup per kRecsPerGroup consecutive records.  Their lines are one contiguous
-//           byte range of the text: each wave composes its records' lines in an LDS window of that
-//           range (lanes copy id, SEQ and QUAL bytes in parallel, lane 0 prints the few numbers),
-//           then the workgroup flushes the window with 16-byte lane-contiguous stores (the range's
-//           unaligned head and tail bytewise).  Nothing is stored outside [start[first], start[end)).
+//   write   one workgroup per kRecsPerGroup consecutive records, their lines one contiguous byte range
+//           of the text: each wave composes its records' lines in an LDS window of that range (lanes
+//           copy id, SEQ and QUAL bytes in parallel, lane 0 prints the few numbers) and the workgroup
+//           flushes the window with 16-byte stores (staged_write.h).
 // A last kernel counts the lines that do not end in '\n' where the scan says they end.
+// The length and write kernels are line_passes.h's, instantiated for SamRule below; the scan, the
+// sort step and the end-of-line check are defined here and serve the paired SAM formatter
+// (sam_pair_format.hip) and the BAM encoder (bam_format.hip) as well.
 //
 // Coordinate-sorted output (-so) is the same passes over output slots: the length pass also stores
 // each record's sort key, a stable radix sort of (key, record index) gives order[slot] = record, the
 // scan runs over the lengths gathered in that order, and the write pass formats record order[j]
 // into slot j.  A workgroup still owns kRecsPerGroup consecutive slots, one contiguous byte range.
-#include "sam_format.h"
+#include "line_passes.h"
 
 #include <cstring>
 #include <rocprim/rocprim.hpp>
@@ -22,45 +24,26 @@
 namespace samgpu {
 
 using samline::Args;
-using samline::Fields;
 
 namespace {
 
-// What only the sorted instances of the length and write kernels take, as their last argument: the
-// unsorted instances get an empty one, and keep the arguments they had before there was a sorted
-// launch (and with them their registers and code).
-template <bool Sorted>
-struct KeyOut {};
-template <>
-struct KeyOut<true> {
-    samline::SortArgs tables;
-    uint32_t *key;   // [n] out: samline::sortKey per record
-};
-template <bool Sorted>
-struct SlotOrder {
-    __device__ uint64_t record(uint64_t j) const { return j; }
-};
-template <>
-struct SlotOrder<true> {
-    const uint32_t *order;   // [n] output slot -> record
-    __device__ uint64_t record(uint64_t j) const { return order[j]; }
-};
-
-// Sorted: key[r] = the record's coordinate-sort key as well
-template <bool Sorted>
-__global__ __launch_bounds__(256) void sam_length_kernel(Args A, uint64_t n, uint32_t *__restrict__ len,
-                                                         samline::Scans *__restrict__ scans, KeyOut<Sorted> K) {
-    const Wave g{nullptr, 0, 0, threadIdx.x & 63u};
-    const uint64_t waves = (uint64_t)gridDim.x * 4u;
-    for (uint64_t r = (uint64_t)blockIdx.x * 4u + threadIdx.x / 64u; r < n; r += waves) {
-        const Fields F = samline::fields(A, r, g);
-        if (g.lane == 0) {
-            len[r] = samline::lineLength(A, F);
-            scans[r] = samline::Scans{F.qlen, (uint16_t)F.seqLen, (uint16_t)F.qualLen};   // both <= kMaxSeq
-            if constexpr (Sorted) K.key[r] = samline::sortKey(K.tables, F);
-        }
+// The single-end SAM line rule (sam_line.h); its side is what the length pass scanned of the
+// record, which the write pass does not scan again.
+struct SamRule {
+    using Fields = samline::Fields;
+    using Side = samline::Scans;
+    using SortTables = samline::SortArgs;
+    Args A;
+    __device__ Fields fields(uint64_t r, const Wave &g) const { return samline::fields(A, r, g); }
+    __device__ uint32_t length(const Fields &F) const { return samline::lineLength(A, F); }
+    __device__ Side side(const Fields &F) const { return Side{F.qlen, (uint16_t)F.seqLen, (uint16_t)F.qualLen}; }   // both <= kMaxSeq
+    __device__ uint32_t sortKey(const SortTables &tables, const Fields &F) const { return samline::sortKey(tables, F); }
+    __device__ void write(uint64_t r, uint64_t s, const Side *scans, const Wave &g) const {
+        const samline::Scans known = scans[r];
+        const Fields F = samline::fields(A, r, g, &known);
+        samline::write(A, r, F, s, g);
     }
-}
+};
 
 // the sort's values before it runs: record j in slot j
 __global__ __launch_bounds__(256) void sam_iota_kernel(uint32_t *__restrict__ iota, uint64_t n) {
@@ -147,50 +130,10 @@ __global__ __launch_bounds__(256) void sam_scan_starts_kernel(const uint32_t *__
     }
 }
 
-// Sorted: start[] is over output slots and slot j prints record O.order[j] (scans[] stays per
-// record), else slot j prints record j.
-template <bool Sorted>
-__global__ __launch_bounds__(256) void sam_write_kernel(Args A, uint64_t n, const uint64_t *__restrict__ start,
-                                                        const samline::Scans *__restrict__ scans,
-                                                        char *__restrict__ out, uint64_t cap, SlotOrder<Sorted> O) {
-    __shared__ uint4 tile[kTileBytes / 16];
-    char *lds = reinterpret_cast<char *>(tile);
-    const uint64_t first = (uint64_t)blockIdx.x * kRecsPerGroup;
-    const uint64_t end = first + kRecsPerGroup < n ? first + kRecsPerGroup : n;
-    const uint64_t r0 = start[first], r1 = start[end];
-    if (r1 > cap) return;   // the host's bound on the text was too small: sam_check_kernel reports it
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x / 64u;
-    // windows are 16-byte aligned in the text, so an LDS chunk is a 16-byte aligned store
-    for (uint64_t w0 = r0 & ~15ull; w0 < r1; w0 += kTileBytes) {
-        const uint64_t w1 = w0 + kTileBytes < r1 ? w0 + kTileBytes : r1;
-        const Wave g{lds, w0, w1, lane};
-        for (uint64_t j = first + wave; j < end; j += 4) {
-            const uint64_t s = start[j], e = start[j + 1];
-            if (e <= w0 || s >= w1) continue;
-            const uint64_t r = O.record(j);
-            if (Sorted && r >= n) continue;   // not a record (never): the slot is empty, the check reports it
-            const samline::Scans known = scans[r];
-            const Fields F = samline::fields(A, r, g, &known);
-            samline::write(A, r, F, s, g);
-        }
-        __syncthreads();
-        const uint32_t chunks = (uint32_t)((w1 - w0 + 15) / 16);
-        for (uint32_t c = threadIdx.x; c < chunks; c += 256) {
-            const uint64_t a = w0 + 16ull * c;
-            if (a >= r0 && a + 16 <= r1) {
-                *reinterpret_cast<uint4 *>(out + a) = tile[c];
-            } else {
-                const uint64_t lo = a > r0 ? a : r0, hi = a + 16 < r1 ? a + 16 : r1;
-                for (uint64_t b = lo; b < hi; b++) out[b] = lds[b - w0];
-            }
-        }
-        __syncthreads();
-    }
-}
-
-__global__ __launch_bounds__(256) void sam_check_kernel(const uint64_t *__restrict__ start, uint64_t n,
-                                                        const char *__restrict__ out, uint64_t cap,
-                                                        uint32_t *bad) {
+// Slot i of the output ends in '\n' where the scan says it ends
+__global__ __launch_bounds__(256) void line_ends_check_kernel(const uint64_t *__restrict__ start, uint64_t n,
+                                                              const char *__restrict__ out, uint64_t cap,
+                                                              uint32_t *bad) {
     const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
     if (i >= n) return;
     const uint64_t s = start[i], e = start[i + 1];
@@ -213,12 +156,11 @@ hipError_t sortTempBytes(uint64_t n, hipStream_t st, size_t *bytes) {
 }
 
 hipError_t sortStep(const SortBuffers &S, const uint32_t *len, uint64_t n, hipStream_t st) {
-    const dim3 perItem((unsigned)((n + 255) / 256));
-    hipLaunchKernelGGL(sam_iota_kernel, perItem, dim3(256), 0, st, S.iota, n);
+    hipLaunchKernelGGL(sam_iota_kernel, perItem(n), dim3(256), 0, st, S.iota, n);
     size_t bytes = S.tempBytes;
     hipError_t e = sortPairs(S.temp, bytes, &S, n, st);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(sam_gather_len_kernel, perItem, dim3(256), 0, st, len, S.order, n, S.slotLen);
+    hipLaunchKernelGGL(sam_gather_len_kernel, perItem(n), dim3(256), 0, st, len, S.order, n, S.slotLen);
     return S.done ? hipEventRecord(S.done, st) : hipSuccess;
 }
 
@@ -229,16 +171,15 @@ void scanStarts(const uint32_t *len, uint64_t n, uint64_t *sums, uint64_t *start
     hipLaunchKernelGGL(sam_scan_starts_kernel, dim3((unsigned)nTiles), dim3(256), 0, st, len, n, sums, start);
 }
 
+void checkLineEnds(const uint64_t *start, uint64_t n, const char *out, uint64_t cap, uint32_t *bad, hipStream_t st) {
+    hipLaunchKernelGGL(line_ends_check_kernel, perItem(n), dim3(256), 0, st, start, n, out, cap, bad);
+}
+
 hipError_t launch(const Args &A, uint64_t n, const Buffers &B, hipStream_t st, const SortBuffers *S) {
-    hipError_t e = hipMemsetAsync(B.bad, 0, sizeof(uint32_t), st);
+    const SamRule R{A};
+    hipError_t e = S ? lengthPass(R, n, B.len, B.scans, B.bad, st, KeyOut<true, SamRule>{S->keys, S->key})
+                     : lengthPass(R, n, B.len, B.scans, B.bad, st, KeyOut<false, SamRule>{});
     if (e != hipSuccess) return e;
-    const uint64_t nGroups = (n + kRecsPerGroup - 1) / kRecsPerGroup;
-    const uint64_t lenBlocks = (n + 3) / 4 < 65536 ? (n + 3) / 4 : 65536;
-    const dim3 perItem((unsigned)((n + 255) / 256));
-    if (S) hipLaunchKernelGGL(sam_length_kernel<true>, dim3((unsigned)lenBlocks), dim3(256), 0, st, A, n, B.len, B.scans,
-                              KeyOut<true>{S->keys, S->key});
-    else hipLaunchKernelGGL(sam_length_kernel<false>, dim3((unsigned)lenBlocks), dim3(256), 0, st, A, n, B.len, B.scans,
-                            KeyOut<false>{});
     if (B.mid[0] && (e = hipEventRecord(B.mid[0], st)) != hipSuccess) return e;
     const uint32_t *len = B.len;
     if (S) {
@@ -247,11 +188,9 @@ hipError_t launch(const Args &A, uint64_t n, const Buffers &B, hipStream_t st, c
     }
     scanStarts(len, n, B.sums, B.start, st);
     if (B.mid[1] && (e = hipEventRecord(B.mid[1], st)) != hipSuccess) return e;
-    if (S) hipLaunchKernelGGL(sam_write_kernel<true>, dim3((unsigned)nGroups), dim3(256), 0, st, A, n, B.start, B.scans,
-                              B.text, B.textCap, SlotOrder<true>{S->order});
-    else hipLaunchKernelGGL(sam_write_kernel<false>, dim3((unsigned)nGroups), dim3(256), 0, st, A, n, B.start, B.scans,
-                            B.text, B.textCap, SlotOrder<false>{});
-    hipLaunchKernelGGL(sam_check_kernel, perItem, dim3(256), 0, st, B.start, n, B.text, B.textCap, B.bad);
+    if (S) writePass(R, n, B.start, B.scans, B.text, B.textCap, st, SlotOrder<true>{S->order});
+    else writePass(R, n, B.start, B.scans, B.text, B.textCap, st, SlotOrder<false>{});
+    checkLineEnds(B.start, n, B.text, B.textCap, B.bad, st);
     return hipGetLastError();
 }
 

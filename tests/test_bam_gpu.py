@@ -165,6 +165,30 @@ def test_no_ops_and_sixty_six_ops(aligner, idx, pieces):
     _same(aligner.bam_format(reads2, ids2, res2, cig2, read_group=None)[0], want2)
 
 
+def test_records_that_pass_the_lds_window(aligner, idx, pieces):
+    """40 reads of 500 bases with 200-byte ids: a workgroup's 32 records are some 32 KB, composed in
+    several 16 KiB windows, unsorted and sorted (mapped in descending order, both directions, some
+    unmapped that carry the NM before them; 1, 3 and 64 CIGAR ops)."""
+    n = 40
+    locs = [0xFFFFFFFF if i % 9 == 4 else pieces[1] + 50 + 3 * (n - i) for i in range(n)]
+    ids = [b"%03d" % i + b"w" * 197 for i in range(n)]
+    reads, ids, res, cig = made_up(locs, [500] * n, [i % 7 for i in range(n)], directions=[i & 1 for i in range(n)],
+                                   ids=ids, n_ops=[(1, 3, 64)[i % 3] for i in range(n)])
+    want, carry = snapgpu.bam_format(idx, reads, ids, res, cig, nm_carry=3)
+    recs = split_records(want)
+    assert len(recs) == n and all(fields(r)["lseq"] == 500 and len(fields(r)["name"]) == 200 for r in recs)
+    assert sum(len(r) for r in recs[:GROUP]) > 16384
+    got, got_carry = aligner.bam_format(reads, ids, res, cig, nm_carry=3)
+    _same(got, want)
+    assert got_carry == carry
+    order = np.zeros(n, dtype=np.uint32)
+    got, got_carry = aligner.bam_format(reads, ids, res, cig, nm_carry=3, sorted_output=True, order=order)
+    assert np.array_equal(order, _key_order(idx, res)) and not np.array_equal(order, np.arange(n))
+    assert sum(len(recs[int(i)]) for i in order[:GROUP]) > 16384
+    _same(got, permuted(want, order))
+    assert got_carry == carry
+
+
 # ------------------------------------------------------------------------ NM carry
 @pytest.fixture(scope="module")
 def carry_case(pieces):

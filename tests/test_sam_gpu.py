@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import snapgpu
+from bam_cases import made_up
 from oracle_ffi import oracle_align, oracle_cigars
 from sam_cases import (G, READ_GROUPS, cigars_from_pairs, clipped_case, fabricated_case, fastq, small_case,
                        small_index)
@@ -135,6 +136,29 @@ def test_batch_sizes(world, n):
     """Around the wave, the workgroup's records (SAM_RECORDS_PER_WORKGROUP) and the scan tile."""
     reads, ids, res, cig, want = _slice(world, n)
     assert world["aligner"].sam_format(reads, ids, res, cig) == want
+
+
+def test_records_that_pass_the_lds_window(aligner, idx):
+    """40 reads of 500 bases with 200-byte ids: a workgroup's 32 lines are some 40 KB of text, composed
+    in several 16 KiB windows, unsorted and sorted (mapped in descending order, both directions, some
+    unmapped; 1, 3 and 64 CIGAR ops)."""
+    n = 40
+    v = idx.view()
+    piece1 = int(C.cast(v.pieceOffsets, C.POINTER(C.c_uint32))[1])
+    locs = [0xFFFFFFFF if i % 9 == 4 else piece1 + 50 + 3 * (n - i) for i in range(n)]
+    ids = [b"%03d" % i + b"w" * 197 for i in range(n)]
+    reads, ids, res, cig = made_up(locs, [500] * n, [i % 7 for i in range(n)], directions=[i & 1 for i in range(n)],
+                                   ids=ids, n_ops=[(1, 3, 64)[i % 3] for i in range(n)])
+    want = snapgpu.sam_format(idx, reads, ids, res, cig)
+    lines = want.splitlines(keepends=True)
+    assert len(lines) == n and all(len(l.split(b"\t")[0]) == 200 and len(l.split(b"\t")[9]) == 500 for l in lines)
+    assert sum(len(l) for l in lines[:snapgpu.SAM_RECORDS_PER_WORKGROUP]) > 2 * 16384
+    assert aligner.sam_format(reads, ids, res, cig) == want
+    text, order = aligner.sam_format(reads, ids, res, cig, sorted_output=True, return_order=True)
+    assert np.array_equal(order, np.argsort(snapgpu.sam_sort_keys(idx, res), kind="stable"))
+    assert not np.array_equal(order, np.arange(n))
+    assert sum(len(lines[int(i)]) for i in order[:snapgpu.SAM_RECORDS_PER_WORKGROUP]) > 2 * 16384
+    assert text == b"".join(lines[int(i)] for i in order) == snapgpu.sam_sort_records(idx, want)
 
 
 def test_buffer_reuse_growing_then_shrinking(world):
