@@ -1127,6 +1127,70 @@ int snapgpu_sam_format_pairs_gpu(snapgpu_paired_aligner_t *pa, const snapgpu_ind
                                  const uint32_t *nOps, const uint32_t *ops, const char *readGroup, char *out,
                                  uint64_t cap, uint64_t *used);
 
+/* ------------------------------------------------------------ BAM records of read pairs
+ * The two uncompressed BAM records of every pair as the paired writer appends them
+ * (SimpleReadWriter::writePair over BAMFormat::writeRead with a mate, Bam.cpp:596-790), without
+ * transcriptome CIGARs: the arguments, the record order (record 2q + w is the w-th written end), the
+ * flags, the "/1" "/2" trim and the refusals of snapgpu_sam_format_pairs.  Where a record differs from
+ * the SAM line of the same end: the QNAME is the whole trimmed id (not cut at the first space), and
+ * an id of more than 254 bytes after the trim is refused (SNAPGPU_EINVAL); refID / next_refID are
+ * piece indices, an unmapped end takes its mate's refID / pos, next_refID / next_pos are the record's
+ * own where the mate is unmapped, all four are -1 with both unmapped; tlen is the SAM TLEN truncated
+ * to 32 bits; bin comes from the reference span of the ops (l_seq without ops), reg2bin(matePos - 1,
+ * matePos) for an unmapped end with a mapped mate, reg2bin(-1, 0) otherwise; SEQ and QUAL cover the
+ * whole unclipped read.  NM: an end with a location writes its own editDistance (also -1), an end
+ * without one repeats the NM of the record written before it, the first such records of a batch
+ * nmCarryIn (0 at the start of a run); *nmCarryOut (may be NULL) = the NM of the last record, the next
+ * batch's nmCarryIn.  No BGZF, no header (snapgpu_bam_header, snapgpu_bgzf_compress take the records).
+ * Size contract as snapgpu_bam_format.  The bytes do not depend on the host thread count. */
+int snapgpu_bam_format_pairs(const snapgpu_index_t *idx, const snapgpu_reads_t *reads0, const snapgpu_reads_t *reads1,
+                             const snapgpu_pair_result_t *results, const int32_t *editDistance, const uint32_t *nOps,
+                             const uint32_t *ops, const char *readGroup, int32_t nmCarryIn, int32_t *nmCarryOut,
+                             char *out, uint64_t cap, uint64_t *used);
+/* The byte size (block_size + 4) of each of the 2n records snapgpu_bam_format_pairs writes. */
+int snapgpu_bam_pair_record_lengths(const snapgpu_index_t *idx, const snapgpu_reads_t *reads0,
+                                    const snapgpu_reads_t *reads1, const snapgpu_pair_result_t *results,
+                                    const int32_t *editDistance, const uint32_t *nOps, const uint32_t *ops,
+                                    const char *readGroup, uint32_t *recordLengths);
+/* The coordinate-sort key of each of the 2n records of n pair results, in write order
+ * (BAMFormat::getSortInfo, Bam.cpp:474-495): the genome location of the record's own refID / pos where
+ * both are >= 0, else that of next_refID / next_pos by the same test, else UINT32_MAX.  The sorted device
+ * calls below write the records in the stable order of these keys. */
+int snapgpu_bam_pair_sort_keys(const snapgpu_index_t *idx, uint64_t n, const snapgpu_pair_result_t *results,
+                               uint32_t *keys);
+/* The same records encoded on the device from the resident pair batch, after
+ * snapgpu_paired_cigar_resident (see the SAM calls above; the same checks of the batches against the
+ * resident one, the same stream).  Only the ids, the clip arrays, the piece offsets and the read
+ * group are uploaded.  The _sorted form writes the records in coordinate order; the NM carry runs over
+ * write order in both (the reference's writer runs before its sort).  The records have their own
+ * output buffers: snapgpu_paired_sam_resident and snapgpu_paired_bam_resident on one batch do not
+ * disturb each other.  A new align call makes the records stale.
+ * snapgpu_paired_bam_download waits and copies the records out (size contract as
+ * snapgpu_bam_format; SNAPGPU_EDEVICE if a record's block_size is not the size the scan gave it);
+ * *nmCarryOut (may be NULL) = the NM of the last record in write order.
+ * snapgpu_paired_bam_order_download: order[j] = the write-order index (2q + w) of the j-th record of
+ * the sorted output, 2n entries; SNAPGPU_EINVAL unless the last resident call was the sorted one.
+ * snapgpu_paired_bam_last_ms: the encoder's kernels between HIP events and the download's wall time. */
+int snapgpu_paired_bam_resident(snapgpu_paired_aligner_t *pa, const snapgpu_reads_t *reads0,
+                                const snapgpu_reads_t *reads1, const char *readGroup, int32_t nmCarryIn);
+int snapgpu_paired_bam_resident_sorted(snapgpu_paired_aligner_t *pa, const snapgpu_reads_t *reads0,
+                                       const snapgpu_reads_t *reads1, const char *readGroup, int32_t nmCarryIn);
+int snapgpu_paired_bam_download(snapgpu_paired_aligner_t *pa, char *out, uint64_t cap, uint64_t *used,
+                                int32_t *nmCarryOut);
+int snapgpu_paired_bam_order_download(snapgpu_paired_aligner_t *pa, uint32_t *order);
+int snapgpu_paired_bam_last_ms(snapgpu_paired_aligner_t *pa, double *kernelMs, double *downloadMs);
+/* The batch form: snapgpu_bam_format_pairs's arguments (idx: the paired aligner's index, or NULL)
+ * uploaded, encoded by the same kernels and downloaded.  sorted != 0: in coordinate order, and order
+ * (may be NULL) receives the 2n write-order indices.  Byte-identical to snapgpu_bam_format_pairs (and
+ * its stable reorder by snapgpu_bam_pair_sort_keys).  It leaves the resident batch, its CIGAR rows and
+ * its SAM text alone; resident records have to be made again. */
+int snapgpu_bam_format_pairs_gpu(snapgpu_paired_aligner_t *pa, const snapgpu_index_t *idx,
+                                 const snapgpu_reads_t *reads0, const snapgpu_reads_t *reads1,
+                                 const snapgpu_pair_result_t *results, const int32_t *editDistance,
+                                 const uint32_t *nOps, const uint32_t *ops, const char *readGroup, int32_t nmCarryIn,
+                                 int32_t *nmCarryOut, char *out, uint64_t cap, uint64_t *used, int sorted,
+                                 uint32_t *order);
+
 /* ------------------------------------------- RNA seed census
  * BaseAligner::CharacterizeSeeds (BaseAligner.cpp:206-508) on the GPU: the seeds of AlignRead's
  * order until numSeeds directions applied (or the wrap runs out), every hit of a side that is

@@ -416,6 +416,9 @@ int stageEvents(StageState &S);
 // The text stage's buffers for n records (0 < n < 2^32) and S.textBound bytes of text, grown, into
 // *B (no mid events).
 int textBuffers(const snapgpu_aligner_t *a, SamState &S, uint64_t n, samgpu::Buffers *B);
+// The sort step's buffers of a sorted call over n records: S's, grown, into *SB (keys and done are
+// left to the caller).
+int sortBuffers(snapgpu_aligner_t *a, SamState &S, uint64_t n, samgpu::SortBuffers *SB);
 // What follows a text stage's kernels (S.ev[1] recorded behind them, S.n records): wait for them,
 // fetch start[n] and bad and compare them with S.textBound (SNAPGPU_EDEVICE, in W's words), *used =
 // the bytes, then copy them to out[0 .. cap) (textDownload; SNAPGPU_EINVAL when they do not fit).

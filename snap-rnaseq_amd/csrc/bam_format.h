@@ -26,4 +26,13 @@ struct Buffers {
 hipError_t launch(const samline::Args &A, uint64_t n, int32_t nmCarryIn, const Buffers &B, hipStream_t st,
                   const samgpu::SortBuffers *S = nullptr);
 
+// The pieces of launch() that the paired encoder (bam_pair_format.hip) runs as well, queued on st.
+// nmCarry: nm[i] of n values becomes its own value where that is not kNoNm, else the last such value
+// before it, else carryIn (nmTiles: scanTiles(n) entries of scratch).  Instantiated for
+// bamline::kNoNm and bampairline::kNoNm.
+// checkBlockSizes: *bad += the slots i < n whose block_size is not start[i + 1] - start[i] - 4, inside cap.
+template <int32_t kNoNm>
+void nmCarry(int32_t *nm, uint64_t n, int32_t *nmTiles, int32_t carryIn, hipStream_t st);
+void checkBlockSizes(const uint64_t *start, uint64_t n, const char *out, uint64_t cap, uint32_t *bad, hipStream_t st);
+
 }  // namespace bamgpu

@@ -14,14 +14,13 @@
 //           and the workgroup flushes the window with 16-byte stores (staged_write.h).
 // A last kernel counts the records whose block_size is not the size the scan gave them.
 // The length and write kernels are line_passes.h's, instantiated for BamRule below; the NM carry
-// passes and the block_size check are this file's own.
-#include "bam_format.h"
-
-#include "line_passes.h"
+// passes and the block_size check are this file's own, and the paired encoder (bam_pair_format.hip)
+// runs them too: bam_passes.h states the order of the passes once for both rules.
+#include "bam_passes.h"
+#include "bam_pair_line.h"
 
 namespace bamgpu {
 
-using bamline::kNoNm;
 using samgpu::kScanTile;
 using samgpu::Wave;
 using samline::Args;
@@ -47,34 +46,41 @@ struct BamRule {
 
 constexpr uint32_t kPerThread = kScanTile / 256;
 
+// The carry passes are templates over kNoNm, the rule's "no NM of its own" (bamline::kNoNm for reads
+// without mate, bampairline::kNoNm for pairs, where -1 is an NM).
+
 // the scan's operator: the later value where it is defined
+template <int32_t kNoNm>
 __device__ int32_t later(int32_t a, int32_t b) { return b != kNoNm ? b : a; }
 
 // inclusive "last defined value" scan of sh[0 .. 256) in place
+template <int32_t kNoNm>
 __device__ void lastDefined256(int32_t *sh) {
     for (uint32_t o = 1; o < 256; o <<= 1) {
         const int32_t t = threadIdx.x >= o ? sh[threadIdx.x - o] : kNoNm;
         __syncthreads();
-        sh[threadIdx.x] = later(t, sh[threadIdx.x]);
+        sh[threadIdx.x] = later<kNoNm>(t, sh[threadIdx.x]);
         __syncthreads();
     }
 }
 
 // tiles[b] = the last defined NM of tile b, or kNoNm
+template <int32_t kNoNm>
 __global__ __launch_bounds__(256) void bam_nm_tile_last_kernel(const int32_t *__restrict__ nm, uint64_t n,
                                                                int32_t *__restrict__ tiles) {
     __shared__ int32_t sh[256];
     const uint64_t base = (uint64_t)blockIdx.x * kScanTile + threadIdx.x * kPerThread;
     int32_t v = kNoNm;
     for (uint32_t j = 0; j < kPerThread; j++)
-        if (base + j < n) v = later(v, nm[base + j]);
+        if (base + j < n) v = later<kNoNm>(v, nm[base + j]);
     sh[threadIdx.x] = v;
     __syncthreads();
-    lastDefined256(sh);
+    lastDefined256<kNoNm>(sh);
     if (threadIdx.x == 255) tiles[blockIdx.x] = sh[255];
 }
 
 // one workgroup: tiles[b] becomes the NM that enters tile b (carryIn before the first defined value)
+template <int32_t kNoNm>
 __global__ __launch_bounds__(256) void bam_nm_tiles_kernel(int32_t *__restrict__ tiles, uint64_t nTiles, int32_t carryIn) {
     __shared__ int32_t sh[256];
     int32_t carry = carryIn;
@@ -82,7 +88,7 @@ __global__ __launch_bounds__(256) void bam_nm_tiles_kernel(int32_t *__restrict__
         const uint64_t i = b0 + threadIdx.x;
         sh[threadIdx.x] = i < nTiles ? tiles[i] : kNoNm;
         __syncthreads();
-        lastDefined256(sh);
+        lastDefined256<kNoNm>(sh);
         const int32_t before = threadIdx.x ? sh[threadIdx.x - 1] : kNoNm, last = sh[255];
         if (i < nTiles) tiles[i] = before != kNoNm ? before : carry;
         if (last != kNoNm) carry = last;
@@ -91,6 +97,7 @@ __global__ __launch_bounds__(256) void bam_nm_tiles_kernel(int32_t *__restrict__
 }
 
 // nm[i]: its own value, else the last defined one before it, else the value that enters its tile
+template <int32_t kNoNm>
 __global__ __launch_bounds__(256) void bam_nm_apply_kernel(int32_t *__restrict__ nm, uint64_t n,
                                                            const int32_t *__restrict__ tiles) {
     __shared__ int32_t sh[256];
@@ -99,11 +106,11 @@ __global__ __launch_bounds__(256) void bam_nm_apply_kernel(int32_t *__restrict__
     int32_t t = kNoNm;
     for (uint32_t j = 0; j < kPerThread; j++) {
         v[j] = base + j < n ? nm[base + j] : kNoNm;
-        t = later(t, v[j]);
+        t = later<kNoNm>(t, v[j]);
     }
     sh[threadIdx.x] = t;
     __syncthreads();
-    lastDefined256(sh);
+    lastDefined256<kNoNm>(sh);
     const int32_t before = threadIdx.x ? sh[threadIdx.x - 1] : kNoNm;
     int32_t cur = before != kNoNm ? before : tiles[blockIdx.x];
     for (uint32_t j = 0; j < kPerThread; j++) {
@@ -129,29 +136,24 @@ __global__ __launch_bounds__(256) void bam_check_kernel(const uint64_t *__restri
 
 }  // namespace
 
-hipError_t launch(const Args &A, uint64_t n, int32_t nmCarryIn, const Buffers &B, hipStream_t st,
-                  const samgpu::SortBuffers *S) {
-    using samgpu::KeyOut;
-    using samgpu::SlotOrder;
-    const BamRule R{A};
-    hipError_t e = S ? samgpu::lengthPass(R, n, B.len, B.nm, B.bad, st, KeyOut<true, BamRule>{{}, S->key})
-                     : samgpu::lengthPass(R, n, B.len, B.nm, B.bad, st, KeyOut<false, BamRule>{});
-    if (e != hipSuccess) return e;
+template <int32_t kNoNm>
+void nmCarry(int32_t *nm, uint64_t n, int32_t *nmTiles, int32_t carryIn, hipStream_t st) {
     const uint64_t nTiles = samgpu::scanTiles(n);
     const dim3 tiles((unsigned)nTiles);
-    hipLaunchKernelGGL(bam_nm_tile_last_kernel, tiles, dim3(256), 0, st, B.nm, n, B.nmTiles);
-    hipLaunchKernelGGL(bam_nm_tiles_kernel, dim3(1), dim3(256), 0, st, B.nmTiles, nTiles, nmCarryIn);
-    hipLaunchKernelGGL(bam_nm_apply_kernel, tiles, dim3(256), 0, st, B.nm, n, B.nmTiles);
-    const uint32_t *len = B.len;
-    if (S) {
-        if ((e = samgpu::sortStep(*S, B.len, n, st)) != hipSuccess) return e;
-        len = S->slotLen;
-    }
-    samgpu::scanStarts(len, n, B.sums, B.start, st);
-    if (S) samgpu::writePass(R, n, B.start, B.nm, B.out, B.outCap, st, SlotOrder<true>{S->order});
-    else samgpu::writePass(R, n, B.start, B.nm, B.out, B.outCap, st, SlotOrder<false>{});
-    hipLaunchKernelGGL(bam_check_kernel, samgpu::perItem(n), dim3(256), 0, st, B.start, n, B.out, B.outCap, B.bad);
-    return hipGetLastError();
+    hipLaunchKernelGGL(bam_nm_tile_last_kernel<kNoNm>, tiles, dim3(256), 0, st, nm, n, nmTiles);
+    hipLaunchKernelGGL(bam_nm_tiles_kernel<kNoNm>, dim3(1), dim3(256), 0, st, nmTiles, nTiles, carryIn);
+    hipLaunchKernelGGL(bam_nm_apply_kernel<kNoNm>, tiles, dim3(256), 0, st, nm, n, nmTiles);
+}
+template void nmCarry<bamline::kNoNm>(int32_t *, uint64_t, int32_t *, int32_t, hipStream_t);
+template void nmCarry<bampairline::kNoNm>(int32_t *, uint64_t, int32_t *, int32_t, hipStream_t);
+
+void checkBlockSizes(const uint64_t *start, uint64_t n, const char *out, uint64_t cap, uint32_t *bad, hipStream_t st) {
+    hipLaunchKernelGGL(bam_check_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, start, n, out, cap, bad);
+}
+
+hipError_t launch(const Args &A, uint64_t n, int32_t nmCarryIn, const Buffers &B, hipStream_t st,
+                  const samgpu::SortBuffers *S) {
+    return launchRule<bamline::kNoNm>(BamRule{A}, n, nmCarryIn, B, st, S);
 }
 
 }  // namespace bamgpu

@@ -136,7 +136,8 @@ SAM_HD Fields fields(const Args &A, uint64_t i, const G &g) {
 }
 
 // the tags after QUAL: RG:Z (with a read group), PG:Z:SNAP, NM:i
-SAM_HD uint32_t tagsLength(const Args &A) { return (A.rg ? 4 + A.rgLen : 0) + 8 + 7; }
+SAM_HD uint32_t tagsLength(const char *rg, uint32_t rgLen) { return (rg ? 4 + rgLen : 0) + 8 + 7; }
+SAM_HD uint32_t tagsLength(const Args &A) { return tagsLength(A.rg, A.rgLen); }
 
 // block_size + 4
 SAM_HD uint32_t recordLength(const Args &A, const Fields &F) {
@@ -152,6 +153,43 @@ template <class G>
 SAM_HD void put32(const G &g, uint64_t at, uint32_t v) {
     put16(g, at, v & 0xffff);
     put16(g, at + 2, v >> 16);
+}
+
+// SEQ and QUAL of the whole unclipped read B / Q of len bases at p, reverse-complemented / reversed
+// for RC.  SEQ: byte k holds bases 2k (high nibble) and 2k + 1; an odd tail has a zero low nibble.
+// QUAL: phred values.  (len + 1) / 2 + len bytes.
+template <class G>
+SAM_HD void seqQual(const char *B, const char *Q, uint32_t len, uint32_t rc, uint64_t p, const G &g) {
+    if (rc) {
+        g.copy(p, (len + 1) / 2, [=](uint32_t k) {
+            const uint32_t hi = seqCode(samline::complement(samline::upperCase(B[len - 1 - 2 * k])));
+            const uint32_t lo = 2 * k + 1 < len ? seqCode(samline::complement(samline::upperCase(B[len - 2 - 2 * k]))) : 0u;
+            return (char)(hi << 4 | lo);
+        });
+        g.copy(p + (len + 1) / 2, len, [=](uint32_t k) { return (char)(Q[len - 1 - k] - '!'); });
+    } else {
+        g.copy(p, (len + 1) / 2, [=](uint32_t k) {
+            const uint32_t hi = seqCode(samline::upperCase(B[2 * k]));
+            const uint32_t lo = 2 * k + 1 < len ? seqCode(samline::upperCase(B[2 * k + 1])) : 0u;
+            return (char)(hi << 4 | lo);
+        });
+        g.copy(p + (len + 1) / 2, len, [=](uint32_t k) { return (char)(Q[k] - '!'); });
+    }
+}
+
+// The tags at p: RG:Z (rg non-null), PG:Z:SNAP, NM:i = nm.  (rg ? 4 + rgLen : 0) + 15 bytes.
+template <class G>
+SAM_HD void tags(const char *rg, uint32_t rgLen, int32_t nm, uint64_t p, const G &g) {
+    if (rg) {
+        const char *tag = "RGZ";
+        g.copy(p, 3, [=](uint32_t k) { return tag[k]; });
+        g.copy(p + 3, rgLen, [=](uint32_t k) { return rg[k]; });
+        if (g.lead()) g.put(p + 3 + rgLen, '\0');
+        p += 4 + rgLen;
+    }
+    const char *tail = "PGZSNAP\0NMi";
+    g.copy(p, 11, [=](uint32_t k) { return tail[k]; });
+    if (g.lead()) put32(g, p + 11, (uint32_t)nm);
 }
 
 // The bytes of record i at output offset `at`: exactly recordLength(A, F) of them.  nm: the NM value
@@ -185,36 +223,9 @@ SAM_HD void write(const Args &A, uint64_t i, const Fields &F, int32_t nm, uint64
     const char *id = A.ids + A.idOffsets[i];
     g.copy(at + 36, F.qlen, [=](uint32_t k) { return id[k]; });
     p += 4 * F.nCigar;
-    // SEQ: byte k holds bases 2k (high nibble) and 2k + 1; an odd tail has a zero low nibble.  QUAL:
-    // phred values.  Both of the whole unclipped read, reverse-complemented / reversed for RC.
-    const uint32_t len = F.len;
-    const char *B = A.bases + F.readStart, *Q = A.quals + F.readStart;
-    if (F.rc) {
-        g.copy(p, (len + 1) / 2, [=](uint32_t k) {
-            const uint32_t hi = seqCode(samline::complement(samline::upperCase(B[len - 1 - 2 * k])));
-            const uint32_t lo = 2 * k + 1 < len ? seqCode(samline::complement(samline::upperCase(B[len - 2 - 2 * k]))) : 0u;
-            return (char)(hi << 4 | lo);
-        });
-        g.copy(p + (len + 1) / 2, len, [=](uint32_t k) { return (char)(Q[len - 1 - k] - '!'); });
-    } else {
-        g.copy(p, (len + 1) / 2, [=](uint32_t k) {
-            const uint32_t hi = seqCode(samline::upperCase(B[2 * k]));
-            const uint32_t lo = 2 * k + 1 < len ? seqCode(samline::upperCase(B[2 * k + 1])) : 0u;
-            return (char)(hi << 4 | lo);
-        });
-        g.copy(p + (len + 1) / 2, len, [=](uint32_t k) { return (char)(Q[k] - '!'); });
-    }
-    p += (len + 1) / 2 + len;
-    if (A.rg) {
-        const char *tag = "RGZ", *rg = A.rg;
-        g.copy(p, 3, [=](uint32_t k) { return tag[k]; });
-        g.copy(p + 3, A.rgLen, [=](uint32_t k) { return rg[k]; });
-        if (g.lead()) g.put(p + 3 + A.rgLen, '\0');
-        p += 4 + A.rgLen;
-    }
-    const char *tail = "PGZSNAP\0NMi";
-    g.copy(p, 11, [=](uint32_t k) { return tail[k]; });
-    if (g.lead()) put32(g, p + 11, (uint32_t)nm);
+    seqQual(A.bases + F.readStart, A.quals + F.readStart, F.len, F.rc, p, g);
+    p += (F.len + 1) / 2 + F.len;
+    tags(A.rg, A.rgLen, nm, p, g);
 }
 
 using samline::Serial;

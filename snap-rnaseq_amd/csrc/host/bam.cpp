@@ -11,9 +11,11 @@
 //
 // The public host encoder (snapgpu_bam_format, _record_lengths, _sort_keys, _header, snapgpu_bgzf_compress)
 // is at the end: records of reads without mate through bam_line.h, the code the device encoder
-// (bam_format.hip) compiles too.
+// (bam_format.hip) compiles too, and records of pairs (snapgpu_bam_format_pairs, _pair_record_lengths,
+// _pair_sort_keys) through bam_pair_line.h, which bam_pair_format.hip compiles.
 #include "internal.h"
 #include "bam_line.h"
+#include "bam_pair_line.h"
 
 #include <zlib.h>
 
@@ -463,6 +465,197 @@ extern "C" int snapgpu_bam_sort_keys(const snapgpu_index_t *idx, uint64_t n, con
         bamline::Fields F;
         bamline::locate(A, i, F);
         keys[i] = bamline::sortKey(A, F);
+    }
+    return SNAPGPU_OK;
+}
+
+// ------------------------------------------------------------------ pair batches (bam_pair_line.h)
+namespace {
+
+struct HostPairRecords {
+    samline::PairArgs A;
+    std::vector<uint32_t> nameOff;
+    std::string names;
+};
+
+// The arguments of snapgpu_sam_format_pairs as bam_pair_line.h takes them, checked as the SAM pair
+// formatter checks them, and every QNAME short enough for BAM.
+int hostPairRecordArgs(HostPairRecords &H, const char *who, const snapgpu_index_t *idx, const snapgpu_reads_t *reads0,
+                       const snapgpu_reads_t *reads1, const snapgpu_pair_result_t *results, const int32_t *editDistance,
+                       const uint32_t *nOps, const uint32_t *ops, const char *readGroup) {
+    if (int rc = samPairArgs(H.A, H.nameOff, H.names, who, idx, reads0, reads1, results, editDistance, nOps, ops, readGroup))
+        return rc;
+    return bamCheckPairIds(reads0, reads1);
+}
+
+}  // namespace
+
+namespace snapgpu {
+
+int bamCheckPairIds(const snapgpu_reads_t *reads0, const snapgpu_reads_t *reads1) {
+    samline::PairArgs A{};
+    const snapgpu_reads_t *R[2] = {reads0, reads1};
+    for (int e = 0; e < 2; e++) { A.ids[e] = R[e]->ids; A.idOffsets[e] = R[e]->idOffsets; A.idLengths[e] = R[e]->idLengths; }
+    for (uint64_t q = 0; q < reads0->n; q++)
+        for (uint32_t e = 0; e < 2; e++)
+            if (samline::pairIdLen(A, q, e) > bamline::kMaxQname) {
+                setError("bam_format: a read id is longer than 254 bytes (the BAM QNAME limit, Bam.cpp:723-726)");
+                return SNAPGPU_EINVAL;
+            }
+    return SNAPGPU_OK;
+}
+
+}  // namespace snapgpu
+
+extern "C" int snapgpu_bam_pair_record_lengths(const snapgpu_index_t *idx, const snapgpu_reads_t *reads0,
+                                               const snapgpu_reads_t *reads1, const snapgpu_pair_result_t *results,
+                                               const int32_t *editDistance, const uint32_t *nOps, const uint32_t *ops,
+                                               const char *readGroup, uint32_t *recordLengths) {
+    HostPairRecords H;
+    if (int rc = hostPairRecordArgs(H, "bam_pair_record_lengths", idx, reads0, reads1, results, editDistance, nOps, ops, readGroup))
+        return rc;
+    if (!recordLengths && reads0->n) {
+        setError("bam_pair_record_lengths: null argument");
+        return SNAPGPU_EINVAL;
+    }
+    const bampairline::Serial g{nullptr};
+    for (uint64_t j = 0; j < 2 * reads0->n; j++)
+        recordLengths[j] = bampairline::recordLength(H.A, bampairline::fields(H.A, j, g));
+    return SNAPGPU_OK;
+}
+
+extern "C" int snapgpu_bam_format_pairs(const snapgpu_index_t *idx, const snapgpu_reads_t *reads0,
+                                        const snapgpu_reads_t *reads1, const snapgpu_pair_result_t *results,
+                                        const int32_t *editDistance, const uint32_t *nOps, const uint32_t *ops,
+                                        const char *readGroup, int32_t nmCarryIn, int32_t *nmCarryOut, char *out,
+                                        uint64_t cap, uint64_t *used) {
+    if (!used) {
+        setError("bam_format_pairs: null argument");
+        return SNAPGPU_EINVAL;
+    }
+    *used = 0;
+    HostPairRecords H;
+    if (int rc = hostPairRecordArgs(H, "bam_format_pairs", idx, reads0, reads1, results, editDistance, nOps, ops, readGroup))
+        return rc;
+    const uint64_t recs = 2 * reads0->n;
+    // sizes and own NM values in parallel, starts and the NM carry on one thread in write order (the
+    // record order), then every thread writes its records in place
+    std::vector<uint64_t> start(recs + 1, 0);
+    std::vector<int32_t> nm(recs);
+    const bampairline::Serial none{nullptr};
+    parallelRanges(recs, 4096, [&](uint64_t a, uint64_t b) {
+        for (uint64_t j = a; j < b; j++) {
+            const bampairline::Fields F = bampairline::fields(H.A, j, none);
+            start[j + 1] = bampairline::recordLength(H.A, F);
+            nm[j] = F.nmOwn;
+        }
+    });
+    int32_t carry = nmCarryIn;
+    for (uint64_t j = 0; j < recs; j++) {
+        start[j + 1] += start[j];
+        if (nm[j] == bampairline::kNoNm) nm[j] = carry;
+        carry = nm[j];
+    }
+    if (nmCarryOut) *nmCarryOut = carry;
+    *used = start[recs];
+    if (start[recs] > cap || (!out && start[recs])) {
+        setError("bam_format_pairs: output buffer too small");
+        return SNAPGPU_EINVAL;
+    }
+    const bampairline::Serial g{out};
+    parallelRanges(recs, 4096, [&](uint64_t a, uint64_t b) {
+        for (uint64_t j = a; j < b; j++) bampairline::write(H.A, j, bampairline::fields(H.A, j, g), nm[j], start[j], g);
+    });
+    return SNAPGPU_OK;
+}
+
+// The same records through bamAppendRecord with SamLine::hasMate, the RNA paired path's encoder, on
+// one host thread: the NM pass and the SamLine as host/rna_paired.cpp's record loop has them (without
+// transcriptome CIGARs).  For tests that pin bam_pair_line.h to it.
+extern "C" int snapgpu_internal_bam_append_pair_records(const snapgpu_index_t *idx, const snapgpu_reads_t *reads0,
+                                                        const snapgpu_reads_t *reads1,
+                                                        const snapgpu_pair_result_t *results,
+                                                        const int32_t *editDistance, const uint32_t *nOps,
+                                                        const uint32_t *ops, const char *readGroup, int32_t nmCarryIn,
+                                                        int32_t *nmCarryOut, char *out, uint64_t cap, uint64_t *used) {
+    if (!used) return SNAPGPU_EINVAL;
+    *used = 0;
+    HostPairRecords H;
+    if (int rc = hostPairRecordArgs(H, "bam_append_pair_records", idx, reads0, reads1, results, editDistance, nOps, ops, readGroup))
+        return rc;
+    const samline::PairArgs &A = H.A;
+    std::string o;
+    int32_t lastNm = nmCarryIn;
+    for (uint64_t q = 0; q < reads0->n; q++) {
+        const snapgpu_pair_result_t &r = A.res[q];
+        uint32_t idLen[2] = {A.idLengths[0][q], A.idLengths[1][q]};
+        const char *id[2] = {A.ids[0] + A.idOffsets[0][q], A.ids[1] + A.idOffsets[1][q]};
+        if (idLen[0] == idLen[1] && idLen[0] > 2 && id[0][idLen[0] - 2] == '/' && id[1][idLen[0] - 2] == '/') {
+            const char c0 = id[0][idLen[0] - 1], c1 = id[1][idLen[1] - 1];
+            if ((c0 == '1' || c0 == '2') && (c0 == '1' || c1 == '2') && c0 != c1) { idLen[0] -= 2; idLen[1] -= 2; }
+        }
+        uint32_t locs[2];
+        for (int k = 0; k < 2; k++) locs[k] = r.status[k] != SNAPGPU_NOT_FOUND ? r.location[k] : kInvalidLocation;
+        const int first = locs[0] > locs[1], second = 1 - first;
+        for (int w = 0; w < 2; w++) {
+            const int k = w == 0 ? first : second, m = 1 - k;
+            SamLine L;
+            L.id = id[k];
+            L.idLen = A.idLengths[k][q];
+            L.qnameLen = idLen[k];
+            L.front = A.front[k] ? A.front[k][q] : 0u;
+            L.clippedLen = A.lengths[k][q];
+            L.fullLen = A.unclipped[k] ? A.unclipped[k][q] : L.clippedLen;
+            L.bases = A.bases[k] + A.offsets[k][q] - L.front;
+            L.quals = A.quals[k] + A.offsets[k][q] - L.front;
+            L.rg = A.rg;
+            L.result = r.status[k];
+            L.loc = locs[k];
+            L.dir = r.direction[k];
+            L.mapq = r.mapq[k];
+            L.ed = A.ed[2 * q + k];
+            L.ops = A.ops + (2 * q + k) * SNAPGPU_CIGAR_MAX_OPS;
+            L.nOps = A.nOps[2 * q + k];
+            L.hasMate = true;
+            L.firstInPair = w == 0;
+            L.mateLoc = locs[m];
+            L.mateDir = r.direction[m];
+            L.mateFront = A.front[m] ? A.front[m][q] : 0u;
+            L.mateClippedLen = A.lengths[m][q];
+            L.mateFullLen = A.unclipped[m] ? A.unclipped[m][q] : L.mateClippedLen;
+            if (locs[k] != kInvalidLocation) lastNm = L.ed;
+            if (!bamAppendRecord(o, *idx->genome, L, lastNm)) {
+                setError("bam_append_pair_records: record not written");
+                return SNAPGPU_EINVAL;
+            }
+        }
+    }
+    if (nmCarryOut) *nmCarryOut = lastNm;
+    *used = o.size();
+    if (o.size() > cap || !out) {
+        setError("bam_append_pair_records: output buffer too small");
+        return SNAPGPU_EINVAL;
+    }
+    memcpy(out, o.data(), o.size());
+    return SNAPGPU_OK;
+}
+
+extern "C" int snapgpu_bam_pair_sort_keys(const snapgpu_index_t *idx, uint64_t n, const snapgpu_pair_result_t *results,
+                                          uint32_t *keys) {
+    if (!idx || !idx->genome || ((!results || !keys) && n)) {
+        setError("bam_pair_sort_keys: null argument");
+        return SNAPGPU_EINVAL;
+    }
+    const Genome &g = *idx->genome;
+    samline::PairArgs A{};
+    A.res = results;
+    A.pieceOffsets = g.pieceOffsets.data();
+    A.nPieces = (int32_t)g.pieceOffsets.size();
+    for (uint64_t j = 0; j < 2 * n; j++) {
+        samline::PairFields P;
+        bampairline::Fields F;
+        bampairline::place(A, j, P, F);
+        keys[j] = bampairline::sortKey(A, F);
     }
     return SNAPGPU_OK;
 }

@@ -10,6 +10,9 @@
 namespace inflateblock {
 struct Member;   // inflate_block.h
 }
+namespace samline {
+struct PairArgs;   // sam_pair_line.h
+}
 
 namespace snapgpu {
 
@@ -167,6 +170,14 @@ std::string bamHeader(const Genome &g, const std::string &samText);
 bool bgzfWrite(FILE *f, const char *data, size_t n, bool eof);
 // the public encoder's id check (host and device forms): SNAPGPU_EINVAL for an id past the QNAME limit
 int bamCheckIds(const uint32_t *idLengths, uint64_t n);
+// ... of a pair batch with ids: the QNAMEs are the ids after writePair's "/1" "/2" trim
+int bamCheckPairIds(const snapgpu_reads_t *reads0, const snapgpu_reads_t *reads1);
+// sam.cpp: the pair formatters' input check (two batches of one length with ids, clip state within
+// the limits, 2n CIGAR rows) -> A over the host arrays, nameOff / names the genome's piece names
+int samPairArgs(samline::PairArgs &A, std::vector<uint32_t> &nameOff, std::string &names, const char *who,
+                const snapgpu_index_t *idx, const snapgpu_reads_t *reads0, const snapgpu_reads_t *reads1,
+                const snapgpu_pair_result_t *results, const int32_t *editDistance, const uint32_t *nOps,
+                const uint32_t *ops, const char *readGroup);
 
 // inflate.cpp: the member walk of a BGZF stream (header checks, BSIZE hops, ISIZE <= 65,536) -> the
 // members and the bytes they inflate to, or SNAPGPU_EFORMAT naming the member's index and byte

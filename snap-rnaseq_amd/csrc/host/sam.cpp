@@ -634,19 +634,14 @@ extern "C" int snapgpu_sam_sort_records(const snapgpu_index_t *idx, const char *
 }
 
 // ------------------------------------------------------------------ pair batches (sam_pair_line.h)
-namespace {
+namespace snapgpu {
 
-struct HostPairLines {
-    samline::PairArgs A;
-    std::vector<uint32_t> nameOff;
-    std::string names;
-};
-
-// The pair formatters' input check and their arguments as sam_pair_line.h takes them: the batches'
-// own ids and clip state, 2n CIGAR rows.
-int hostPairArgs(HostPairLines &H, const char *who, const snapgpu_index_t *idx, const snapgpu_reads_t *reads0,
-                 const snapgpu_reads_t *reads1, const snapgpu_pair_result_t *results, const int32_t *editDistance,
-                 const uint32_t *nOps, const uint32_t *ops, const char *readGroup) {
+// The pair formatters' input check (SAM and BAM) and their arguments as sam_pair_line.h takes them:
+// the batches' own ids and clip state, 2n CIGAR rows.
+int samPairArgs(samline::PairArgs &A, std::vector<uint32_t> &nameOff, std::string &names, const char *who,
+                const snapgpu_index_t *idx, const snapgpu_reads_t *reads0, const snapgpu_reads_t *reads1,
+                const snapgpu_pair_result_t *results, const int32_t *editDistance, const uint32_t *nOps,
+                const uint32_t *ops, const char *readGroup) {
     if (!idx || !idx->genome || !reads0 || !reads1) {
         setError(std::string(who) + ": null argument");
         return SNAPGPU_EINVAL;
@@ -662,8 +657,7 @@ int hostPairArgs(HostPairLines &H, const char *who, const snapgpu_index_t *idx, 
     }
     const snapgpu_reads_t *R[2] = {reads0, reads1};
     const Genome &g = *idx->genome;
-    samPieceNames(g, H.nameOff, H.names);
-    samline::PairArgs &A = H.A;
+    samPieceNames(g, nameOff, names);
     memset(&A, 0, sizeof(A));
     for (int e = 0; e < 2; e++) {
         if (n && (!R[e]->ids || !R[e]->idOffsets || !R[e]->idLengths)) {
@@ -686,12 +680,29 @@ int hostPairArgs(HostPairLines &H, const char *who, const snapgpu_index_t *idx, 
     A.ed = editDistance; A.nOps = nOps; A.ops = ops;
     A.rowPair = 2; A.rowEnd = 1;
     A.pieceOffsets = g.pieceOffsets.data();
-    A.pieceNameOff = H.nameOff.data();
-    A.pieceNames = H.names.data();
+    A.pieceNameOff = nameOff.data();
+    A.pieceNames = names.data();
     A.nPieces = (int32_t)g.pieceOffsets.size();
     A.rgLen = readGroup ? (uint32_t)strlen(readGroup) : 0u;
     A.rg = readGroup;
     return SNAPGPU_OK;
+}
+
+}  // namespace snapgpu
+
+namespace {
+
+struct HostPairLines {
+    samline::PairArgs A;
+    std::vector<uint32_t> nameOff;
+    std::string names;
+};
+
+// snapgpu::samPairArgs into H
+int hostPairArgs(HostPairLines &H, const char *who, const snapgpu_index_t *idx, const snapgpu_reads_t *reads0,
+                 const snapgpu_reads_t *reads1, const snapgpu_pair_result_t *results, const int32_t *editDistance,
+                 const uint32_t *nOps, const uint32_t *ops, const char *readGroup) {
+    return samPairArgs(H.A, H.nameOff, H.names, who, idx, reads0, reads1, results, editDistance, nOps, ops, readGroup);
 }
 
 // f(t, a, b) for thread t's records [a, b) of 2n, whole pairs each

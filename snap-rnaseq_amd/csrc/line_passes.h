@@ -1,6 +1,7 @@
 // line_passes.h -- the length pass and the write pass of the device formatters, stated once and
-// instantiated per line rule: single-end SAM (sam_format.hip), paired SAM (sam_pair_format.hip) and
-// BAM (bam_format.hip).  Device code and its launches: only .hip files include this.
+// instantiated per line rule: single-end SAM (sam_format.hip), paired SAM (sam_pair_format.hip), BAM
+// (bam_format.hip) and paired BAM (bam_pair_format.hip).  Device code and its launches: only .hip
+// files include this.
 //
 // A line rule is a small struct passed to the kernels by value.  It carries the rule's arguments
 // (samline::Args / PairArgs) and has

@@ -174,7 +174,7 @@ static int samPrepare(snapgpu_aligner_t *a, SamState &S, const SamHostIn &H, boo
 }
 
 // The sort step's buffers of a sorted call over n records: S's, grown, into SB.
-static int sortBuffers(snapgpu_aligner_t *a, SamState &S, uint64_t n, samgpu::SortBuffers *SB) {
+int sortBuffers(snapgpu_aligner_t *a, SamState &S, uint64_t n, samgpu::SortBuffers *SB) {
     HIPCHK(samgpu::sortTempBytes(n, a->sideStream, &SB->tempBytes));
     for (DevBuf *b : {&S.key, &S.keySorted, &S.iota, &S.order, &S.slotLen}) HIPCHK(devGrow(a, *b, n * 4));
     HIPCHK(devGrow(a, S.sortTemp, SB->tempBytes));

@@ -56,26 +56,28 @@ SAM_HD uint32_t pairEnd(const PairArgs &A, uint64_t j, uint32_t locs[2]) {
     return (j & 1) == 0 ? first : 1u - first;
 }
 
-template <class G>
-SAM_HD PairFields pairFields(const PairArgs &A, uint64_t j, const G &g, const Scans *known = nullptr) {
-    PairFields P;
+// What pairPlace() hands on beside the fields: the record's own and its mate's location (invalid
+// where NotFound), and whether both lie on one piece.
+struct PairPlace {
+    uint32_t loc, mateLoc;
+    bool onePiece;
+};
+
+// Where record j and its mate lie, from the pair record and the piece offsets alone: P.end, and of
+// F the strand, FLAG, MAPQ, the piece and POS (already with the mate's part), RNEXT and PNEXT
+// (getSAMData's hasMate branch, SAM.cpp:914-973).  The BAM pair rule (bam_pair_line.h) starts here too.
+SAM_HD PairPlace pairPlace(const PairArgs &A, uint64_t j, PairFields &P) {
     Fields &F = P.F;
-    const uint64_t q = j >> 1;
-    const snapgpu_pair_result_t &r = A.res[q];
+    const snapgpu_pair_result_t &r = A.res[j >> 1];
     uint32_t locs[2];
     const uint32_t e = pairEnd(A, j, locs), m = 1u - e;
     P.end = e;
-    const uint32_t front = A.front[e] ? A.front[e][q] : 0u;
-    const uint32_t clipped = A.lengths[e][q];
-    F.fullLen = A.unclipped[e] ? A.unclipped[e][q] : clipped;
-    F.readStart = A.offsets[e][q] - front;
     // getSAMData: NotFound -> unmapped, unmapped -> forward
     const uint32_t loc = locs[e], mateLoc = locs[m];
     F.rc = loc != kInvalid && r.direction[e] == SNAPGPU_RC;
     F.flags = 0;
     F.mapq = 0;
     F.piece = -1;
-    F.pieceLen = 1;
     F.pos = 0;
     int32_t pieceIdx = -1;
     if (loc != kInvalid) {
@@ -83,7 +85,6 @@ SAM_HD PairFields pairFields(const PairArgs &A, uint64_t j, const G &g, const Sc
         const int32_t p = pieceAt(A.pieceOffsets, A.nPieces, loc);
         if (p >= 0) {
             F.piece = pieceIdx = p;
-            F.pieceLen = A.pieceNameOff[p + 1] - A.pieceNameOff[p];
             F.pos = loc - A.pieceOffsets[p] + 1;
         }
         int32_t mq = r.mapq[e];
@@ -92,12 +93,10 @@ SAM_HD PairFields pairFields(const PairArgs &A, uint64_t j, const G &g, const Sc
     } else {
         F.flags |= 0x04;             // SAM_UNMAPPED
     }
-    // mate fields (SAM.cpp:914-973): RNEXT "=" unless both are mapped on different pieces, TLEN
-    // from the clipped-read extents
+    // mate fields (SAM.cpp:914-973): RNEXT "=" unless both are mapped on different pieces
     F.flags |= 0x01 | ((j & 1) == 0 ? 0x40 : 0x80);   // SAM_MULTI_SEGMENT, SAM_FIRST_SEGMENT / SAM_LAST_SEGMENT
     P.matePiece = -1;
     P.pnext = 0;
-    P.tlen = 0;
     int32_t mateIdx = -1;
     if (mateLoc != kInvalid) {
         const int32_t mp = pieceAt(A.pieceOffsets, A.nPieces, mateLoc);
@@ -108,7 +107,6 @@ SAM_HD PairFields pairFields(const PairArgs &A, uint64_t j, const G &g, const Sc
         if (r.direction[m] == SNAPGPU_RC) F.flags |= 0x20;   // SAM_NEXT_REVERSED
         if (loc == kInvalid) {       // the unmapped end takes the mate's RNAME / POS
             F.piece = mp >= 0 ? mp : -1;
-            F.pieceLen = mp >= 0 ? A.pieceNameOff[mp + 1] - A.pieceNameOff[mp] : 1u;
             pieceIdx = -2;           // never the mate's piece below
             P.matePiece = -2;
             F.pos = P.pnext;
@@ -118,11 +116,32 @@ SAM_HD PairFields pairFields(const PairArgs &A, uint64_t j, const G &g, const Sc
         P.matePiece = -2;
         P.pnext = F.pos;
     }
+    if (loc != kInvalid && mateLoc != kInvalid) F.flags |= 0x02;   // SAM_ALL_ALIGNED
+    const bool onePiece = pieceIdx >= 0 && pieceIdx == mateIdx;
+    if (onePiece) P.matePiece = -2;
+    return PairPlace{loc, mateLoc, onePiece};
+}
+
+// The piece index behind RNEXT: where P.matePiece says "=", the piece the record itself names.
+SAM_HD int32_t pairMateIndex(const PairFields &P) { return P.matePiece == -2 ? P.F.piece : P.matePiece; }
+
+// The unclipped read of the end pairPlace() chose, its soft clips as the strand mirrors them, and
+// TLEN from the clipped-read extents of both ends.
+SAM_HD void pairExtents(const PairArgs &A, uint64_t j, const PairPlace &L, PairFields &P) {
+    Fields &F = P.F;
+    const uint64_t q = j >> 1;
+    const snapgpu_pair_result_t &r = A.res[q];
+    const uint32_t e = P.end, m = 1u - e;
+    const uint32_t front = A.front[e] ? A.front[e][q] : 0u;
+    const uint32_t clipped = A.lengths[e][q];
+    F.fullLen = A.unclipped[e] ? A.unclipped[e][q] : clipped;
+    F.readStart = A.offsets[e][q] - front;
     const uint32_t back = F.fullLen - clipped - front;
     F.before = F.rc ? back : front;
     F.after = F.rc ? front : back;
-    if (loc != kInvalid && mateLoc != kInvalid) {
-        F.flags |= 0x02;             // SAM_ALL_ALIGNED
+    P.tlen = 0;
+    if (L.loc != kInvalid && L.mateLoc != kInvalid) {
+        const uint32_t loc = L.loc, mateLoc = L.mateLoc;
         const uint32_t mFront = A.front[m] ? A.front[m][q] : 0u, mClipped = A.lengths[m][q];
         const uint32_t mFull = A.unclipped[m] ? A.unclipped[m][q] : mClipped;
         const int64_t myStart = (int64_t)(uint32_t)(loc - F.before);
@@ -130,20 +149,35 @@ SAM_HD PairFields pairFields(const PairArgs &A, uint64_t j, const G &g, const Sc
         const int64_t mBefore = mFront, mAfter = (int64_t)mFull - mClipped - mFront;
         const int64_t mateStart = (int64_t)mateLoc - (r.direction[m] == SNAPGPU_RC ? mAfter : mBefore);
         const int64_t mateEnd = (int64_t)mateLoc + mClipped + (r.direction[m] == SNAPGPU_FORWARD ? mAfter : mBefore);
-        if (pieceIdx >= 0 && pieceIdx == mateIdx) P.tlen = myStart < mateStart ? mateEnd - myStart : -(myEnd - mateStart);
+        if (L.onePiece) P.tlen = myStart < mateStart ? mateEnd - myStart : -(myEnd - mateStart);
     }
-    if (pieceIdx >= 0 && pieceIdx == mateIdx) P.matePiece = -2;
-    P.mateLen = P.matePiece >= 0 ? A.pieceNameOff[P.matePiece + 1] - A.pieceNameOff[P.matePiece] : 1u;
-    // QNAME: writePair drops "/1" and "/2" from both ids (the condition as rna_paired.cpp has it),
-    // then the id ends at its first space
+}
+
+// Length of end e's id of pair q once writePair has dropped "/1" and "/2" from both ids (the
+// condition as rna_paired.cpp has it).
+SAM_HD uint32_t pairIdLen(const PairArgs &A, uint64_t q, uint32_t e) {
     uint32_t idLen[2] = {A.idLengths[0][q], A.idLengths[1][q]};
     const char *id0 = A.ids[0] + A.idOffsets[0][q], *id1 = A.ids[1] + A.idOffsets[1][q];
     if (idLen[0] == idLen[1] && idLen[0] > 2 && id0[idLen[0] - 2] == '/' && id1[idLen[0] - 2] == '/') {
         const char c0 = id0[idLen[0] - 1], c1 = id1[idLen[1] - 1];
         if ((c0 == '1' || c0 == '2') && (c0 == '1' || c1 == '2') && c0 != c1) { idLen[0] -= 2; idLen[1] -= 2; }
     }
-    P.idLen = idLen[e];
-    const char *id = e ? id1 : id0;
+    return idLen[e];
+}
+
+template <class G>
+SAM_HD PairFields pairFields(const PairArgs &A, uint64_t j, const G &g, const Scans *known = nullptr) {
+    PairFields P;
+    Fields &F = P.F;
+    const uint64_t q = j >> 1;
+    const PairPlace L = pairPlace(A, j, P);
+    pairExtents(A, j, L, P);
+    const uint32_t e = P.end, loc = L.loc;
+    F.pieceLen = F.piece >= 0 ? A.pieceNameOff[F.piece + 1] - A.pieceNameOff[F.piece] : 1u;
+    P.mateLen = P.matePiece >= 0 ? A.pieceNameOff[P.matePiece + 1] - A.pieceNameOff[P.matePiece] : 1u;
+    // QNAME: the trimmed id ends at its first space
+    P.idLen = pairIdLen(A, q, e);
+    const char *id = A.ids[e] + A.idOffsets[e][q];
     const uint32_t idN = P.idLen;
     F.qlen = known ? known->qlen : g.firstOf(idN, [=](uint32_t k) { return id[k] == ' '; });
     // CIGAR and NM only at a location (the paired writer passes the invalid one for NotFound)

@@ -830,6 +830,69 @@ class PairedAligner:
         _check(lib().snapgpu_paired_sam_last_ms(self._h, *[C.byref(x) for x in v]), "paired_sam_last_ms")
         return tuple(x.value for x in v)
 
+    def run_bam(self, reads0, reads1, read_group="FASTQ", sorted_output=False, nm_carry=0):
+        """BAM records of the resident batch, its uploaded records and the CIGARs run_cigars() left in
+        HBM, encoded on the GPU (asynchronous).  reads0 / reads1: as run_sam(); sorted_output: the
+        records in coordinate order, bam_order() then gives that order; nm_carry: the NM that ends
+        without location repeat until the first end with one (the previous batch's bam_nm_carry())."""
+        rg = None if read_group is None else (read_group.encode() if isinstance(read_group, str) else bytes(read_group))
+        fn = lib().snapgpu_paired_bam_resident_sorted if sorted_output else lib().snapgpu_paired_bam_resident
+        _check(fn(self._h, reads0._p, reads1._p, rg, int(nm_carry)), "paired_bam_resident")
+        self._bam_carry = None
+
+    def bam(self, timing=None):
+        """The records run_bam() wrote -> bytes (waits).  timing: as sam()."""
+        used, carry = C.c_uint64(), C.c_int32()
+        fn = lib().snapgpu_paired_bam_download
+        rc = fn(self._h, None, 0, C.byref(used), C.byref(carry))
+        if rc != 0 and used.value == 0:
+            _check(rc, "paired_bam_download")
+        buf = np.empty(max(1, used.value), dtype=np.uint8)
+        _check(fn(self._h, buf.ctypes.data, used.value, C.byref(used), C.byref(carry)), "paired_bam_download")
+        if timing is not None:
+            timing["done"] = time.perf_counter()
+        self._bam_carry = carry.value
+        return buf[:used.value].tobytes()
+
+    def bam_nm_carry(self):
+        """The NM carry-out of the last run_bam() (waits): the nm_carry of the next batch."""
+        if getattr(self, "_bam_carry", None) is None:
+            used, carry = C.c_uint64(), C.c_int32()
+            rc = lib().snapgpu_paired_bam_download(self._h, None, 0, C.byref(used), C.byref(carry))
+            if rc != 0 and used.value == 0:
+                _check(rc, "paired_bam_download")
+            self._bam_carry = carry.value
+        return self._bam_carry
+
+    def bam_order(self):
+        """The output order of the last run_bam(sorted_output=True) -> uint32[2n] (waits): order[j] is
+        the write-order index 2q + w of the j-th record."""
+        n = 2 * self.resident_pairs()
+        order = np.zeros(max(1, n), dtype=np.uint32)
+        _check(lib().snapgpu_paired_bam_order_download(self._h, order.ctypes.data), "paired_bam_order_download")
+        return order[:n]
+
+    def bam_format(self, reads0, reads1, results, cigars, read_group="FASTQ", nm_carry=0, sorted_output=False,
+                   order=None):
+        """The module-level bam_format_pairs on the GPU (snapgpu_bam_format_pairs_gpu: uploads reads,
+        records and CIGARs, runs the resident path's kernels, downloads the records) -> (bytes, NM
+        carry-out).  sorted_output: the records in coordinate order (the stable order of
+        bam_pair_sort_keys); order: a uint32[2n] array that then receives that order."""
+        if order is not None and not sorted_output:
+            raise ValueError("order needs sorted_output")
+        if order is not None and (order.dtype != np.uint32 or order.shape != (2 * reads0.n,) or not order.flags.c_contiguous):
+            raise ValueError("order must be a contiguous uint32 array with two entries per pair")
+        args, keep, cap = _pair_inputs(self.index, reads0, reads1, results, cigars, read_group)
+        tail = [int(sorted_output), order.ctypes.data if order is not None and reads0.n else None]
+        return _carry_call(lambda *a: lib().snapgpu_bam_format_pairs_gpu(self._h, *a), args, nm_carry, cap,
+                           "bam_format_pairs_gpu", tail)
+
+    def bam_ms(self):
+        """(encoder kernel ms, download ms) of the last resident BAM calls (snapgpu_paired_bam_last_ms)."""
+        k, d = C.c_double(), C.c_double()
+        _check(lib().snapgpu_paired_bam_last_ms(self._h, C.byref(k), C.byref(d)), "paired_bam_last_ms")
+        return k.value, d.value
+
     def __del__(self):
         if getattr(self, "_h", None):
             lib().snapgpu_paired_aligner_free(self._h)
@@ -1317,6 +1380,63 @@ def _pair_cigars(aligner, reads0, reads1, results, useM=False):
         k = aligner.Cigars(r, loc[e::2], dr[e::2], useM=useM)
         c.editDistance[e::2], c.nOps[e::2], c.ops[e::2] = k.editDistance, k.nOps, k.ops
     return c
+
+
+def _carry_call(fn, args, nm_carry, cap, what, tail=()):
+    """fn(*args, nm_carry, &carry, out, cap, &used, *tail) under the encoders' size contract ->
+    (bytes, NM carry-out)."""
+    used, carry = C.c_uint64(), C.c_int32()
+    buf = np.empty(max(1, cap), dtype=np.uint8)
+    rc = fn(*args, int(nm_carry), C.byref(carry), buf.ctypes.data, cap, C.byref(used), *tail)
+    if rc != 0 and used.value > cap:
+        cap = used.value
+        buf = np.empty(cap, dtype=np.uint8)
+        rc = fn(*args, int(nm_carry), C.byref(carry), buf.ctypes.data, cap, C.byref(used), *tail)
+    _check(rc, what)
+    return buf[:used.value].tobytes(), carry.value
+
+
+def bam_format_pairs(index, reads0, reads1, results, cigars, read_group="FASTQ", nm_carry=0, timing=None):
+    """The two uncompressed BAM records of every pair (snapgpu_bam_format_pairs:
+    SimpleReadWriter::writePair over BAMFormat::writeRead with a mate), in write order -> (bytes, NM
+    carry-out).  Arguments as sam_format_pairs; nm_carry: the NM that ends without location repeat
+    until the first end with one.  timing: a dict that receives "format_s"."""
+    args, keep, cap = _pair_inputs(index, reads0, reads1, results, cigars, read_group)
+    t0 = time.perf_counter()
+    out = _carry_call(lib().snapgpu_bam_format_pairs, args, nm_carry, cap, "bam_format_pairs")
+    if timing is not None:
+        timing["format_s"] = time.perf_counter() - t0
+    return out
+
+
+def _bam_append_pair_records(index, reads0, reads1, results, cigars, read_group="FASTQ", nm_carry=0):
+    """bam_format_pairs' records through the RNA paired path's own encoder (bamAppendRecord with a
+    mate, csrc/host/bam.cpp) on one host thread -> (bytes, NM carry-out) (tests)."""
+    args, keep, cap = _pair_inputs(index, reads0, reads1, results, cigars, read_group)
+    fn = lib().snapgpu_internal_bam_append_pair_records
+    fn.restype = C.c_int
+    fn.argtypes = _ffi._PAIR_RECORDS
+    return _carry_call(fn, args, nm_carry, cap, "bam_append_pair_records")
+
+
+def bam_pair_record_lengths(index, reads0, reads1, results, cigars, read_group="FASTQ"):
+    """Byte size of each of the 2n records bam_format_pairs writes, block_size + 4 -> np.uint32 array."""
+    args, keep, _ = _pair_inputs(index, reads0, reads1, results, cigars, read_group)
+    out = np.zeros(max(1, 2 * reads0.n), dtype=np.uint32)
+    _check(lib().snapgpu_bam_pair_record_lengths(*args, out.ctypes.data), "bam_pair_record_lengths")
+    return out[:2 * reads0.n]
+
+
+def bam_pair_sort_keys(index, results):
+    """The coordinate-sort key of each of the 2n records of pair results, in write order
+    (snapgpu_bam_pair_sort_keys: BAMFormat::getSortInfo, by piece index) -> np.uint32 array.
+    np.argsort(keys, kind="stable") is the order of the sorted device calls."""
+    res = np.ascontiguousarray(results, dtype=PAIR_RESULT_DTYPE)
+    n = len(res)
+    out = np.zeros(max(1, 2 * n), dtype=np.uint32)
+    src = res if n else np.zeros(1, dtype=PAIR_RESULT_DTYPE)
+    _check(lib().snapgpu_bam_pair_sort_keys(index._h, n, src.ctypes.data, out.ctypes.data), "bam_pair_sort_keys")
+    return out[:2 * n]
 
 
 def sam_sort_keys(index, results):

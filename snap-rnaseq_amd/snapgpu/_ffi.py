@@ -492,6 +492,20 @@ _PROTOS += [
     ("snapgpu_sam_format_pairs_gpu", C.c_int, [C.c_void_p] + _PAIR_LINES + [C.c_void_p, C.c_uint64,
                                                                             C.POINTER(C.c_uint64)]),
 ]
+_PAIR_RECORDS = _PAIR_LINES + [C.c_int32, C.POINTER(C.c_int32), C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+_PROTOS += [
+    ("snapgpu_bam_format_pairs", C.c_int, _PAIR_RECORDS),
+    ("snapgpu_bam_pair_record_lengths", C.c_int, _PAIR_LINES + [C.c_void_p]),
+    ("snapgpu_bam_pair_sort_keys", C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
+    ("snapgpu_paired_bam_resident", C.c_int, [C.c_void_p, C.POINTER(Reads), C.POINTER(Reads), C.c_char_p, C.c_int32]),
+    ("snapgpu_paired_bam_resident_sorted", C.c_int, [C.c_void_p, C.POINTER(Reads), C.POINTER(Reads), C.c_char_p,
+                                                     C.c_int32]),
+    ("snapgpu_paired_bam_download", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64),
+                                              C.POINTER(C.c_int32)]),
+    ("snapgpu_paired_bam_order_download", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("snapgpu_paired_bam_last_ms", C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    ("snapgpu_bam_format_pairs_gpu", C.c_int, [C.c_void_p] + _PAIR_RECORDS + [C.c_int, C.c_void_p]),
+]
 
 CIGAR_MAX_OPS = 64   # SNAPGPU_CIGAR_MAX_OPS
 
